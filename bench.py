@@ -17,7 +17,8 @@ Inputs are resident in HBM when the timed region starts.  N > 1: every rank scor
 Prints ONE JSON line (rank 0).  `roofline` describes the kernel with the largest share of the step,
 timed with HIP events on its launch stream inside the timed region; `kernels` lists every kernel of
 the step from a profiled warm-up step; `cpu_baseline` is the CPU oracle (the reference algorithm as
-written, torch-CPU fp32) on a bounded sample.
+written, torch-CPU fp32) on a bounded sample.  `--dump-outputs DIR` also writes what the last timed step returned
+(every input is seeded: the same arguments give the same inputs, so two builds compare output for output).
 """
 import argparse
 import json
@@ -102,7 +103,12 @@ def parse():
                          "1 = one batch at a time on one stream.  A sharded store keeps 1 (the exchange's collectives stay on one stream)")
     ap.add_argument("--force-exchange", action="store_true",
                     help="run the sharded-store exchange even with one rank (exercises the RCCL path on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB in all: per-token vectors whole, a fixed seeded sample of the rows of the [tokens, x] matrices")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
     if args.blocks is None:
         args.blocks = 128 if args.layers == 1 else 16
     return args
@@ -1021,6 +1027,48 @@ def launch_ranks(args):
 _T0 = time.perf_counter()
 
 
+DUMP_BYTES = 64_000_000          # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: the arrays the timed path returned for its last step -- the dicts of GnnLmEngine.score of the step's
+    sub-batches, joined in token order -- as `path`/<name>.npy: float32, float64 for integer and float64 outputs (exact).
+    Per-token vectors are written whole; of the [tokens, x] matrices (gcn_feat, knn_*) the same rows of a permutation seeded
+    with 0, as many as the budget leaves, in token order (their indices: rows.npy).  Should the vectors alone take more than
+    half the budget, they are sampled the same way (vector_rows.npy).  Same arguments, same inputs, same files."""
+    arrays = {k: (torch.cat([o[k] for o in outs]) if len(outs) > 1 else outs[0][k]) for k in outs[0]}
+    n = arrays["logp"].shape[0]
+    wide = lambda t: t.dtype == torch.float64 or not t.is_floating_point()
+    row_bytes = lambda ts: sum(t[0].numel() * (8 if wide(t) else 4) for t in ts)
+    vec = {k: t for k, t in arrays.items() if t.dim() == 1}
+    mat = {k: t for k, t in arrays.items() if t.dim() > 1}
+    perm = np.random.RandomState(0).permutation(n)
+    header = 128                                                  # (numpy's .npy header of these arrays)
+    left = DUMP_BYTES - header * (len(arrays) + 2)
+    n_vec = n if n * row_bytes(vec.values()) <= left // 2 else (left // 2) // (row_bytes(vec.values()) + 8)
+    left -= n_vec * row_bytes(vec.values()) + (n_vec * 8 if n_vec < n else 0)
+    n_mat = min(n, left // (row_bytes(mat.values()) + 8)) if mat else 0
+    files = {}
+    pick = lambda m: torch.from_numpy(np.sort(perm[:m])).to(arrays["logp"].device)
+    if n_vec < n:
+        files["vector_rows"] = pick(n_vec)
+    for k, t in vec.items():
+        files[k] = t if n_vec == n else t[files["vector_rows"]]
+    if mat:
+        files["rows"] = pick(n_mat)
+        for k, t in mat.items():
+            files[k] = t[files["rows"]]
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for k, t in files.items():
+        a = (t.double() if wide(t) else t.float()).cpu().numpy()
+        f = os.path.join(path, k + ".npy")
+        np.save(f, a)
+        total += os.path.getsize(f)
+    assert total <= DUMP_BYTES, f"--dump-outputs: {total} bytes"
+    return {"dir": path, "bytes": total, "tokens": n, "matrix_rows": n_mat, "vector_rows": n_vec, "files": sorted(files)}
+
+
 def stage(name):
     """Progress on stderr (rank 0's JSON line owns stdout): which leg of the run a crash or a time-out belongs to."""
     print(f"[bench.py {time.perf_counter() - _T0:7.1f} s] {name}", file=sys.stderr, flush=True)
@@ -1140,6 +1188,10 @@ def main():
         compute_stream.wait_stream(torch.cuda.current_stream())
         torch.cuda.set_stream(compute_stream)
     pending = {}
+    # --dump-outputs: the last timed step's result dicts (one per sub-batch), kept by reference only -- nothing is copied in the
+    # timed region
+    keep_last = args.dump_outputs is not None and rank == 0
+    last_outs, last_lane = [], [None]
 
     n_fetches = [0]
 
@@ -1168,7 +1220,7 @@ def main():
         b.fetched_centres_only = centres_only
         return b
 
-    def score_one(bi, a, prefetch_next):
+    def score_one(bi, a, prefetch_next, keep=False):
         b = batches[bi % len(batches)]
         if fetch_in_step:
             n_fetches[0] += 1
@@ -1177,6 +1229,8 @@ def main():
         elif fetcher is not None:
             b = take_fetched(bi)
         out = eng.score(b, args.lmbda, args.temperature, knn_index=idx, k=args.k)
+        if keep:
+            last_outs.append(out)
         ops.masked_sum_f64(out["logp"], None, a)                  # score_sum (eval_lm.py:273)
         if fetch_in_step and len(merged_counts) < 64:
             merged_counts.append(eng.hgt._last_groups)            # (n, device counter) -- read after the run
@@ -1197,6 +1251,9 @@ def main():
                 out = eng.score_finish(lane_pending[j])
                 ops.masked_sum_f64(out["logp"], None, lane_accs[j])
             lane_pending[j] = None
+            if last_lane[0] == j:
+                last_outs.append(out)
+                last_lane[0] = None
 
     def drain_lanes():
         for j in range(n_lanes):
@@ -1212,6 +1269,8 @@ def main():
                 else:
                     b = batches[i % len(batches)]
                 lane_pending[j] = eng.score_begin(b, args.lmbda, args.temperature, knn_index=idx, k=args.k)
+            if last and keep_last:
+                last_lane[0] = j
             if fetcher is not None and not last:
                 issue_fetch(i + 1)                                    # the next batch's rows: requested now, on the fetch stream
             return
@@ -1220,11 +1279,11 @@ def main():
             bi = i * args.streams + s_i
             nxt = None if (last or args.streams > 1) else bi + 1
             if s_i == 0:
-                score_one(bi, accs[0], nxt)
+                score_one(bi, accs[0], nxt, keep=last and keep_last)
             else:
                 side[s_i - 1].wait_stream(main) if i == 0 else None
                 with torch.cuda.stream(side[s_i - 1]):
-                    score_one(bi, accs[s_i], None)
+                    score_one(bi, accs[s_i], None, keep=last and keep_last)
 
     def barrier():
         drain_lanes()                                             # (batches still in flight on the lanes belong to the steps before the barrier)
@@ -1233,7 +1292,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    graphs = {}
+    graphs, graph_outs = {}, {}
 
     def capture_graphs():
         """One HIP graph per pooled batch: the ~45 launches of a step (all stream-ordered, device-side row
@@ -1245,6 +1304,8 @@ def main():
                 out = eng.score(batches[bi], args.lmbda, args.temperature)
                 ops.masked_sum_f64(out["logp"], None, acc)
             graphs[bi] = gph
+            if keep_last:
+                graph_outs[bi] = out                              # (the graph's own memory: rewritten by every replay)
 
     # ---- parity gate FIRST (7 s of CPU-only oracle with the GPU idle: nothing timed may follow it closely): the engine that is
     # about to be timed against the oracle on a prefix of its first block
@@ -1354,6 +1415,13 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         prof = _lib.profile_end()[dominant]
+    if keep_last:
+        if args.graph:
+            last_outs.append(graph_outs[(args.steps - 1) % len(batches)])
+        dumped = dump_outputs(args.dump_outputs, last_outs)
+        stage(f"outputs of the last timed step: {dumped}")
+        last_outs.clear()
+        graph_outs.clear()
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)) if args.streams == 1 and n_lanes == 1 else []
     for a in accs[1:] + lane_accs[1:]:
         acc += a

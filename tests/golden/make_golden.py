@@ -1,12 +1,11 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ by RUNNING THE REFERENCE ITSELF.
 
-Run in the authoring container only (needs /root/reference; the GPU box has neither the
-reference nor this need):
+Needs a source tree of the reference (the tests only read the stored vectors, never the reference):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py <reference source tree>
 
-What is executed from /root/reference (nothing of it is copied into this repo):
+What is executed from the reference tree (nothing of it is copied into this repo):
   * knn/data_store.py                    imported as is
   * knn/pq_wrapper.py, knn/knn_model.py  imported with an EMPTY ``faiss`` module pre-seeded in
                                          sys.modules (faiss is only touched in constructors and in
@@ -34,7 +33,7 @@ import types
 import numpy as np
 import torch
 
-REF = "/root/reference"
+REF = None                      # the reference's source tree: the command-line argument
 OUT = os.path.dirname(os.path.abspath(__file__))
 torch.set_num_threads(1)
 
@@ -683,6 +682,9 @@ def gen_adaptive_and_scorer():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) != 2 or not os.path.isdir(sys.argv[1]):
+        sys.exit("usage: python tests/golden/make_golden.py <reference source tree>")
+    REF = os.path.abspath(sys.argv[1])
     install_stubs()
     gen_datastore()
     gen_pq()

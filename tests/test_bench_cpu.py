@@ -70,3 +70,44 @@ def test_roofline_helpers_are_consistent():
         assert val == round(k["hbm_bytes_per_launch"]) and src == t["_meta"]["profile"]
     else:
         assert val is None and "other kernel sources" in src
+
+
+def test_dump_outputs_writes_the_last_step_within_its_budget(tmp_path, monkeypatch):
+    """`bench.dump_outputs` (--dump-outputs): the step's sub-batch dicts joined in token order, float32 / float64 files, per-token
+    vectors whole, the [tokens, x] matrices at one seeded sample of rows (rows.npy) that fills but never passes the byte budget;
+    the same outputs give the same files, and vectors too large for half the budget are sampled as well."""
+    import importlib
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2_000_000)
+    g = torch.Generator().manual_seed(0)
+
+    def part(n, k=64, d=96):
+        return {"gcn_feat": torch.randn(n, d, generator=g), "lm_logp": -torch.rand(n, generator=g), "logp": -torch.rand(n, generator=g),
+                "recall": torch.randint(0, k, (n,), generator=g, dtype=torch.int32),
+                "knn_sims": torch.rand(n, k, generator=g), "knn_ids": torch.randint(0, 10 ** 11, (n, k), generator=g)}
+    outs = [part(3000), part(2000)]
+    whole = {k_: torch.cat([o[k_] for o in outs]).numpy() for k_ in outs[0]}
+    info = bench.dump_outputs(str(tmp_path / "a"), outs)
+    files = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(files) == sorted(list(whole) + ["rows"]) and info["tokens"] == 5000 and info["vector_rows"] == 5000
+    assert sum(os.path.getsize(tmp_path / "a" / (f + ".npy")) for f in files) == info["bytes"] <= 2_000_000
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert files["knn_ids"].dtype == np.float64 and files["recall"].dtype == np.float64 and files["logp"].dtype == np.float32
+    for k_ in ("lm_logp", "logp", "recall"):
+        assert np.array_equal(files[k_], whole[k_])
+    rows = files["rows"].astype(np.int64)
+    assert np.array_equal(rows, files["rows"]) and len(rows) == info["matrix_rows"] and np.all(np.diff(rows) > 0)
+    assert 0 <= rows[0] and rows[-1] < 5000 and 0.9 * 2_000_000 < info["bytes"]           # the budget is used, not exceeded
+    for k_ in ("gcn_feat", "knn_sims", "knn_ids"):
+        assert np.array_equal(files[k_], whole[k_][rows].astype(files[k_].dtype))
+    bench.dump_outputs(str(tmp_path / "b"), outs)
+    for f in files:
+        assert (tmp_path / "a" / (f + ".npy")).read_bytes() == (tmp_path / "b" / (f + ".npy")).read_bytes()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 60_000)
+    info = bench.dump_outputs(str(tmp_path / "c"), outs)
+    vr = np.load(tmp_path / "c" / "vector_rows.npy").astype(np.int64)
+    assert info["bytes"] <= 60_000 and 0 < info["vector_rows"] == len(vr) < 5000 and np.all(np.diff(vr) > 0)
+    assert np.array_equal(np.load(tmp_path / "c" / "logp.npy"), whole["logp"][vr])

@@ -171,3 +171,38 @@ def test_bench_two_ranks_merge_before_the_exchange():
     from gnnlm_amd.dist import bucket_capacity
     assert res["padded"]["config"]["exchange_bytes_per_step_per_rank_host_staged"] <= bucket_capacity(n_all, 2) * 2 * (8 + 5 * 16)
     assert len({r["config"]["synthetic_ppl"] for r in res.values()}) == 1
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the last timed step's outputs as float32 / float64 files, 64 MB at most.  With one pooled batch every step scores
+    the same tokens, so the dumped logp must give the run's own score sum (synthetic_ppl): search on the device with two batches in
+    flight, several streams, the HIP-graph replay.  The same arguments with another --steps time that many steps and dump the same files."""
+    import numpy as np
+
+    def run(name, *extra):
+        d = tmp_path / name
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--warmup", "2", "--settle-s", "0.05", "--no-cpu-baseline", "--no-extras",
+               "--pool", "1", "--dump-outputs", str(d), *extra]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+        files = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64_000_000
+        n = r["config"]["blocks_per_step_per_gpu"] * r["config"]["tokens_per_block"]
+        assert files["logp"].shape == (n,) and files["lm_logp"].shape == (n,)
+        ppl = float(np.exp(-files["logp"].astype(np.float64).mean()))
+        assert abs(ppl - r["config"]["synthetic_ppl"]) <= 1e-4 + 1e-6 * ppl, (ppl, r["config"]["synthetic_ppl"])
+        return r, files
+    search = ("--n-store", "3000000", "--blocks", "4", "--gcn-k", "16", "--k", "64", "--search-check", "8", "--lanes", "2")
+    r3, a = run("steps3", *search, "--steps", "3")
+    r5, b = run("steps5", *search, "--steps", "5")
+    assert r3["steps"] == 3 and r5["steps"] == 5 and r3["config"]["knn_search"]["lanes"] == 2
+    assert {"logp", "lm_logp", "p_knn", "recall", "gcn_feat", "knn_sims", "knn_ids", "knn_vals", "rows"} <= set(a) and sorted(a) == sorted(b)
+    rows = a["rows"].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and rows[-1] < 4 * 256 and a["knn_ids"].shape == (len(rows), 64) and a["gcn_feat"].shape[0] == len(rows)
+    for k_ in a:
+        assert np.array_equal(a[k_], b[k_]), k_
+    small = ("--small", "--blocks", "2", "--n-store", "30000", "--gcn-k", "16", "--k", "32", "--tokens-per-sample", "32", "--steps", "3")
+    run("graph", *small, "--graph")
+    run("streams", *small, "--streams", "2")

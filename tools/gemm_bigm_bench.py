@@ -1,7 +1,7 @@
 """The row-subset projections of the multi-layer path at growing row counts (M x 1024 x 1024, store epilogue, plain and with a
 row map): does the rate hold beyond the 655,360 rows of a 4-block step?  One launch over all rows against chunked launches."""
 import sys, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from gnnlm_amd import _lib
 dev = torch.device("cuda:0")

@@ -1,7 +1,7 @@
 """The routed label look-ups of the ids-only kNN interpolation (csrc/knn_bucket.hip) at the bench's shape, per call, by the library's own event
 profiler; `GNNLM_LIB=<variant>.so` times an A/B build (tools/build_variant.sh kbN knn_bucket.hip -DGNNLM_KB_EXP=N / -DGNNLM_KB_TILE=T)."""
 import sys, os, csv, glob
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from gnnlm_amd import ops, _lib
 dev = torch.device("cuda:0")

@@ -5,7 +5,7 @@ Round 4 A/B with this tool: the kernel's lane-to-row mapping (lane l owns 64 CON
 (piece t * 64 + l: every load instruction of a wave covers 1 KiB of contiguous bytes): 1750 us against 2429 us -- a lane's four loads of one 64-byte
 stretch merge in the L1, a wave's interleaved loads of one row do not.  The shipped mapping stays."""
 import sys, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from gnnlm_amd import _lib
 dev = torch.device("cuda:0")
