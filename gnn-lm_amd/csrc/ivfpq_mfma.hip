@@ -136,6 +136,188 @@ __global__ __launch_bounds__(256) void quantize_lut_kernel(const float* __restri
     }
 }
 
+// ADC tables and their int8 image in ONE launch (gnnlm_ivfpq_tables): the pair gnnlm_gemm_nt (M = 64 batched [n x 256] GEMMs,
+// K = dsub) + quantize_lut_kernel wrote the f32 tables (2 GiB at 32768 queries) and read them back.  Here a workgroup owns
+// TQ = 32 queries and computes their tiles twice from the operands (qr rows and the 1-MiB codebook: L2-resident):
+//   pass 1: lut = every [32 x 256] tile of every sub-quantizer, stored (a query's 64-KiB row, full 128-B lines), and per
+//           (query, m) the min and max over the 256 codes (one wave owns all codes of its m: in-wave reductions only);
+//   meta:   delta, sum_lo, amax, inv per query -- quantize_lut_kernel's formulas and its left-to-right chain over m;
+//   pass 2: the same tiles again, quantised, transposed to [code][slot] through LDS in eight (half, 64-code) pieces, 2 KiB
+//           contiguous per query and piece.
+// Bits: the f32 tiles are those of gemm_nt_f32_kernel (gemm_f32.hip, the kernel gemm_nt picks for K <= 32: ragged K, no LDS-DMA)
+// -- the same v_mfma_f32_32x32x2_f32 with A = query rows, B = codebook rows, lane half h supplying k = 8 s + 4 h + {x, y, z, w}
+// (zero beyond dsub), the same instruction order per accumulator.  Its k-steps s >= ceil(dsub / 8) multiply zeros only; they
+// are not issued here: they add +0 to an accumulator that is never -0 (it starts at +0, and a round-to-nearest sum is -0 only
+// if both addends are), which leaves it unchanged.  Min / max do not depend on the order they are taken in (no -0, no NaN in
+// a table), so the quantisation sees the values quantize_lut_kernel sees and applies the same two f32 operations to them.
+constexpr int TQ = 32;                                  // queries per workgroup (= the MFMA's rows)
+constexpr int TAB_STAGE = TQ * 64 * 32;                 // pass 2 staging: [query][64 codes][32 slots] bytes = 64 KiB
+constexpr int TABLES_LDS = TAB_STAGE + 64 * TQ * 4 + TQ * 4;       // + lo [64][TQ] + inv [TQ] (hi [64][TQ]: in the staging area, free until
+                                                                     // pass 2) = 72.1 KiB: 2 workgroups per CU
+static_assert(2 * TABLES_LDS <= 160 * 1024, "two workgroups of the tables kernel per CU");
+
+template <int DSUB>
+__global__ __launch_bounds__(256, 2) void ivfpq_tables_kernel(const gnnlm_ivfpq_tables_t p) {
+    typedef float f32x16 __attribute__((ext_vector_type(16)));
+    constexpr int S = (DSUB + 7) / 8;                   // k-steps of 8 that hold data
+    extern __shared__ __attribute__((aligned(16))) unsigned char tlds[];
+    uint32_t* stage = reinterpret_cast<uint32_t*>(tlds);
+    float* lo_s = reinterpret_cast<float*>(tlds + TAB_STAGE);                 // [m][query]
+    float* hi_s = reinterpret_cast<float*>(tlds);                             // [m][query], read by the meta step only
+    float* inv_s = lo_s + 64 * TQ;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int half = lane >> 5, l32 = lane & 31;
+    const int64_t q0 = (int64_t)blockIdx.x * TQ;
+    const int nrow = (int)min((int64_t)TQ, p.n - q0);
+    // the lane's A row (rows beyond n read the last query: computed, never stored)
+    const float* arow = p.qr + (q0 + min(l32, nrow - 1)) * p.ld_qr;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto load_a = [&](int m, float4 (&a)[S]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const int k = 8 * s + 4 * half;
+            a[s] = k < DSUB ? *reinterpret_cast<const float4*>(arow + m * DSUB + k) : z4;
+        }
+    };
+    auto load_b = [&](int m, int c, float4 (&b)[S]) __attribute__((always_inline)) {     // codebook row (m, c)
+        const float* brow = p.pq + ((int64_t)m * 256 + c) * DSUB;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const int k = 8 * s + 4 * half;
+            b[s] = k < DSUB ? *reinterpret_cast<const float4*>(brow + k) : z4;
+        }
+    };
+    auto mfma = [&](const float4 (&a)[S], const float4 (&b)[S], f32x16& acc) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s].x, b[s].x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s].y, b[s].y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s].z, b[s].z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s].w, b[s].w, acc, 0, 0, 0);
+        }
+    };
+    // C/D layout of the 32x32 MFMA: col = lane & 31 (code), row = (r & 3) + 8 (r >> 2) + 4 half (query)
+    auto row_of = [&](int r) __attribute__((always_inline)) { return (r & 3) + 8 * (r >> 2) + 4 * half; };
+
+    // ---- pass 1: f32 tables + per-(query, m) min / max.  Wave w: m = w, w + 4, ...; all 256 codes, two tiles of 32 at a time
+    for (int m = wave; m < 64; m += 4) {
+        float4 a[S];
+        load_a(m, a);
+        float mn[16], mx[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { mn[r] = INFINITY; mx[r] = -INFINITY; }
+#pragma unroll
+        for (int t0 = 0; t0 < 8; t0 += 2) {
+            float4 b[2][S];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) load_b(m, 32 * (t0 + t) + l32, b[t]);
+            f32x16 acc[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) mfma(a, b[t], acc[t]);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                float* dst = p.lut + q0 * p.ld_lut + m * 256 + 32 * (t0 + t) + l32;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = row_of(r);
+                    if (row < nrow) dst[row * p.ld_lut] = acc[t][r];
+                    mn[r] = fminf(mn[r], acc[t][r]);
+                    mx[r] = fmaxf(mx[r], acc[t][r]);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float lo = -half32_max(-mn[r]), hi = half32_max(mx[r]);
+            if (l32 == 0) { lo_s[m * TQ + row_of(r)] = lo; hi_s[m * TQ + row_of(r)] = hi; }
+        }
+    }
+    __syncthreads();
+    // ---- meta: quantize_lut_kernel's per-query reduction, same chain
+    if (tid < TQ) {
+        float maxrange = 0.f, sum_lo = 0.f, amax = 0.f;
+        for (int m = 0; m < 64; ++m) {
+            const float mn = lo_s[m * TQ + tid], mx = hi_s[m * TQ + tid];
+            maxrange = fmaxf(maxrange, mx - mn);
+            sum_lo += mn;
+            amax = fmaxf(amax, fmaxf(fabsf(mn), fabsf(mx)));
+        }
+        const bool flat = !(maxrange > 0.f);
+        const float inv = flat ? 0.f : (255.f / maxrange) * (1.f - 3.8146973e-6f);          // 1 - 2^-18
+        const float delta = flat ? 1e-30f : (maxrange / 255.f) * (1.f + 7.6293945e-6f);     // 1 + 2^-17
+        inv_s[tid] = inv;
+        if (tid < nrow) *reinterpret_cast<float4*>(p.qmeta + (q0 + tid) * 4) = make_float4(delta, sum_lo, amax, 0.f);
+    }
+    __syncthreads();
+    float inv[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) inv[r] = inv_s[row_of(r)];
+
+    // ---- pass 2: (half h, codes 64 cq ..): wave w quantises m = 32 h + 8 w + j (j = 0..7) of the piece's two tiles and packs
+    // four consecutive m of a (query, code) into the dword of slots 8 w + 4 jj ..  Staging dword d of (query, code cl) sits at
+    // d' = (d + cl / 8 + 4 ((query >> 2) & 1)) & 7 of the code's 32-byte row: the 64 lanes of a store (and of a read below)
+    // hit 64 different banks.
+    for (int h = 0; h < 2; ++h) {
+        for (int cq = 0; cq < 4; ++cq) {
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+                uint32_t pk[2][16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) pk[0][r] = pk[1][r] = 0u;
+#pragma nounroll
+                for (int j = 0; j < 4; ++j) {                        // (rolled: unrolled, all four steps' loads are hoisted and spill)
+                    const int m = 32 * h + 8 * wave + 4 * jj + j;
+                    float4 a[S], b[2][S];
+                    load_a(m, a);
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) load_b(m, 64 * cq + 32 * t + l32, b[t]);
+                    f32x16 acc[2];
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) mfma(a, b[t], acc[t]);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float lo = lo_s[m * TQ + row_of(r)];
+#pragma unroll
+                        for (int t = 0; t < 2; ++t) {
+                            const float y = (acc[t][r] - lo) * inv[r];
+                            const uint32_t u = (uint32_t)min(255, max(0, (int)floorf(y))) ^ 0x80u;   // the SIGNED byte u - 128
+                            pk[t][r] |= u << (8 * j);
+                        }
+                    }
+                }
+                const int d = 2 * wave + jj;
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const int cl = 32 * t + l32;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = row_of(r);
+                        stage[(row * 64 + cl) * 8 + ((d + (cl >> 3) + 4 * ((row >> 2) & 1)) & 7)] = pk[t][r];
+                    }
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < TQ * 64 / 256; ++i) {
+                const int e = tid + 256 * i, row = e >> 6, cl = e & 63;
+                const uint32_t* src = stage + (row * 64 + cl) * 8;
+                const int rot = (cl >> 3) + 4 * ((row >> 2) & 1);
+                uint32_t o[8];
+#pragma unroll
+                for (int dd = 0; dd < 8; ++dd) o[dd] = src[(dd + rot) & 7];
+                if (row < nrow) {
+                    uint4* dst = reinterpret_cast<uint4*>(p.qlut + (q0 + row) * QLUT_BYTES + h * 8192 + (64 * cq + cl) * 32);
+                    dst[0] = uint4{o[0], o[1], o[2], o[3]};
+                    dst[1] = uint4{o[4], o[5], o[6], o[7]};
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // The integer image of a query's threshold for one list: a key can score above tau only if the MFMA's sum (sum_u - 128 * 64: the
 // table bytes are u - 128) reaches it.  eps: rounding of the f32 score chain (65 adds), of sum_lo and of this formula's
 // subtractions: (M + 2) 2^-22 sum |terms|.  survive iff sum_u + 64 > thr' with thr' in (thr - 1, thr + 1)
@@ -1060,6 +1242,28 @@ int ivfpq_quantize_lut(const float* lut, int64_t ld_lut, int64_t n, int M, uint8
                   "ivfpq_quantize_lut: need M = 64 and 16-byte aligned tables");
     if (n == 0) return OK;
     hipLaunchKernelGGL(quantize_lut_kernel, dim3((unsigned)n), dim3(256), 0, stream, lut, ld_lut, qlut, qmeta);
+    GNNLM_LAUNCH_CHECK();
+    return OK;
+}
+
+int ivfpq_tables(const gnnlm_ivfpq_tables_t& d, hipStream_t stream) {
+    GNNLM_REQUIRE(d.qr && d.pq && d.lut && d.qlut && d.qmeta && d.n >= 0 && d.n < (1ll << 31), "ivfpq_tables: null operand or bad n");
+    GNNLM_REQUIRE(d.M == 64 && (d.dsub == 4 || d.dsub == 8 || d.dsub == 16 || d.dsub == 32),
+                  "ivfpq_tables: need M = 64 and dsub in {4, 8, 16, 32} (other shapes: gnnlm_gemm_nt + gnnlm_ivfpq_quantize_lut)");
+    GNNLM_REQUIRE(d.ld_qr >= 64 * d.dsub && d.ld_qr % 4 == 0 && d.ld_lut >= 64 * 256 && d.ld_lut % 4 == 0 &&
+                      (uintptr_t)d.qr % 16 == 0 && (uintptr_t)d.pq % 16 == 0 && (uintptr_t)d.lut % 16 == 0 &&
+                      (uintptr_t)d.qlut % 16 == 0 && (uintptr_t)d.qmeta % 16 == 0,
+                  "ivfpq_tables: rows of qr / lut must be 16-byte aligned and hold 64 * dsub / 64 * 256 floats");
+    if (d.n == 0) return OK;
+    const dim3 grid((unsigned)cdiv(d.n, (int64_t)TQ));
+#define GNNLM_TABLES_LAUNCH(DS)                                                                                 \
+    GNNLM_LDS_OPT_IN(&ivfpq_tables_kernel<DS>, TABLES_LDS);                                                     \
+    hipLaunchKernelGGL(ivfpq_tables_kernel<DS>, grid, dim3(256), TABLES_LDS, stream, d);
+    if (d.dsub == 4) { GNNLM_TABLES_LAUNCH(4) }
+    else if (d.dsub == 8) { GNNLM_TABLES_LAUNCH(8) }
+    else if (d.dsub == 16) { GNNLM_TABLES_LAUNCH(16) }
+    else { GNNLM_TABLES_LAUNCH(32) }
+#undef GNNLM_TABLES_LAUNCH
     GNNLM_LAUNCH_CHECK();
     return OK;
 }

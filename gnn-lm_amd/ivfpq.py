@@ -236,6 +236,7 @@ class IVFPQIndex:
         self.refine_tau = os.environ.get("GNNLM_IVF_REFINE", "1") != "0"     # gnnlm_ivfpq_refine between the filter and the re-score (A/B: 0)
         self.fuse_refine = os.environ.get("GNNLM_IVF_FUSED", "1") != "0"     # ... inside the re-score's launch (A/B: 0 = two launches)
         self.fork_tables = os.environ.get("GNNLM_IVF_FORK", "1") != "0"      # ADC tables on a side stream beside the coarse scores (A/B: 0)
+        self.fused_tables = os.environ.get("GNNLM_IVF_TABLES", "1") != "0"   # f32 + int8 tables in one launch, gnnlm_ivfpq_tables (A/B: 0 = GEMM + quantisation)
         self._side_streams = {}                                              # raw stream -> its side stream
         self.stats = {}                                                      # device-side work counters of the last search (bench.py)
 
@@ -555,6 +556,12 @@ class IVFPQIndex:
                 side = self._side_streams[cur.cuda_stream] = torch.cuda.Stream(device=dev)
             side.wait_stream(cur)
         with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+            if tables is not None and self.fused_tables and self.dsub in (4, 8, 16, 32):
+                t = _lib.gnnlm_ivfpq_tables_t()
+                t.qr, t.ld_qr, t.n, t.pq, t.M, t.dsub = qr.data_ptr(), qr.stride(0), nq, self.pq.data_ptr(), self.M, self.dsub
+                t.lut, t.ld_lut, t.qlut, t.qmeta = lut.data_ptr(), lut.stride(0), tables[0].data_ptr(), tables[1].data_ptr()
+                _lib.call_desc("gnnlm_ivfpq_tables", t)
+                return lut, tables, side
             g = _lib.gnnlm_gemm_t()
             g.A, g.lda, g.W, g.ldw, g.C, g.ldc = qr.data_ptr(), qr.stride(0), self.pq.data_ptr(), self.dsub, lut.data_ptr(), self.M * 256
             g.M, g.N, g.K, g.batch1 = nq, 256, self.dsub, self.M

@@ -345,6 +345,18 @@ int gnnlm_ivfpq_pack_lut(const float* lut, int64_t ld_lut, int64_t n, int32_t M,
  * ---------------------------------------------------------------------------------------------- */
 int gnnlm_ivfpq_pack_tiles(const uint8_t* codes, int64_t N, int32_t M, uint8_t* out, void* stream);
 int gnnlm_ivfpq_quantize_lut(const float* lut, int64_t ld_lut, int64_t n, int32_t M, uint8_t* qlut, float* qmeta, void* stream);
+/* Added within ABI 11 (additive: a new entry and struct, no existing layout changed).  The ADC tables and their int8 image in
+ * one launch: lut [n, 64 * 256] f32 (row stride ld_lut) = <qr_m, pq_mc>, bit for bit what gnnlm_gemm_nt computes from
+ * A = qr (lda = ld_qr, sA1 = dsub), W = pq [64][256][dsub] (ldw = dsub, sW1 = 256 dsub), batch1 = 64, K = dsub at the default
+ * f32 precision; qlut / qmeta bit for bit what gnnlm_ivfpq_quantize_lut makes of that lut.  M = 64, dsub in {4, 8, 16, 32},
+ * every pointer 16-byte aligned; other shapes are refused (use the two calls). */
+typedef struct gnnlm_ivfpq_tables {
+    const float* qr;  int64_t ld_qr;  int64_t n;
+    const float* pq;  int32_t M;  int32_t dsub;
+    float* lut;  int64_t ld_lut;
+    uint8_t* qlut;  float* qmeta;
+} gnnlm_ivfpq_tables_t;
+int gnnlm_ivfpq_tables(const gnnlm_ivfpq_tables_t* desc, void* stream);
 /* The task table of gnnlm_ivfpq_scan8 from the probe table: (query, probe) pairs of probe_list [n, P] (row stride ld_probe; -1 = none)
  * -> groups of up to 8 queries that probe the same list, in list order: grp_list [G], grp_q [G, 8] (-1 padded), n_groups [1]
  * (device), optionally grp_out [G, 8] = (query * P + probe slot) * seg (the pair's segment of a [n, P, seg] array; NULL: not
