@@ -7,8 +7,6 @@
 // Tasks arrive grouped by list, so the workgroups running at the same time read the same code rows out of L2 / the
 // Infinity Cache; a list is read from HBM about once per search batch.  Bound: the LDS look-up rate (M random 4-B
 // reads per (query, key) pair).
-#include <cstdlib>
-
 #include "kernels.h"
 
 namespace gnnlm {
@@ -78,111 +76,13 @@ __global__ __launch_bounds__(256) void ivfpq_scan_kernel(gnnlm_ivfpq_scan_t p) {
     }
 }
 
-
-// Two tasks per workgroup with the two queries' tables interleaved in LDS (float2 per entry, 128 KiB at M = 64):
-// when both tasks probe the SAME list -- the common case, tasks arrive sorted by list -- every key's code row is read
-// once and every look-up is one ds_read_b64 that serves both queries: half the LDS instructions and half the address
-// arithmetic per (query, key) pair of the one-task kernel above (measured at the reference's index shape, 8192 queries,
-// k = 1024, nprobe 32 over 103 M keys: 121 ms of scan time with one query per workgroup).  Tasks of different lists
-// (a list boundary inside the pair) are scanned one after the other with their half of the table.
-#ifndef GNNLM_IVF_EXP
-#define GNNLM_IVF_EXP 0      // ablation builds (tools/build_variant.sh): 1 no code loads, 2 no table load, 4 no outputs
-#endif
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <int WHICH>    // 0: query 0 only, 1: query 1 only, 2: both (same list)
-__device__ __forceinline__ void scan_list(const gnnlm_ivfpq_scan_t& p, const f32x2* lut, int M, int64_t lo, int64_t len, int tid, int nt,
-                                          int q0, int slot0, int q1, int slot1) {
-    const float bias0 = WHICH != 1 ? p.probe_bias[(int64_t)q0 * p.ld_probe + slot0] : 0.f;
-    const float bias1 = WHICH != 0 ? p.probe_bias[(int64_t)q1 * p.ld_probe + slot1] : 0.f;
-    float *ov0 = nullptr, *ov1 = nullptr;
-    int64_t *oi0 = nullptr, *oi1 = nullptr;
-    float tau0 = 0.f, tau1 = 0.f;
-    if (!p.tau) {
-        if (WHICH != 1) { ov0 = p.out_val + (int64_t)q0 * p.ld_out + (int64_t)(slot0 - p.p0) * p.seg; if (p.out_id) oi0 = p.out_id + (int64_t)q0 * p.ld_out + (int64_t)(slot0 - p.p0) * p.seg; }
-        if (WHICH != 0) { ov1 = p.out_val + (int64_t)q1 * p.ld_out + (int64_t)(slot1 - p.p0) * p.seg; if (p.out_id) oi1 = p.out_id + (int64_t)q1 * p.ld_out + (int64_t)(slot1 - p.p0) * p.seg; }
-        for (int64_t j = min(len, (int64_t)p.seg) + tid; j < p.seg; j += nt) {
-            if (WHICH != 1) { if (oi0) oi0[j] = -1; else ov0[j] = -INFINITY; }
-            if (WHICH != 0) { if (oi1) oi1[j] = -1; else ov1[j] = -INFINITY; }
-        }
-    } else {
-        if (WHICH != 1) tau0 = p.tau[q0];
-        if (WHICH != 0) tau1 = p.tau[q1];
-    }
-    for (int64_t j = tid; j < len; j += nt) {
-        const uint4* crow = reinterpret_cast<const uint4*>(p.codes + (lo + j) * M);
-        f32x2 s0 = {0.f, 0.f}, s1 = {0.f, 0.f}, s2 = {0.f, 0.f}, s3 = {0.f, 0.f};
-        for (int c16 = 0; c16 < M / 16; ++c16) {
-            const uint4 v = crow[c16];
-            const f32x2* t = lut + c16 * 16 * 256;
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                s0 += t[(4 * u + 0) * 256 + (w[u] & 255u)];
-                s1 += t[(4 * u + 1) * 256 + ((w[u] >> 8) & 255u)];
-                s2 += t[(4 * u + 2) * 256 + ((w[u] >> 16) & 255u)];
-                s3 += t[(4 * u + 3) * 256 + (w[u] >> 24)];
-            }
-        }
-        const f32x2 s = (s0 + s1) + (s2 + s3);
-        if (!p.tau) {
-            if (j < p.seg) {
-                if (WHICH != 1) ov0[j] = bias0 + s.x;
-                if (WHICH != 0) ov1[j] = bias1 + s.y;
-                if (p.out_id) {
-                    const int64_t id = p.ids[lo + j];
-                    if (WHICH != 1) oi0[j] = id;
-                    if (WHICH != 0) oi1[j] = id;
-                }
-            }
-        } else {
-            const int64_t id = p.ids[lo + j];
-            if (WHICH != 1 && bias0 + s.x > tau0) {
-                const int pos = atomicAdd(&p.cand_cnt[q0], 1);
-                if (pos < p.cap) { p.cand_val[(int64_t)q0 * p.cap + pos] = bias0 + s.x; p.cand_id[(int64_t)q0 * p.cap + pos] = id; }
-            }
-            if (WHICH != 0 && bias1 + s.y > tau1) {
-                const int pos = atomicAdd(&p.cand_cnt[q1], 1);
-                if (pos < p.cap) { p.cand_val[(int64_t)q1 * p.cap + pos] = bias1 + s.y; p.cand_id[(int64_t)q1 * p.cap + pos] = id; }
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(1024) void ivfpq_scan2_kernel(gnnlm_ivfpq_scan_t p) {
-    extern __shared__ __attribute__((aligned(16))) float lut_raw[];
-    f32x2* lut = reinterpret_cast<f32x2*>(lut_raw);                       // [M][256] (query 0, query 1)
-    const int tid = threadIdx.x, nt = 1024;
-    const int64_t t0 = 2 * (int64_t)blockIdx.x, t1 = t0 + 1;
-    const bool two = t1 < p.n_tasks;
-    const int M = p.M;
-    const int q0 = p.task_q[t0], slot0 = p.task_p[t0];
-    const int q1 = two ? p.task_q[t1] : q0, slot1 = two ? p.task_p[t1] : slot0;
-    const int64_t la = p.probe_list[(int64_t)q0 * p.ld_probe + slot0];
-    const int64_t lb = two ? p.probe_list[(int64_t)q1 * p.ld_probe + slot1] : -1;
-    {
-        const float* a = p.lut + (int64_t)q0 * p.ld_lut;
-        const float* b = p.lut + (int64_t)q1 * p.ld_lut;
-        for (int e = tid; e < M * 256; e += nt) lut[e] = f32x2{a[e], b[e]};
-    }
-    __syncthreads();
-    int64_t loa = 0, lena = 0, lob = 0, lenb = 0;
-    if (la >= 0) { loa = p.list_off[la]; lena = p.list_off[la + 1] - loa; }
-    if (lb >= 0) { lob = p.list_off[lb]; lenb = p.list_off[lb + 1] - lob; }
-    if (two && la == lb) {
-        scan_list<2>(p, lut, M, loa, lena, tid, nt, q0, slot0, q1, slot1);
-    } else {
-        scan_list<0>(p, lut, M, loa, lena, tid, nt, q0, slot0, q1, slot1);
-        if (two) scan_list<1>(p, lut, M, lob, lenb, tid, nt, q0, slot0, q1, slot1);
-    }
-}
-
-
 // ------------------------------------------------------------------------------------------------------------------
 // Conflict-free scan over the PACKED index image (gnnlm_ivfpq_pack_codes / gnnlm_ivfpq_pack_lut), M = 32 or 64.
 //
-// The kernels above are bound by LDS bank conflicts: the 32 lanes of a half-wave read 32 random entries of ONE
+// Two tasks per workgroup with the two queries' tables interleaved in LDS: when both tasks probe the SAME list -- the
+// common case, tasks arrive sorted by list -- every key's code row is read once and every look-up serves both queries.
+// Tasks of different lists (a list boundary inside the pair) are scanned one after the other with their half of the table.
+// The kernel above is bound by LDS bank conflicts: the 32 lanes of a half-wave read 32 random entries of ONE
 // sub-quantizer's table (~3.5 lanes on the busiest bank pair).  Here a lane's look-up number s goes to sub-quantizer
 // (lane + s) mod 32 of its own key, and the tables are stored [half][code][32 sub-quantizers] (8 B per entry: the two
 // queries of the workgroup), so the 32 lanes of a group always hit 32 different bank pairs whatever the codes are.  The
@@ -191,9 +91,14 @@ __global__ __launch_bounds__(1024) void ivfpq_scan2_kernel(gnnlm_ivfpq_scan_t p)
 // Per (two queries, key, sub-quantizer): v_perm_b32 + ds_read_b64 + v_pk_add_f32.  Key rows are stored piece-major in
 // blocks of 64 rows, so a wave's 16-B loads are 1 KiB contiguous.  Workgroups of one XCD take neighbouring task pairs
 // (one list's tasks share an L2).
+#ifndef GNNLM_IVF_EXP
+#define GNNLM_IVF_EXP 0      // ablation builds (tools/build_variant.sh): 1 no code loads, 2 no table load, 4 no outputs
+#endif
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int STAGE_CAP = 1024;
 constexpr int STAGE_BYTES = 16 + 2 * STAGE_CAP * 8;
-template <int M, int WHICH>    // WHICH as above
+template <int M, int WHICH>    // 0: query 0 only, 1: query 1 only, 2: both (same list)
 __device__ __forceinline__ void scan_rot(const gnnlm_ivfpq_scan_t& p, const char* lut, int* stage, int64_t lo, int64_t len, int tid,
                                          int q0, int slot0, int q1, int slot1) {
     constexpr int NT = 1024, NW = NT / 64;
@@ -568,11 +473,6 @@ int ivfpq_scan(const gnnlm_ivfpq_scan_t& d, hipStream_t stream) {
     GNNLM_REQUIRE(!d.list_term || (!d.packed && d.ld_list_term >= (int64_t)d.M * 256 && d.ld_list_term % 4 == 0 && (uintptr_t)d.list_term % 16 == 0),
                   "ivfpq_scan: the L2 metric runs on row-major codes with 16-byte aligned list tables");
     ProfScope prof(K_IVF, stream, 0.0, 0.0);
-    if (d.list_term) {
-        hipLaunchKernelGGL(ivfpq_scan_kernel, dim3((unsigned)d.n_tasks), dim3(256), lds, stream, d);
-        GNNLM_LAUNCH_CHECK();
-        return OK;
-    }
     if (d.packed) {
         GNNLM_REQUIRE(d.M == 32 || d.M == 64, "ivfpq_scan: the packed image exists for M = 32 and 64");
         const int64_t n_pairs = cdiv(d.n_tasks, (int64_t)2);
@@ -581,12 +481,6 @@ int ivfpq_scan(const gnnlm_ivfpq_scan_t& d, hipStream_t stream) {
         GNNLM_LDS_OPT_IN(&ivfpq_scan_rot_kernel<32>, 64 * 1024 + STAGE_BYTES);
         if (d.M == 64) hipLaunchKernelGGL(ivfpq_scan_rot_kernel<64>, dim3((unsigned)(8 * per_xcd)), dim3(1024), 2 * lds + STAGE_BYTES, stream, d, n_pairs, per_xcd);
         else hipLaunchKernelGGL(ivfpq_scan_rot_kernel<32>, dim3((unsigned)(8 * per_xcd)), dim3(1024), 2 * lds + STAGE_BYTES, stream, d, n_pairs, per_xcd);
-        GNNLM_LAUNCH_CHECK();
-        return OK;
-    }
-    if (d.M <= 64 && !getenv("GNNLM_IVF_SINGLE")) {
-        GNNLM_LDS_OPT_IN(&ivfpq_scan2_kernel, 128 * 1024);
-        hipLaunchKernelGGL(ivfpq_scan2_kernel, dim3((unsigned)cdiv(d.n_tasks, 2)), dim3(1024), 2 * lds, stream, d);
         GNNLM_LAUNCH_CHECK();
         return OK;
     }

@@ -868,10 +868,18 @@ __global__ __launch_bounds__(1024) void ivfpq_tau_kernel(gnnlm_ivfpq_tau_t p) {
 #ifndef GNNLM_REFINE_NT
 #define GNNLM_REFINE_NT 1024     // threads per query (A/B: 512 was slower, 0.46 against 0.40 ms)
 #endif
-// (a workgroup's refinement as a function: its own kernel below, and the prologue of the fused refine + re-score launch.  `hist`:
-// 2048 ints of LDS the caller lends.  Returns the records left and the threshold to every thread.)
+// The refinement's operands (ivfpq_refine_rescore_kernel fills them from its gnnlm_ivfpq_rescore_t): survivor records [n, cap, 2]
+// compacted in place, surv_cnt / out_cnt [n, 16] (column 0: the filter's count / the records left), tau [n] raised in place.
+struct RefineParams {
+    uint32_t* surv;  const int32_t* surv_cnt;  int32_t* out_cnt;  int32_t cap;
+    float* tau;  const float* qmeta;
+    const float* coarse;  int64_t ld_coarse;
+    int64_t n;  int32_t k;
+};
+// (a workgroup's refinement as a function: the prologue of the fused refine + re-score launch.  `hist`: 2048 ints of LDS the caller
+// lends.  Returns the records left and the threshold to every thread.)
 template <int EPT>
-__device__ __forceinline__ void refine_wg(const gnnlm_ivfpq_refine_t& p, const int64_t q, int* hist, int& n_left, float& tau_left) {
+__device__ __forceinline__ void refine_wg(const RefineParams& p, const int64_t q, int* hist, int& n_left, float& tau_left) {
     constexpr int NT = GNNLM_REFINE_NT, NB = 2048, NWV = NT / 64;
     __shared__ int wtot[NWV];
     __shared__ int dig_s, base_s;
@@ -1031,14 +1039,6 @@ __device__ __forceinline__ void refine_wg(const gnnlm_ivfpq_refine_t& p, const i
     tau_left = tau1;
 }
 
-template <int EPT>
-__global__ __launch_bounds__(GNNLM_REFINE_NT) void ivfpq_refine_kernel(gnnlm_ivfpq_refine_t p) {
-    __shared__ int hist[2048];
-    int n_left;
-    float tau_left;
-    refine_wg<EPT>(p, (int64_t)blockIdx.x, hist, n_left, tau_left);
-}
-
 // Exact float32 scores of the survivors, in the summation order of the f32 scan (ivfpq.hip scan_rot: look-up s of half h
 // goes to sub-quantizer 32 h + (row + s) % 32, even look-ups into one chain, odd ones into the other, halves in order,
 // score = bias + (chain0 + chain1)).  One workgroup per query, its table in LDS.
@@ -1168,12 +1168,12 @@ __global__ __launch_bounds__(GNNLM_RESCORE_NT) void ivfpq_rescore_kernel(gnnlm_i
     rescore_wg<M, false>(p, q, min(p.surv_cnt[q * SURV_CNT_STRIDE], p.cap), p.tau[q], rtab);
 }
 
-// Refinement + re-score of a query in ONE launch (round 6; gnnlm_ivfpq_rescore with `qmeta`).  The two kernels were one workgroup
+// Refinement + re-score of a query in ONE launch (round 6; gnnlm_ivfpq_rescore with `qmeta`).  As two kernels they were one workgroup
 // per query each, both waiting on memory most of their time (the re-score 40 % of its 35 us for its 64-KiB table to arrive: copied
 // through registers behind a barrier -- tools/rescore_phases.py).  Here the table is requested FIRST, by LDS-DMA (no registers, nothing
 // waits for it), the refinement runs while it arrives (its histogram in the code rows' staging area), and the re-score starts on the
 // records the refinement has just compacted (in place, in the query's survivor list: this workgroup's own writes, ordered by the
-// barrier).  Same arithmetic, same order: the candidates are those of the two-launch path.
+// barrier).  Same arithmetic, same order: the candidates are those the two launches gave.
 static_assert(GNNLM_REFINE_NT == GNNLM_RESCORE_NT, "the fused refine + re-score launch runs both on one workgroup shape");
 template <int EPT>
 __global__ __launch_bounds__(GNNLM_RESCORE_NT) void ivfpq_refine_rescore_kernel(gnnlm_ivfpq_rescore_t p) {
@@ -1195,7 +1195,7 @@ __global__ __launch_bounds__(GNNLM_RESCORE_NT) void ivfpq_refine_rescore_kernel(
                      "s_mov_b32 m0, %0"
                      : "=&s"(keep_) : "v"(src), "s"(dst) : "memory");
     }
-    gnnlm_ivfpq_refine_t r;
+    RefineParams r;
     r.surv = const_cast<uint32_t*>(p.surv);  r.surv_cnt = p.surv_cnt;  r.out_cnt = p.out_cnt;  r.cap = p.cap;
     r.tau = const_cast<float*>(p.tau);  r.qmeta = p.qmeta;  r.coarse = p.coarse;  r.ld_coarse = p.ld_coarse;  r.n = p.n;  r.k = p.k;
     int n_left;
@@ -1318,42 +1318,26 @@ int ivfpq_split_payload(int64_t* idx, int64_t n, int label_bits, int32_t val_las
     return OK;
 }
 
-int ivfpq_refine(const gnnlm_ivfpq_refine_t& d, hipStream_t stream) {
-    GNNLM_REQUIRE(d.n >= 0 && d.n < (1ll << 31) && d.k > 0 && d.cap > 0, "ivfpq_refine: bad shape");
-    if (d.n == 0) return OK;
-    GNNLM_REQUIRE(d.surv && d.surv_cnt && d.out_cnt && d.tau && d.qmeta && d.coarse, "ivfpq_refine: null operand");
-    ProfScope prof(K_TAU, stream, 0.0, 16.0 * (double)d.n * d.k);
-    // 16 records per thread in registers (the default capacity of 16384 records; what is beyond is re-read)
-    hipLaunchKernelGGL(ivfpq_refine_kernel<16>, dim3((unsigned)d.n), dim3(GNNLM_REFINE_NT), 0, stream, d);
-    GNNLM_LAUNCH_CHECK();
-    return OK;
-}
-
 int ivfpq_rescore(const gnnlm_ivfpq_rescore_t& d, hipStream_t stream) {
     GNNLM_REQUIRE(d.n >= 0 && d.n < (1ll << 31), "ivfpq_rescore: bad query count");
     if (d.n == 0) return OK;
     GNNLM_REQUIRE(d.codes && d.payload && d.lut && d.coarse && d.tau && d.surv && d.surv_cnt && d.cand_val && d.cand_id && d.cand_cnt &&
                       d.cap > 0 && d.cand_cap > 0,
                   "ivfpq_rescore: null operand");
-    GNNLM_REQUIRE((d.M == 64 || d.M == 32) && d.ld_lut >= (int64_t)d.M * 256 && d.ld_lut % 4 == 0 && (uintptr_t)d.lut % 16 == 0 &&
+    GNNLM_REQUIRE(d.M == 64 && d.ld_lut >= (int64_t)d.M * 256 && d.ld_lut % 4 == 0 && (uintptr_t)d.lut % 16 == 0 &&
                       (uintptr_t)d.codes % 16 == 0,
-                  "ivfpq_rescore: need M = 32 or 64, 16-byte aligned tables");
+                  "ivfpq_rescore: need M = 64, 16-byte aligned tables");
     ProfScope prof(K_RESCORE, stream, 0.0, 0.0);
     const size_t lds = (size_t)d.M * 256 * 4 + GNNLM_RESCORE_NT * (size_t)d.M;
     if (d.qmeta) {                                                          // refinement + re-score in one launch (ABI 10)
-        GNNLM_REQUIRE(d.M == 64 && d.k > 0, "ivfpq_rescore: the fused refinement needs M = 64 and k > 0");
+        GNNLM_REQUIRE(d.k > 0, "ivfpq_rescore: the refinement needs k > 0");
         GNNLM_LDS_OPT_IN(&ivfpq_refine_rescore_kernel<8>, lds);
         hipLaunchKernelGGL(ivfpq_refine_rescore_kernel<8>, dim3((unsigned)d.n), dim3(GNNLM_RESCORE_NT), lds, stream, d);
         GNNLM_LAUNCH_CHECK();
         return OK;
     }
-    if (d.M == 64) {
-        GNNLM_LDS_OPT_IN(&ivfpq_rescore_kernel<64>, lds);
-        hipLaunchKernelGGL(ivfpq_rescore_kernel<64>, dim3((unsigned)d.n), dim3(GNNLM_RESCORE_NT), lds, stream, d);
-    } else {
-        GNNLM_LDS_OPT_IN(&ivfpq_rescore_kernel<32>, lds);
-        hipLaunchKernelGGL(ivfpq_rescore_kernel<32>, dim3((unsigned)d.n), dim3(GNNLM_RESCORE_NT), lds, stream, d);
-    }
+    GNNLM_LDS_OPT_IN(&ivfpq_rescore_kernel<64>, lds);
+    hipLaunchKernelGGL(ivfpq_rescore_kernel<64>, dim3((unsigned)d.n), dim3(GNNLM_RESCORE_NT), lds, stream, d);
     GNNLM_LAUNCH_CHECK();
     return OK;
 }

@@ -17,7 +17,7 @@ k-th-best threshold, the remaining lists only emit scores above that threshold.
 At M = 64 (the reference's PQ64) the thresholded round is a FILTER on the int8 matrix cores followed by an exact re-score
 (``csrc/ivfpq_mfma.hip``: 8-bit tables with a guaranteed one-sided bound, eight queries of a list per workgroup, the
 sums taken by ``v_smfmac_i32_16x16x128_i8`` (round 3: ``v_mfma_i32_16x16x64_i8``); survivors re-scored in float32 in the summation order of the float32 scan), so
-candidates and scores are those of the one-pass float32 scan -- ``GNNLM_IVF_SCAN=f32`` selects that scan for A/B runs.
+candidates and scores are those of the one-pass float32 scan -- ``IVFPQIndex(..., scan="f32")`` selects that scan.
 With ``attach_vals`` the index carries each key's label next to its id (one 8-byte payload per key), and the search
 returns ``vals[ids]`` with the neighbours: the label gather of knn/knn_model.py:198 disappears.
 
@@ -61,18 +61,13 @@ class _LazyStats(dict):
     def items(self):
         return [(k, self[k]) for k in list(self.keys())]
 
-    def clone(self):
-        out = _LazyStats()
-        for k, v in self.items():
-            dict.__setitem__(out, k, v.clone() if torch.is_tensor(v) else v)
-        return out
-
 
 class _PendingSearch:
     """Handle of ``IVFPQIndex.search_begin``."""
 
-    def __init__(self, index, q, k, query_block, return_vals, val, idx, over, worst, ev, cap):
+    def __init__(self, index, q, k, query_block, return_vals, stats, val, idx, over, worst, ev, cap):
         self.index, self.q, self.k, self.query_block, self.return_vals = index, q, k, query_block, return_vals
+        self.stats = stats                               # work counters of THIS search: index.stats once it has finished
         self.val, self.idx, self.over, self.worst, self.ev = val, idx, over, worst, ev
         self.cap = cap                                   # survivor capacity the buffers of THIS search were allocated with
         self._out = None
@@ -184,8 +179,7 @@ class IVFPQIndex:
         self.R, self.coarse, self.pq = R, coarse, pq                         # [d, d], [nlist, d], [M, 256, dsub]  f32
         self.list_off, self.list_ids, self.list_codes = list_off, list_ids, list_codes   # i64 [nlist+1], i64 [N], u8 [N, M]
         self.nprobe, self.cosine, self.dense_probes, self.cand_cap = nprobe, cosine, dense_probes, cand_cap
-        # every S-th tile of the threshold lists is histogrammed (GNNLM_IVF_SAMPLE; 1: all of them -- see _search_block_mfma)
-        self.threshold_sample = max(1, int(os.environ.get("GNNLM_IVF_SAMPLE", "4")))
+        self.threshold_sample = 4                # every S-th tile of the threshold lists is histogrammed (1: all of them -- see _search_block_mfma)
         self.sample_min_keys_per_k = 64          # ... when the threshold lists hold at least this many keys per neighbour asked for
         self.sample_sigmas = 4.5                 # margin of the sample's rank (tests lower it to force the verification to fail)
         self.sample_fail_frac = 0.01             # more failing queries than this in a batch: the index stops sampling
@@ -202,8 +196,8 @@ class IVFPQIndex:
         # M = 32 / 64: the scan runs on its own image of the code rows (blocks of 64 rows, bytes in rotated order) and on
         # tables in [half][code][sub-quantizer] order -- look-ups without LDS bank conflicts (csrc/ivfpq.hip)
         # M = 64: the int8-MFMA search's image of the code rows (tiles of 16 rows, rotated byte order; csrc/ivfpq_mfma.hip)
+        # scan="f32": the float32 scan at M = 64 too (tests compare the int8-MFMA search with it)
         self.packed_codes = self.tiles = None
-        scan = scan or os.environ.get("GNNLM_IVF_SCAN", "mfma")              # "f32": the float32 scan everywhere (A/B, tests)
         self.list_term = None
         if metric == "l2":
             # squared distances with residual codes: |q' - c_l - r|^2 = |q' - c_l|^2 + sum_m (T[l][m][code] - 2 <q'_m, p_mc>) with the
@@ -233,12 +227,9 @@ class IVFPQIndex:
         # where list lengths vary: 32768 keeps the re-searches of overflowing queries rare), the float32 scan's candidates
         if self.cand_cap is None:
             self.cand_cap = 32768 if self.tiles is not None else 16384
-        self.refine_tau = os.environ.get("GNNLM_IVF_REFINE", "1") != "0"     # gnnlm_ivfpq_refine between the filter and the re-score (A/B: 0)
-        self.fuse_refine = os.environ.get("GNNLM_IVF_FUSED", "1") != "0"     # ... inside the re-score's launch (A/B: 0 = two launches)
-        self.fork_tables = os.environ.get("GNNLM_IVF_FORK", "1") != "0"      # ADC tables on a side stream beside the coarse scores (A/B: 0)
-        self.fused_tables = os.environ.get("GNNLM_IVF_TABLES", "1") != "0"   # f32 + int8 tables in one launch, gnnlm_ivfpq_tables (A/B: 0 = GEMM + quantisation)
+        self.refine_tau = True                   # the threshold refinement inside the re-score's launch (False: the re-score alone, tests)
         self._side_streams = {}                                              # raw stream -> its side stream
-        self.stats = {}                                                      # device-side work counters of the last search (bench.py)
+        self.stats = {}                                                      # device-side work counters of the last search that finished (bench.py)
 
     def attach_vals(self, vals):
         """Carry the keys' labels with the index: payload[r] = id << 24 | vals[id] for the key at list position r (the reference
@@ -363,8 +354,6 @@ class IVFPQIndex:
     def _groups(self, pl, seg=None):
         """The scan's task table on the device (gnnlm_ivfpq_build_groups: histogram, prefix, scatter -- four small launches instead
         of the ~25 of ``build_groups``, the torch reference of the same table); same tuple."""
-        if not pl.is_cuda or os.environ.get("GNNLM_IVF_TORCH_GROUPS"):
-            return build_groups(pl, self.nlist, seg)
         nq, P = pl.shape
         dev = pl.device
         G = nq * P // 8 + self.nlist + 1
@@ -391,9 +380,9 @@ class IVFPQIndex:
         calls (the language model's softmax, which does not depend on the neighbours) keeps the device busy while the host looks at
         the count and enqueues what follows: no pipeline bubble behind the search's one host round trip."""
         q = q.to(self.device, torch.float32).contiguous()
-        self.stats = _LazyStats(pairs=0, survivors=0, candidates=0, queries=q.shape[0], M=self.M, requeried=0)
+        stats = self._new_stats(q.shape[0])
         cap = self.cand_cap                                                  # the capacity THIS search's buffers were allocated with
-        val, idx, over = self._search_once(q, k, query_block, self.dense_probes, cap)
+        val, idx, over = self._search_once(q, k, query_block, self.dense_probes, cap, stats)
         worst = ev = None
         if over is not None:
             if getattr(self, "_worst_host", None) is None:                    # pinned landing slots, one per search in flight (a ring of 8)
@@ -403,7 +392,10 @@ class IVFPQIndex:
             worst.copy_(over.max().reshape(1), non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-        return _PendingSearch(self, q, k, query_block, return_vals, val, idx, over, worst, ev, cap)
+        return _PendingSearch(self, q, k, query_block, return_vals, stats, val, idx, over, worst, ev, cap)
+
+    def _new_stats(self, n):
+        return _LazyStats(pairs=0, survivors=0, candidates=0, queries=n, M=self.M, requeried=0)
 
     def _finish(self, h):
         q, k, query_block = h.q, h.k, h.query_block
@@ -422,19 +414,19 @@ class IVFPQIndex:
             n_cols = int((over[bad] == self.COLUMNS).sum().item())            # too many CANDIDATES for the selection's columns: searched again one by one
             if n_under > self.sample_fail_frac * q.shape[0] and self.threshold_sample > 1:   # the sample does not stand for its lists on this data: stop sampling
                 self.threshold_sample = 1
-                self.stats = _LazyStats(pairs=0, survivors=0, candidates=0, queries=q.shape[0], M=self.M, requeried=0)
-                val, idx, over = self._search_once(q, k, query_block, self.dense_probes, cap)
+                h.stats = self._new_stats(q.shape[0])
+                val, idx, over = self._search_once(q, k, query_block, self.dense_probes, cap, h.stats)
                 continue
             if (bad.numel() - n_under - n_cols) * 8 > q.shape[0] and cap < (1 << 18):
                 cap *= 2
                 self.cand_cap = max(self.cand_cap, cap)
-                self.stats = _LazyStats(pairs=0, survivors=0, candidates=0, queries=q.shape[0], M=self.M, requeried=0)
-                val, idx, over = self._search_once(q, k, query_block, self.dense_probes, cap)
+                h.stats = self._new_stats(q.shape[0])
+                val, idx, over = self._search_once(q, k, query_block, self.dense_probes, cap, h.stats)
                 continue
             sub, cap2 = q[bad].contiguous(), cap
-            main = self.stats.clone()
             while True:                                                       # every probed list in the threshold / dense round
-                v2, i2, o2 = self._search_once(sub, k, query_block, self.nprobe, cap2)
+                # (the counters describe the main pass: the re-search's go to a throw-away set)
+                v2, i2, o2 = self._search_once(sub, k, query_block, self.nprobe, cap2, _LazyStats())
                 if o2 is None or int(o2.max().item()) <= cap2:
                     break
                 if cap2 >= (1 << 22):                                         # survivors beyond the capacity would be dropped silently
@@ -442,10 +434,9 @@ class IVFPQIndex:
                                           f"capacity ({cap2}); lower k / nprobe or search this index with scan='f32'")
                 cap2 *= 2
             val[bad], idx[bad] = v2, i2
-            dict.__setitem__(main, "requeried", int(bad.numel()))             # (the counters describe the main pass)
-            self.stats = main
+            dict.__setitem__(h.stats, "requeried", int(bad.numel()))
             break
-        self._overflow = None
+        self.stats = h.stats
         if self.metric == "l2":
             val = -val                                                        # scores are -distance: squared distances, ascending, +inf padded
         if not self.has_vals:
@@ -455,7 +446,7 @@ class IVFPQIndex:
         _lib.call("gnnlm_ivfpq_split_payload", _lib.ptr(idx), idx.numel(), self.LABEL_BITS, self.val_last, _lib.ptr(vals), _lib.stream())
         return (val, idx, vals) if h.return_vals else (val, idx)
 
-    def _search_once(self, q, k, query_block, dense_probes, cap):
+    def _search_once(self, q, k, query_block, dense_probes, cap, stats):
         n, dev = q.shape[0], self.device
         nprobe = min(self.nprobe, self.nlist)
         dense = max(1, min(dense_probes, nprobe))
@@ -469,17 +460,17 @@ class IVFPQIndex:
         qb = query_block if self.tiles is not None else max(1, min(query_block, self.score_bytes // max(1, 4 * dense * max(self.max_list, 1))))
         over = None
         for q0 in range(0, n, qb):
-            o = self._search_block(q[q0:q0 + qb], k, val[q0:q0 + qb], idx[q0:q0 + qb], nprobe, dense, cap)
+            o = self._search_block(q[q0:q0 + qb], k, val[q0:q0 + qb], idx[q0:q0 + qb], nprobe, dense, cap, stats)
             if o is not None:
                 over = o if over is None else torch.cat([over, o])
         return val, idx, over
 
-    def _search_block(self, qs, k, bv, bi, nprobe, dense, cap):
+    def _search_block(self, qs, k, bv, bi, nprobe, dense, cap, stats):
         dev = self.device
         nq = qs.shape[0]
         qr = ops.gemm_nt(qs, self.R)                                            # q' = R q
         # the ADC tables (a store-bound batched GEMM, 2 KB per query and sub-quantizer) and their 8-bit images depend on q' alone: they
-        # are built on a side stream beside the coarse scores / probe selection / task table of this stream (GNNLM_IVF_FORK=0: in line)
+        # are built on a side stream beside the coarse scores / probe selection / task table of this stream
         lut, tables, side = self._tables_begin(qr)
         cs = ops.gemm_nt(qr, self.coarse)                                       # <q', c_l>
         pv = torch.empty(nq, nprobe, device=dev, dtype=torch.float32)
@@ -489,7 +480,7 @@ class IVFPQIndex:
             pv = (2.0 * pv - (qr ** 2).sum(1, keepdim=True)).contiguous()      # the list's bias: -|q' - c_l|^2
         else:
             ops.topk_merge(cs, pv, pi, largest=True, init=True)                 # the nprobe best lists, best first
-        self.stats.add("pairs", lambda pi=pi: (self.list_off[1:] - self.list_off[:-1])[pi.clamp(min=0)].masked_fill(pi < 0, 0).sum().double())
+        stats.add("pairs", lambda pi=pi: (self.list_off[1:] - self.list_off[:-1])[pi.clamp(min=0)].masked_fill(pi < 0, 0).sum().double())
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)                       # (lut / tables were allocated on THIS stream: no record_stream needed)
         # (the int8 path: `cap` bounds a query's SURVIVORS of the filter; what scores above the refined threshold afterwards is a fraction of them
@@ -499,7 +490,7 @@ class IVFPQIndex:
         ci = torch.empty(nq, ccap, device=dev, dtype=torch.int64)
         cc = torch.zeros(nq, device=dev, dtype=torch.int32)
         if self.tiles is not None:
-            return self._search_block_mfma(k, bv, bi, nprobe, dense, cs, pv, pi, lut, cv, ci, cc, cap, tables)
+            return self._search_block_mfma(k, bv, bi, nprobe, dense, cs, pv, pi, lut, tables, cv, ci, cc, cap, stats)
         lut_s = lut
         if self.packed_codes is not None:
             lut_s = torch.empty_like(lut)
@@ -517,7 +508,7 @@ class IVFPQIndex:
         # round 2: the other lists only emit scores above the query's k-th best so far
         tau = torch.where(bi[:, k - 1] >= 0, bv[:, k - 1], torch.full_like(bv[:, k - 1], float("-inf"))).contiguous()
         self._scan(lut_s, pv, pi, dense, nprobe, tau=tau, cand=(cv, ci, cc), cap=cap)
-        self.stats.add("candidates", lambda cc=cc: cc.sum().double())
+        stats.add("candidates", lambda cc=cc: cc.sum().double())
         if getattr(self, "keep_candidates", False):                          # tests / debugging: the round-2 candidates of the last block
             self.last_candidates = (cv, ci, cc, tau)
         ops.topk_merge(cv, bv, bi, ids=ci, largest=True, init=False, row_ncols=cc.clamp(max=cap))
@@ -549,14 +540,14 @@ class IVFPQIndex:
         if self.tiles is not None:
             tables = (torch.empty(nq, 2, 256, 32, dtype=torch.uint8, device=dev), torch.empty(nq, 4, dtype=torch.float32, device=dev))
         side = None
-        if self.tiles is not None and self.fork_tables and not torch.cuda.is_current_stream_capturing():
+        if self.tiles is not None and not torch.cuda.is_current_stream_capturing():
             cur = torch.cuda.current_stream()
             side = self._side_streams.get(cur.cuda_stream)
             if side is None:
                 side = self._side_streams[cur.cuda_stream] = torch.cuda.Stream(device=dev)
             side.wait_stream(cur)
         with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-            if tables is not None and self.fused_tables and self.dsub in (4, 8, 16, 32):
+            if tables is not None and self.dsub in (4, 8, 16, 32):
                 t = _lib.gnnlm_ivfpq_tables_t()
                 t.qr, t.ld_qr, t.n, t.pq, t.M, t.dsub = qr.data_ptr(), qr.stride(0), nq, self.pq.data_ptr(), self.M, self.dsub
                 t.lut, t.ld_lut, t.qlut, t.qmeta = lut.data_ptr(), lut.stride(0), tables[0].data_ptr(), tables[1].data_ptr()
@@ -571,14 +562,14 @@ class IVFPQIndex:
                 _lib.call("gnnlm_ivfpq_quantize_lut", _lib.ptr(lut), lut.stride(0), nq, self.M, _lib.ptr(tables[0]), _lib.ptr(tables[1]), _lib.stream())
         return lut, tables, side
 
-    def _search_block_mfma(self, k, bv, bi, nprobe, dense, cs, pv, pi, lut, cv, ci, cc, cap, tables=None):
+    def _search_block_mfma(self, k, bv, bi, nprobe, dense, cs, pv, pi, lut, tables, cv, ci, cc, cap, stats):
         """M = 64: everything on the int8 matrix cores (csrc/ivfpq_mfma.hip).  (1) threshold pass: histograms of the integer sums of the
         first `dense` lists -> a lower bound tau of the query's k-th best score (no per-key output, no selection); (2) filter: every probed
         list, keys whose integer sum can reach tau; (3) exact float32 scores of the survivors, score > tau -> candidates;
         (4) one k-selection over the candidates."""
         dev = self.device
         nq, ccap = pv.shape[0], cv.shape[1]
-        qlut, qmeta = tables if tables is not None else ops.ivfpq_quantize_lut(lut, self.M)
+        qlut, qmeta = tables
         hist = torch.empty(nq, dense, 1024, device=dev, dtype=torch.int32)      # per (query, list): sum_u >> 4 counted on the device
         # The threshold pass histograms a SAMPLE of its lists' keys (every S-th tile of 16) when they hold plenty of them: tau is then the
         # bound of rank k / S + 4.5 sigma of the sample (sigma = sqrt(k (S - 1)) / S: the k best land in the sample binomially), i.e. with
@@ -596,32 +587,23 @@ class IVFPQIndex:
         surv = torch.empty(nq, cap, 2, device=dev, dtype=torch.int32)
         sc16 = torch.zeros(nq, 16, device=dev, dtype=torch.int32)              # one 64-byte line per counter (column 0)
         g2 = self._groups(pi)
-        self.stats.add("groups", lambda g=g2[2]: g[0].double())
+        stats.add("groups", lambda g=g2[2]: g[0].double())
         self._scan8(qlut, qmeta, cs, g2, tau=tau, surv=(surv, sc16))
         sc = sc16[:, 0]
-        # a tighter threshold from the survivors' own integer sums (all lists, un-binned), and only the survivors that can beat it
-        rc16 = sc16
-        fused = self.refine_tau and self.fuse_refine                          # refinement inside the re-score's launch (ABI 10)
-        if fused:
-            rc16 = torch.empty_like(sc16)
-            self.stats.add("rescored", lambda rc=rc16: rc[:, 0].sum().double())
-        elif self.refine_tau:
-            rc16 = torch.empty_like(sc16)
-            f = _lib.gnnlm_ivfpq_refine_t()
-            f.surv, f.surv_cnt, f.out_cnt, f.cap = surv.data_ptr(), sc16.data_ptr(), rc16.data_ptr(), cap
-            f.tau, f.qmeta, f.coarse, f.ld_coarse, f.n, f.k = tau.data_ptr(), qmeta.data_ptr(), cs.data_ptr(), cs.stride(0), nq, k
-            _lib.call_desc("gnnlm_ivfpq_refine", f)
-            self.stats.add("rescored", lambda rc=rc16: rc[:, 0].sum().double())
         r = _lib.gnnlm_ivfpq_rescore_t()
         r.codes, r.payload, r.M = self.list_codes.data_ptr(), self.payload.data_ptr(), self.M
         r.lut, r.ld_lut, r.coarse, r.ld_coarse, r.tau = lut.data_ptr(), lut.stride(0), cs.data_ptr(), cs.stride(0), tau.data_ptr()
-        r.surv, r.surv_cnt, r.cap, r.n = surv.data_ptr(), (sc16 if fused else rc16).data_ptr(), cap, nq
+        r.surv, r.surv_cnt, r.cap, r.n = surv.data_ptr(), sc16.data_ptr(), cap, nq
         r.cand_val, r.cand_id, r.cand_cnt, r.cand_cap = cv.data_ptr(), ci.data_ptr(), cc.data_ptr(), ccap
-        if fused:
+        if self.refine_tau:
+            # inside the re-score's launch: a tighter threshold from the survivors' own integer sums (all lists, un-binned), and only
+            # the survivors that can beat it are re-scored
+            rc16 = torch.empty_like(sc16)
             r.qmeta, r.k, r.out_cnt = qmeta.data_ptr(), k, rc16.data_ptr()
+            stats.add("rescored", lambda rc=rc16: rc[:, 0].sum().double())
         _lib.call_desc("gnnlm_ivfpq_rescore", r)
-        self.stats.add("survivors", lambda sc=sc: sc.sum().double())
-        self.stats.add("candidates", lambda cc=cc: cc.sum().double())
+        stats.add("survivors", lambda sc=sc: sc.sum().double())
+        stats.add("candidates", lambda cc=cc: cc.sum().double())
         if getattr(self, "keep_candidates", False):
             self.last_candidates = (cv, ci, cc, tau)
         ops.topk_merge(cv, bv, bi, ids=ci, largest=True, init=True, row_ncols=cc.clamp(max=ccap))
@@ -631,13 +613,9 @@ class IVFPQIndex:
         if S > 1:                                                              # the sampled threshold's proof: k candidates above it (or every key there is)
             avail = (self.list_off[1:] - self.list_off[:-1])[pi.clamp(min=0)].masked_fill(pi < 0, 0).sum(1)
             short = cc.to(torch.int64) < avail.clamp(max=k)
-            self.stats.add("underflow", lambda short=short: short.sum().double())
+            stats.add("underflow", lambda short=short: short.sum().double())
             over = torch.where(short, torch.full_like(sc, self.UNDERFLOW), over)
         return over
-
-    def check(self):
-        """Kept for callers of earlier versions: ``search_device`` itself re-searches queries whose survivors did not fit."""
-        return None
 
     def search(self, queries, k):
         d, i = self.search_device(torch.as_tensor(np.asarray(queries)), k)

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GNNLM_ABI_VERSION 11
+#define GNNLM_ABI_VERSION 12
 #define GNNLM_OK 0
 #define GNNLM_E_INVALID (-22)
 #define GNNLM_E_NOMEM (-12)
@@ -341,7 +341,9 @@ int gnnlm_ivfpq_pack_lut(const float* lut, int64_t ld_lut, int64_t n, int32_t M,
  *   gnnlm_ivfpq_tau            the threshold itself: a lower bound of the k-th best score from histograms of the integer sums of
  *                              the first D lists (gnnlm_ivfpq_scan8 with out_hist), replacing the float32 dense round + its k-selection
  *   gnnlm_ivfpq_rescore        exact scores of the survivors (summation order of gnnlm_ivfpq_scan's packed kernel),
- *                              score > tau[q] -> (cand_val, cand_id = payload[row]); cand_cnt[q] counts all of them
+ *                              score > tau[q] -> (cand_val, cand_id = payload[row]); cand_cnt[q] counts all of them.  With
+ *                              `qmeta` the threshold is first refined from the survivors themselves, in the same launch
+ * ABI 12: the refinement (ABI 7) has no entry point of its own any more; it runs only inside gnnlm_ivfpq_rescore (ABI 10).
  * ---------------------------------------------------------------------------------------------- */
 int gnnlm_ivfpq_pack_tiles(const uint8_t* codes, int64_t N, int32_t M, uint8_t* out, void* stream);
 int gnnlm_ivfpq_quantize_lut(const float* lut, int64_t ld_lut, int64_t n, int32_t M, uint8_t* qlut, float* qmeta, void* stream);
@@ -402,33 +404,25 @@ typedef struct gnnlm_ivfpq_tau {
     float* tau;
 } gnnlm_ivfpq_tau_t;
 int gnnlm_ivfpq_tau(const gnnlm_ivfpq_tau_t* desc, void* stream);
-/* ABI 7.  Between the filter and the re-score: a tighter threshold from the survivors themselves.  A survivor record is
- * {row, list | sum_u << 18} with sum_u the key's integer sum (16383: more than the filter's staging could hold): a lower bound of
- * the key's score over ALL probed lists.  tau[q] <- max(tau[q], the k-th largest lower bound of query q's survivors) (at
- * least k keys score above it), the records whose upper bound cannot exceed it are dropped (compacted in place), out_cnt
- * [n, 16] int32 (column 0) = records left; surv_cnt stays what the filter counted.  The search result does not change. */
-typedef struct gnnlm_ivfpq_refine {
-    uint32_t* surv;  const int32_t* surv_cnt;  int32_t* out_cnt;  int32_t cap;
-    float* tau;  const float* qmeta;
-    const float* coarse;  int64_t ld_coarse;
-    int64_t n;  int32_t k;
-} gnnlm_ivfpq_refine_t;
-int gnnlm_ivfpq_refine(const gnnlm_ivfpq_refine_t* desc, void* stream);
 /* ABI 7.  Results of a search over an index that carries labels (payload = id << label_bits | label, -1 = no result): idx [n]
  * -> the ids in place, out_vals [n] (optional) the labels, `val_last` where there is no result (numpy's vals[-1], knn_model.py:198) */
 int gnnlm_ivfpq_split_payload(int64_t* idx, int64_t n, int32_t label_bits, int32_t val_last, int32_t* out_vals, void* stream);
 typedef struct gnnlm_ivfpq_rescore {
     const uint8_t* codes;  const int64_t* payload;    /* [N, M] list-ordered codes, [N] what a candidate carries (key id, or id << 24 | label) */
-    int32_t M;
+    int32_t M;                                        /* 64 */
     const float* lut;  int64_t ld_lut;                /* [n, M * 256] f32 */
     const float* coarse;  int64_t ld_coarse;
     const float* tau;
     const uint32_t* surv;  const int32_t* surv_cnt;  int32_t cap;
     int64_t n;
     float* cand_val;  int64_t* cand_id;  int32_t* cand_cnt;  int32_t cand_cap;
-    /* ABI 10: with `qmeta` (M = 64, k > 0) the refinement of gnnlm_ivfpq_refine runs inside the same launch, ahead of the re-score
-     * and under the arrival of the query's table: surv is compacted in place, tau[q] raised in place (both are written through
-     * these pointers), out_cnt [n, 16] int32 (column 0; optional) = records left, as there.  NULL: the re-score alone. */
+    /* ABI 10: with `qmeta` (k > 0) a tighter threshold from the survivors themselves, in the same launch ahead of the re-score and
+     * under the arrival of the query's table.  A survivor record is {row, list | sum_u << 18} with sum_u the key's integer sum
+     * (16383: more than the filter's staging could hold): a lower bound of the key's score over ALL probed lists.
+     * tau[q] <- max(tau[q], the k-th largest lower bound of query q's survivors) (at least k keys score above it), the records
+     * whose upper bound cannot exceed it are dropped: surv is compacted in place, tau raised in place (both are written through
+     * these pointers), out_cnt [n, 16] int32 (column 0; optional) = records left; surv_cnt stays what the filter counted.  The
+     * search result does not change.  NULL: the re-score alone. */
     const float* qmeta;  int32_t k;  int32_t* out_cnt;
 } gnnlm_ivfpq_rescore_t;
 int gnnlm_ivfpq_rescore(const gnnlm_ivfpq_rescore_t* desc, void* stream);

@@ -1,6 +1,7 @@
 """gnnlm_ivfpq_tables (csrc/ivfpq_mfma.hip): the f32 ADC tables and their int8 image in one launch.  Contract under test: the
 three outputs are BIT-identical to the pair it replaces (gnnlm_gemm_nt with the descriptor of IVFPQIndex._tables_begin, then
-gnnlm_ivfpq_quantize_lut), and a whole search with it (GNNLM_IVF_TABLES=1, the default) equals the search without it."""
+gnnlm_ivfpq_quantize_lut), and a whole search with it (the default) equals the float32 scan's.  Also: the work counters of a
+search are its own when two searches are in flight on one index."""
 import numpy as np
 import pytest
 import torch
@@ -89,16 +90,25 @@ def _index(dev, d, N, seed):
 
 
 @pytest.mark.parametrize("d,N", [(256, 150_001), (1024, 60_000)])     # dsub 4 (the small_index shape) and 16 (the reference's)
-def test_search_with_fused_tables_equals_two_launches(dev, monkeypatch, d, N):
+def test_search_with_fused_tables_equals_f32_scan(dev, d, N):
     from gnnlm_amd.ivfpq import IVFPQIndex
+    from test_ivfpq_mfma_gpu import _assert_same
     index, q = _index(dev, d, N, seed=d)
-    args = (index.R, index.coarse, index.pq, index.list_off, index.list_ids, index.list_codes)
-    monkeypatch.setenv("GNNLM_IVF_TABLES", "0")
-    old = IVFPQIndex(*args, nprobe=9)
-    monkeypatch.setenv("GNNLM_IVF_TABLES", "1")
-    new = IVFPQIndex(*args, nprobe=9)
-    assert new.fused_tables and not old.fused_tables
+    f32 = IVFPQIndex(index.R, index.coarse, index.pq, index.list_off, index.list_ids, index.list_codes, nprobe=9, scan="f32")
     for k in (1024, 64):
-        va, ia = old.search_device(q, k)
-        vb, ib = new.search_device(q, k)
-        assert torch.equal(va, vb) and torch.equal(ia, ib), k
+        va, ia = index.search_device(q, k)
+        vb, ib = f32.search_device(q, k)
+        _assert_same(va.cpu().numpy(), ia.cpu().numpy(), vb.cpu().numpy(), ib.cpu().numpy(), k)
+
+
+def test_stats_belong_to_the_search_that_finished(dev):
+    """Two searches in flight on one index (bench.py --lanes, the pipelined eval_lm): index.stats describes the search that
+    finished last, not the one that began last."""
+    index, q = _index(dev, 256, 150_001, seed=256)
+    a = index.search_begin(q, 1024)
+    b = index.search_begin(q[:20].contiguous(), 1024)
+    a.result()
+    assert index.stats["queries"] == 77
+    pairs_a = float(index.stats["pairs"])
+    b.result()
+    assert index.stats["queries"] == 20 and float(index.stats["pairs"]) < pairs_a

@@ -432,22 +432,20 @@ def test_empty_list_among_the_threshold_lists(dev, small_index):
     _assert_same(v, i, vf.cpu().numpy(), if_.cpu().numpy())
 
 
-def test_search_result_does_not_depend_on_the_grouping(dev, small_index):
+def test_search_result_does_not_depend_on_the_grouping(dev, small_index, monkeypatch):
     """Which queries of a list share a workgroup, and in which order survivors and candidates are appended, is decided by
     atomics (gnnlm_ivfpq_build_groups, the survivor counters): the RESULT must not depend on it -- repeated searches, the torch
     reference of the task table and a shuffled query order all give the same scores and ids, bit for bit."""
-    import os
+    from gnnlm_amd.ivfpq import build_groups
     index, q = small_index
     qd = torch.from_numpy(np.concatenate([q, q[::-1], q[5:25]])).to(dev)
     v0, i0 = index.search_device(qd, 1024)
     for _ in range(3):
         v, i = index.search_device(qd, 1024)
         assert torch.equal(v, v0) and torch.equal(i, i0)
-    os.environ["GNNLM_IVF_TORCH_GROUPS"] = "1"
-    try:
-        v, i = index.search_device(qd, 1024)
-    finally:
-        del os.environ["GNNLM_IVF_TORCH_GROUPS"]
+    monkeypatch.setattr(index, "_groups", lambda pl, seg=None: build_groups(pl, index.nlist, seg))
+    v, i = index.search_device(qd, 1024)
+    monkeypatch.undo()
     assert torch.equal(v, v0) and torch.equal(i, i0)
     perm = torch.randperm(qd.shape[0], generator=torch.Generator().manual_seed(3)).to(dev)
     v, i = index.search_device(qd[perm].contiguous(), 1024)
@@ -550,9 +548,9 @@ def test_reference_shape_search_vs_oracle(dev, reference_shape_index, tmp_path):
 
 
 def test_refine_tightens_the_threshold_and_keeps_the_result(dev, small_index):
-    """gnnlm_ivfpq_refine (ABI 7): the k-th largest LOWER bound among a query's survivors is a valid threshold (at least k keys of
-    the probed lists score above it), never below the threshold pass's, the records dropped cannot beat it, and the search result is
-    the one without the step -- bit for bit."""
+    """The threshold refinement inside the re-score (gnnlm_ivfpq_rescore with qmeta): the k-th largest LOWER bound among a query's
+    survivors is a valid threshold (at least k keys of the probed lists score above it), never below the threshold pass's, the records
+    dropped cannot beat it, and the search result is the one without the step -- bit for bit."""
     from gnnlm_amd.ivfpq import IVFPQIndex
     index, q = small_index
     args = (index.R, index.coarse, index.pq, index.list_off, index.list_ids, index.list_codes)
