@@ -16,9 +16,14 @@ Inputs are resident in HBM when the timed region starts.  N > 1: every rank scor
 
 Prints ONE JSON line (rank 0).  `roofline` describes the kernel with the largest share of the step,
 timed with HIP events on its launch stream inside the timed region; `kernels` lists every kernel of
-the step from a profiled warm-up step; `cpu_baseline` is the CPU oracle (the reference algorithm as
-written, torch-CPU fp32) on a bounded sample.  `--dump-outputs DIR` also writes what the last timed step returned
+the step from a profiled warm-up step.  `--dump-outputs DIR` also writes what the last timed step returned
 (every input is seeded: the same arguments give the same inputs, so two builds compare output for output).
+
+A plain run does only what the headline figure needs: set-up, warm-up and settle, the timed steps, the dump, the line.
+`--full` adds the rest.  Before the timed region: the oracle parity gates of the step and of the search, and the distance
+of an opt-in --precision from f32.  After it: the same steps with the search results given, the replicated-store comparison
+of a sharded run, the sub-benchmarks (recipe_L3, driver_path, knn_search), the label-gather A/B of the kNN interpolation and
+`cpu_baseline`, the CPU oracle (the reference algorithm as written, torch-CPU fp32) on a bounded sample.
 """
 import argparse
 import json
@@ -66,10 +71,13 @@ def parse():
                     help="untimed back-to-back steps run before the timed region until this many seconds of GPU work have "
                          "passed AND two successive chunks agree within 2 %% (clock / power state settled)")
     ap.add_argument("--settle-max-s", type=float, default=6.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the first block before timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need (parity gates, search-given leg, replicated-store "
+                         "comparison, sub-benchmarks, label-gather A/B, CPU baseline); the --no-* switches below leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the oracle checks of the first block and of the search before timing")
     ap.add_argument("--no-extras", dest="extras", action="store_false",
-                    help="skip the recipe_L3 and driver_path sub-benchmarks (run after the timed region, N = 1 only)")
+                    help="--full: skip the recipe_L3, driver_path and knn_search sub-benchmarks (run after the timed region, N = 1 only)")
     ap.add_argument("--cpu-tokens", type=int, default=384)
     ap.add_argument("--l3-blocks", type=int, default=16, help="blocks per step of the 3-layer recipe sub-benchmark (recipe_L3)")
     ap.add_argument("--l3-steps", type=int, default=20)
@@ -1307,15 +1315,14 @@ def main():
             if keep_last:
                 graph_outs[bi] = out                              # (the graph's own memory: rewritten by every replay)
 
-    # ---- parity gate FIRST (7 s of CPU-only oracle with the GPU idle: nothing timed may follow it closely): the engine that is
-    # about to be timed against the oracle on a prefix of its first block
-    if rank == 0:
-        stage("parity gate")
+    # ---- --full: parity gate FIRST (7 s of CPU-only oracle with the GPU idle: nothing timed may follow it closely): the engine
+    # that is about to be timed against the oracle on a prefix of its first block
     parity = None
-    if rank == 0 and fetcher is None and not args.no_parity:
+    if rank == 0 and fetcher is None and args.full and not args.no_parity:
+        stage("parity gate")
         parity = verify_block(eng, batches[0], args, cpu_model, min(args.tokens_per_sample, 256 if args.layers == 1 else 64))
     dlogp = None
-    if args.precision != "f32" and fetcher is None:               # accuracy of the opt-in mode on one real batch
+    if args.full and args.precision != "f32" and fetcher is None:    # accuracy of the opt-in mode on one real batch
         got = eng.score(batches[0], args.lmbda, args.temperature)["logp"].clone()
         eng.hgt.gemm_precision = eng.asm.gemm_precision = 0
         ref = eng.score(batches[0], args.lmbda, args.temperature)["logp"]
@@ -1328,7 +1335,7 @@ def main():
     step(0)
     barrier()
     search_gate = None
-    if idx is not None and rank == 0 and args.search_check > 0 and not args.no_parity:
+    if args.full and idx is not None and rank == 0 and args.search_check > 0 and not args.no_parity:
         # the search the step is about to run, against the float64 oracle on the step's own queries (refuses to go on otherwise)
         # (with a sharded store the HGT forward is a collective step: rank 0 alone checks the search on the block's input features)
         q0 = eng.features(batches[0]) if fetcher is None else batches[0].tgt_feats.float()
@@ -1425,14 +1432,14 @@ def main():
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)) if args.streams == 1 and n_lanes == 1 else []
     for a in accs[1:] + lane_accs[1:]:
         acc += a
-    # ---- the same K steps with the search results GIVEN (the batches' precomputed sims / ids: rounds 1-5 quoted this as `value`)
-    if rank == 0:
-        stage("search-given leg")
+    # ---- --full: the same K steps with the search results GIVEN (the batches' precomputed sims / ids: rounds 1-5 quoted this as `value`)
     given = None
     search_stats = None
     if idx is not None:
         search_stats = {k_: (float(v_.item()) if torch.is_tensor(v_) else v_) for k_, v_ in idx.stats.items()}
-        if fetcher is None:
+        if fetcher is None and args.full:
+            if rank == 0:
+                stage("search-given leg")
             acc_g = torch.zeros(1, device=dev, dtype=torch.float64)
             run_g = lambda i: ops.masked_sum_f64(eng.score(batches[i % len(batches)], args.lmbda, args.temperature)["logp"], None, acc_g)
             for i in range(3):
@@ -1461,6 +1468,7 @@ def main():
                     fetcher.account_merged(n_, c_, 2, 2)
                 fetcher.link_bytes *= n_fetches[0] / len(mc)
         link_bytes_per_step = fetcher.link_bytes / max(1, n_fetches[0])
+    if fetcher is not None and args.full:
         # the same steps on a REPLICATED store (every rank holds the whole table, no exchange): what the sharding costs
         from gnnlm_amd.engine import GnnLmEngine
         from gnnlm_amd.hgt import CodeStore
@@ -1491,10 +1499,9 @@ def main():
                 dtr = ttr.item()
             replicated = {"tokens_per_s": round(args.steps * args.blocks * args.tokens_per_sample * world / dtr, 1),
                           "ms_per_step": round(dtr / args.steps * 1e3, 4)}
-    if rank == 0:
-        stage("extras")
     recipe = drv = search = None
-    if rank == 0 and world == 1 and fetcher is None and not args.small and args.extras:
+    if rank == 0 and world == 1 and fetcher is None and not args.small and args.full and args.extras:
+        stage("extras")
         if args.layers == 1 and args.precision == "f32":
             stage("extras: recipe_L3")
             recipe = recipe_l3(args, eng, batches, dev)
@@ -1556,7 +1563,7 @@ def main():
         if name == "knn_interp_kernel" and knn_ab is not None:
             r_["label_gather"] = knn_ab
         return r_
-    knn_ab = knn_interp_ab() if rank == 0 else None
+    knn_ab = knn_interp_ab() if rank == 0 and args.full else None
     if rank == 0:
         r = roof(dominant, prof)      # (the filter: `pairs` of idx.stats are the (query, key) pairs of ONE search -- every launch of the timed region scans as many)
         r["traffic"], r["traffic_source"] = pmc_traffic(dominant)
@@ -1614,7 +1621,7 @@ def main():
             res["driver_path"] = drv
         if search is not None:
             res["knn_search"] = search
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             stage("cpu_baseline")
             res["cpu_baseline"] = cpu_baseline(args, cpu_model)
         print(json.dumps(res))

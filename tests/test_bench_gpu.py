@@ -28,7 +28,7 @@ def run_bench(*extra):
 @pytest.mark.parametrize("extra", [(), ("--force-exchange",), ("--force-exchange", "--shard-vals", "--layers", "2"),
                                    ("--graph", "--no-cpu-baseline"), ("--precision", "bf16x6", "--no-cpu-baseline")])
 def test_bench_contract(extra):
-    r = run_bench(*extra)
+    r = run_bench("--full", *extra)
     for k in REQUIRED:
         assert k in r, k
     assert r["n_gpus"] == 1 and r["steps"] == 3 and r["warmup"] == 2 and r["higher_is_better"] is True
@@ -52,7 +52,7 @@ def test_bench_search_inside_the_step():
     timed step (`value`), checked against the float64 oracle first; the search-given figure rides beside it; one lane and three
     lanes (batches in flight on separate streams) add up the same scores."""
     common = ("--n-store", "3000000", "--blocks", "4", "--steps", "4", "--warmup", "3", "--gcn-k", "16", "--k", "64", "--settle-s", "0.05",
-              "--no-cpu-baseline", "--no-extras", "--search-check", "8")
+              "--full", "--no-cpu-baseline", "--no-extras", "--search-check", "8")
     out = {}
     for lanes in ("1", "3"):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *common, "--lanes", lanes]
@@ -75,6 +75,35 @@ def test_bench_search_inside_the_step():
     assert r["config"]["synthetic_ppl"] == out["1"]["config"]["synthetic_ppl"]
 
 
+def test_bench_plain_run_is_lean(tmp_path):
+    """A plain run (no --full) sets up, warms up, times its steps, dumps and prints the headline line: no parity gates, search-given
+    leg, sub-benchmarks or CPU baseline.  It computes what the same run with --full computes: the same score sum and dumped outputs."""
+    import numpy as np
+    common = ("--n-store", "3000000", "--blocks", "4", "--steps", "3", "--warmup", "3", "--gcn-k", "16", "--k", "64", "--settle-s", "0.05",
+              "--search-check", "8")
+    out = {}
+    for name, extra in (("plain", ()), ("full", ("--full", "--no-cpu-baseline", "--no-extras"))):
+        d = tmp_path / name
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *common, *extra, "--dump-outputs", str(d)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        out[name] = json.loads(lines[0]), {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    (r, files), (rf, files_f) = out["plain"], out["full"]
+    for k in REQUIRED:
+        assert k in r, k
+    assert r["value"] > 0 and r["value_includes_search"] is True and r["steps"] == 3 and r["warmup"] == 3
+    for k in ("parity", "cpu_baseline", "recipe_L3", "driver_path", "knn_search"):
+        assert k not in r, k
+    assert r["value_search_given"] is None and r["config"]["knn_search"]["parity"] is None
+    assert rf["value_search_given"] > 0 and rf["parity"]["max_abs_dlogp_vs_oracle"] < 1e-4 and rf["config"]["knn_search"]["parity"]["ok"] is True
+    assert r["config"]["synthetic_ppl"] == rf["config"]["synthetic_ppl"]
+    assert sorted(files) == sorted(files_f)
+    for k in files:
+        assert np.array_equal(files[k], files_f[k]), k
+
+
 def test_bench_modes_agree():
     """The sharded-store exchange and the HIP-graph replay reproduce the direct path's score sum."""
     a = run_bench("--no-cpu-baseline")
@@ -92,7 +121,7 @@ def test_bench_two_ranks_on_one_gpu(extra):
     timing and the score reduction -- runs with a real second rank.  L = 2 goes through the halo layout."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29613", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--small", "--blocks", "2", "--steps", "3",
-           "--warmup", "2", "--n-store", "30000", "--gcn-k", "16", "--k", "32", "--tokens-per-sample", "32", "--no-cpu-baseline",
+           "--warmup", "2", "--n-store", "30000", "--gcn-k", "16", "--k", "32", "--tokens-per-sample", "32", "--full", "--no-cpu-baseline",
            "--settle-s", "0.05", *extra]
     env = dict(os.environ, GNNLM_BENCH_BACKEND="gloo", GNNLM_BENCH_DEVICE="0")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
@@ -114,7 +143,7 @@ def test_bench_two_ranks_search_inside_the_step():
     the exchange, and every rank's OWN replica of the kNN index searched inside its timed step (weak scaling: no collective on the
     search).  Both ranks on device 0 over gloo."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n-store", "3000000", "--blocks", "4", "--steps", "3", "--warmup", "3",
-           "--gcn-k", "16", "--k", "64", "--settle-s", "0.05", "--no-cpu-baseline", "--no-extras", "--search-check", "8"]
+           "--gcn-k", "16", "--k", "64", "--settle-s", "0.05", "--full", "--no-cpu-baseline", "--no-extras", "--search-check", "8"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GNNLM_BENCH_BACKEND="gloo", GNNLM_BENCH_DEVICE="0")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
@@ -130,7 +159,7 @@ def test_bench_plain_launch_starts_its_own_ranks():
     """`python bench.py --gpus 2` with NO launcher around it (what the driver's scaling run types): the script starts the two
     ranks itself as child processes, relays rank 0's one JSON line and the exit code.  Both ranks on device 0 over gloo."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--small", "--blocks", "2", "--steps", "3", "--warmup", "2",
-           "--n-store", "30000", "--gcn-k", "16", "--k", "32", "--tokens-per-sample", "32", "--no-cpu-baseline", "--settle-s", "0.05"]
+           "--n-store", "30000", "--gcn-k", "16", "--k", "32", "--tokens-per-sample", "32", "--full", "--no-cpu-baseline", "--settle-s", "0.05"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GNNLM_BENCH_BACKEND="gloo", GNNLM_BENCH_DEVICE="0")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
