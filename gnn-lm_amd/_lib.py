@@ -116,6 +116,7 @@ def lib():
         L.gnnlm_adaptive_workspace_bytes.argtypes = [vp, i64]
         L.gnnlm_adaptive_target_logp.argtypes = [vp, vp, i64, vp, i64, vp, vp, ctypes.c_size_t, vp]
         L.gnnlm_masked_sum_f64.argtypes = [vp, vp, i64, vp, vp]
+        L.gnnlm_rows_sum_f64.argtypes = [vp, i64, i64, i64, vp, vp]
         L.gnnlm_ivfpq_pack_codes.argtypes = [vp, i64, i32, vp, vp]
         L.gnnlm_ivfpq_pack_lut.argtypes = [vp, i64, i64, i32, vp, vp]
         L.gnnlm_ivfpq_pack_tiles.argtypes = [vp, i64, i32, vp, vp]
@@ -128,7 +129,7 @@ def lib():
         L.gnnlm_hgt_workspace_bytes.argtypes = [vp, vp]
         L.gnnlm_hgt_forward.argtypes = [vp, vp, vp, ctypes.c_size_t, vp]
         for nm in ("gnnlm_gemm_nt", "gnnlm_pq_gather_decode", "gnnlm_star_attn", "gnnlm_chain_attn",
-                   "gnnlm_knn_interp", "gnnlm_topk_merge", "gnnlm_ivfpq_scan", "gnnlm_gather_rows_peer",
+                   "gnnlm_knn_interp", "gnnlm_knn_interp_grid", "gnnlm_topk_merge", "gnnlm_ivfpq_scan", "gnnlm_gather_rows_peer",
                    "gnnlm_ivfpq_scan8", "gnnlm_ivfpq_rescore", "gnnlm_ivfpq_tau", "gnnlm_group_assign",
                    "gnnlm_ivfpq_tables"):
             getattr(L, nm).argtypes = [vp, vp]

@@ -171,8 +171,12 @@ int label_tags(const void* vals, int itemsize, int64_t n, uint8_t* tag, hipStrea
 size_t knn_interp_scratch_bytes(int64_t n, int k, int64_t n_local);
 bool knn_interp_bucketed_eligible(const KnnInterpParams& p);
 int knn_interp_bucketed(const KnnInterpParams& p, float log_1ml, float log_l, hipStream_t stream);
+// every point of ks x temperatures x lmbdas from one read of the search result (knn_grid.hip)
+int knn_interp_grid(const gnnlm_knn_interp_grid_t& d, hipStream_t stream);
 
 // sum of x[start[b] : ] per ... simple masked sum in double: out[0] += sum(x[i] * (mask?mask[i]:1))
 int masked_sum_f64(const float* x, const uint8_t* mask, int64_t n, double* out, hipStream_t stream);
+// out[g] += sum(x[g * ld : g * ld + n]) for g < rows, each row in masked_sum_f64's summation order (knn_grid.hip)
+int rows_sum_f64(const float* x, int64_t ld, int64_t rows, int64_t n, double* out, hipStream_t stream);
 
 }  // namespace gnnlm

@@ -16,6 +16,11 @@ same tokens in the same order, eval_lm.py:238-242), features ``{split}_dstore/ke
 neighbours ``neighbors.mmap.{gcn_k}``, PQ codes ``train_dstore/quantized-keys.npy``; blocks follow
 ``--sample-break-mode none`` (token_block_utils_fast.pyx:22-35).  Every table is uploaded to HBM once.
 Output: the reference's two final lines (eval_lm.py:325-331).
+
+Tuning in one pass (this build): ``--sweep-lmbda 0,0.1,0.25 --sweep-temperature 1,0.1 --sweep-k 256,1024`` scores every point
+of the grid from the run's one forward and one search (the reference runs the whole evaluation once per setting,
+gnnlm_scripts/wiki103/hgt_lm_wiki103_reproduce.sh:137) and prints one ``sweep k=.. temperature=.. lmbda=.. loss=.. ppl=..``
+line per point after the two result lines.
 """
 import argparse
 import ast
@@ -113,6 +118,14 @@ def get_parser():
                         "the streams of a call land on; 6: 0.85-0.88 M every time; 8: 0.82-0.98 M.  0 (default): 6 when the batches are single blocks "
                         "(the recipe's `--max-tokens 256` with --batch-blocks 0), else 1.  Not with --store sharded "
                         "(collectives stay on one stream)")
+    p.add_argument("--sweep-lmbda", default=None,
+                   help="(this build) with --knnlm: comma-separated interpolation weights (0 <= lmbda <= 1).  Any of the three --sweep-* lists turns "
+                        "the run into a tuning sweep: every point of --sweep-k x --sweep-temperature x --sweep-lmbda is scored from the SAME forward "
+                        "and the SAME search as the run's own setting (one pass instead of one per point), and printed as one `sweep ...` line "
+                        "after the two result lines.  A list not given is the run's own --lmbda / --temperature / --k")
+    p.add_argument("--sweep-temperature", default=None, help="(this build) comma-separated softmax temperatures (> 0), see --sweep-lmbda")
+    p.add_argument("--sweep-k", default=None, help="(this build) comma-separated neighbour counts, each 1 <= k' <= --k (the first k' of the search's "
+                                                   "result: what a k'-search returns), see --sweep-lmbda")
     p.add_argument("--result-json", default=None,
                    help="(this build) write the run's figures (score_sum, count, ppl, tokens, seconds, per-rank sums, xGMI bytes) to this "
                         "file as JSON; in a multi-process run rank r writes PATH.rank<r> and rank 0 also PATH")
@@ -212,6 +225,62 @@ def word_outputs(args, hypos, sample_ids, symbols, bpe_toks, bpe_len, word_stats
             else:
                 logger.info(str(int(sample_ids[i])) + " " + ('\t'.join('{} [{:2f}]'.format(x[0], x[1]) for x in word_prob)))
     return skipped_total
+
+
+SWEEP_MAX = {"k": 8, "temperature": 16, "lmbda": 16}     # capacities of gnnlm_knn_interp_grid_t
+
+
+def parse_sweep(args):
+    """The run's tuning grid ``(ks, temperatures, lmbdas)`` from --sweep-k / --sweep-temperature / --sweep-lmbda, or None when none of
+    them is given.  A list not given is the run's own value.  Host-only: raises ``ValueError`` before any device work.  The options are
+    read with getattr: callers that build their own namespace (bench.py) do not know them."""
+    raw = {"k": getattr(args, "sweep_k", None), "temperature": getattr(args, "sweep_temperature", None), "lmbda": getattr(args, "sweep_lmbda", None)}
+    if all(v is None for v in raw.values()):
+        return None
+    if not getattr(args, "knnlm", False):
+        raise ValueError("--sweep-lmbda / --sweep-temperature / --sweep-k need --knnlm (there is no kNN term to tune otherwise)")
+    if getattr(args, "save_knnlm_dstore", False):
+        raise ValueError("--sweep-* cannot be combined with --save-knnlm-dstore")
+    own = {"k": args.k, "temperature": args.temperature, "lmbda": args.lmbda}
+    out = {}
+    for name, conv in (("k", int), ("temperature", float), ("lmbda", float)):
+        if raw[name] is None:
+            out[name] = [conv(own[name])]
+            continue
+        items = [v.strip() for v in str(raw[name]).split(",")]
+        try:
+            out[name] = [conv(v) for v in items]
+        except ValueError:
+            raise ValueError(f"--sweep-{name}: expected a comma-separated list of {'integers' if conv is int else 'numbers'}, got {raw[name]!r}")
+        if len(out[name]) > SWEEP_MAX[name]:
+            raise ValueError(f"--sweep-{name}: at most {SWEEP_MAX[name]} values per run, got {len(out[name])}")
+        if len(set(out[name])) != len(out[name]):
+            raise ValueError(f"--sweep-{name}: repeated value in {raw[name]!r}")
+    if any(not 1 <= v <= args.k for v in out["k"]):
+        raise ValueError(f"--sweep-k: every k' must lie in 1 .. --k ({args.k}): the sweep reads the first k' neighbours of the run's own search")
+    if args.k > 1024:
+        raise ValueError("--sweep-*: --k > 1024 is not built for the sweep")
+    if any(not (v > 0.0 and math.isfinite(v)) for v in out["temperature"]):
+        raise ValueError("--sweep-temperature: every temperature must be > 0")
+    if any(not 0.0 <= v <= 1.0 for v in out["lmbda"]):
+        raise ValueError("--sweep-lmbda: every lmbda must lie in 0 .. 1")
+    return out["k"], out["temperature"], out["lmbda"]
+
+
+def sweep_table(sweep, sums, count):
+    """One dict per grid point in ``ops.grid_points`` order (k slowest, lmbda fastest) from the points' score sums."""
+    rows = []
+    for (k, t, l), ssum in zip(ops.grid_points(*sweep), sums):
+        loss = -ssum / count / math.log(2) if count else float("nan")
+        rows.append({"k": k, "temperature": t, "lmbda": l, "score_sum": ssum, "loss": loss, "ppl": 2 ** loss})
+    return rows
+
+
+def sweep_lines(rows):
+    """The printed form of :func:`sweep_table`: one line per point, the lowest perplexity marked."""
+    best = min(range(len(rows)), key=lambda i: rows[i]["ppl"]) if rows else -1
+    return ["sweep k={} temperature={:g} lmbda={:g} loss={:.4f} ppl={:.2f}{}".format(r["k"], r["temperature"], r["lmbda"], r["loss"], r["ppl"],
+                                                                                   "  <- best" if i == best else "") for i, r in enumerate(rows)]
 
 
 def block_ranges(n_tokens, block, context_window=0):
@@ -323,6 +392,8 @@ def main(args, tables=None, model=None):
         raise ValueError("--save-knnlm-dstore needs --dstore-mmap")
     if args.knnlm and args.save_knnlm_dstore:
         raise ValueError("Cannot use knnlm while trying to build the datastore!")
+    sweep = parse_sweep(args)
+    args.sweep = sweep                                                                     # (read by the scorer)
     if args.context_window > 0:
         # LMContextWindowDataset (fairseq/data/lm_context_window_dataset.py) prepends context tokens and scores only the
         # new ones; shrinking the block without the prefix would silently give another ppl
@@ -488,6 +559,9 @@ def main(args, tables=None, model=None):
     main_stream = torch.cuda.current_stream(device)
     lanes = [main_stream] + [torch.cuda.Stream(device=device) for _ in range(n_streams - 1)]
     accs = [acc] + [torch.zeros_like(acc) for _ in lanes[1:]]
+    # the sweep's score sums: one float64 per grid point and lane, fed by ONE launch per batch
+    n_grid = len(ops.grid_points(*sweep)) if sweep else 0
+    sweep_accs = {id(a_): torch.zeros(n_grid, device=device, dtype=torch.float64) for a_ in accs} if sweep else None
     for s_ in lanes[1:]:
         s_.wait_stream(main_stream)
     in_flight, order = [None] * n_streams, [0] * n_streams
@@ -495,8 +569,9 @@ def main(args, tables=None, model=None):
 
     def consume(hypos, sample, acc, ev0, ev1):
         """What the loop does with a batch's hypotheses (a handle of generate_begin is finished first), on the batch's own stream."""
-        if isinstance(hypos, dict):
-            hypos = scorer.generate_finish(hypos)
+        handle = hypos if isinstance(hypos, dict) else None
+        if handle is not None:
+            hypos = scorer.generate_finish(handle)
         ev1.record()
         timers.append((ev0, ev1))
         state["ntok"] += sample["ntokens"]
@@ -515,6 +590,8 @@ def main(args, tables=None, model=None):
             save["idx"] += n_new
         pos = torch.cat([h[0]["positional_scores"].float().reshape(-1) for h in hypos])     # one launch per batch
         ops.masked_sum_f64(pos, None, acc)                                                  # score_sum (:273), in f64
+        if sweep:
+            ops.rows_sum_f64(handle["sweep_logp"], sweep_accs[id(acc)])                     # the same positions, every grid point
         # ... and as the reference adds it up: one float32 sum per hypothesis (`pos_scores.sum()`), accumulated in a float32 scalar
         # (`score_sum += ...cpu()`, :273) -- the per-hypothesis sums are kept on the device and chained on the host at the end
         lens = [h[0]["positional_scores"].numel() for h in hypos]
@@ -559,8 +636,11 @@ def main(args, tables=None, model=None):
             order[lane] = bi
             continue
         ev0.record()
-        hypos = scorer.generate([model], sample, knn_dstore=knn_dstore, temperature=args.temperature) if args.knnlm \
-            else scorer.generate([model], sample)
+        if sweep:                                               # (the handle carries the grid's log-probs to consume)
+            hypos = scorer.generate_begin([model], sample, knn_dstore=knn_dstore, temperature=args.temperature)
+        else:
+            hypos = scorer.generate([model], sample, knn_dstore=knn_dstore, temperature=args.temperature) if args.knnlm \
+                else scorer.generate([model], sample)
         consume(hypos, sample, acc, ev0, ev1)
     for lane in sorted((l_ for l_ in range(n_streams) if in_flight[l_] is not None), key=lambda l_: order[l_]):   # what is still in flight, in batch order
         torch.cuda.set_stream(lanes[lane])
@@ -571,6 +651,8 @@ def main(args, tables=None, model=None):
         torch.cuda.set_stream(main_stream)
         for s_, a_ in zip(lanes[1:], accs[1:]):
             main_stream.wait_stream(s_)
+            if sweep:
+                sweep_accs[id(accs[0])] += sweep_accs[id(a_)]
             accs[0] += a_
         acc = accs[0]
         # what the model keeps per stream (merge tables of n_store x 4 bytes, scratch arenas) goes with the side lanes: the next
@@ -586,6 +668,7 @@ def main(args, tables=None, model=None):
     if fetcher is not None:
         fetcher.check()                                                                     # (padded exchange: nothing was dropped)
     score_sum = acc.item()                                                                  # the only host sync
+    sweep_sums = sweep_accs[id(acc)].tolist() if sweep else []
     if save is not None:
         save["keys"].flush()
         save["vals"].flush()
@@ -603,8 +686,10 @@ def main(args, tables=None, model=None):
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         # the one reduction of the data-parallel run (16 B + the timer): score_sum, count, tokens summed; the time is the slowest rank's
         host = dist.get_backend() != "nccl"
-        t = torch.tensor([score_sum, float(count), float(ntok)], device="cpu" if host else device, dtype=torch.float64)
+        # (a sweep's sums travel in the same collective: with --store sharded collectives are ordered, one more would be one too many)
+        t = torch.tensor([score_sum, float(count), float(ntok)] + sweep_sums, device="cpu" if host else device, dtype=torch.float64)
         dist.all_reduce(t)
+        sweep_sums = t[3:].tolist()
         tm = torch.tensor([gen_time, wall], device="cpu" if host else device, dtype=torch.float64)
         dist.all_reduce(tm, op=dist.ReduceOp.MAX)
         score_sum, count, ntok = t[0].item(), int(t[1].item()), int(t[2].item())
@@ -617,6 +702,11 @@ def main(args, tables=None, model=None):
         logger.info(line2)
         print(line1)
         print(line2)
+    sweep_rows = sweep_table(sweep, sweep_sums, count) if sweep else None
+    if sweep and (rank == 0 or not (dist.is_available() and dist.is_initialized())):
+        for line in sweep_lines(sweep_rows):
+            logger.info(line)
+            print(line)
     # the same with the reference's float32 accumulation (fairseq_cli/eval_lm.py:273-274): logged, not printed --
     # the two lines above are the reference's output.  Per rank in a multi-process run (the reference has one accumulator).
     if count_rank:
@@ -632,6 +722,8 @@ def main(args, tables=None, model=None):
             "wall_seconds": wall, "word_stats": word_stats if args.output_word_stats else None,
             "score_sum_f32_order": float(score_sum_f32), "rank": rank, "world": world, "store": store_mode, "rank_score_sum": rank_score_sum, "rank_tokens": rank_tokens,
             "xgmi_bytes": link_bytes}
+    if sweep:
+        res["sweep"] = sweep_rows
     if getattr(args, "result_json", None):
         js = {k_: v for k_, v in res.items() if k_ != "word_stats"}
         for path in ([args.result_json + f".rank{rank}"] if world > 1 else []) + ([args.result_json] if rank == 0 else []):

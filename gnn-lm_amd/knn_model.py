@@ -291,16 +291,35 @@ class KNNModel(object):
         dists, knns, kvals = self._search(q, k)
         return ("done", q, (dists, knns, kvals))
 
-    def interpolate_finish(self, handle, targets, lm_logp, t, lmbda):
+    def search_finish(self, handle):
+        """Wait for the search of ``interpolate_begin`` and return a handle that holds its result (``sims``, ``knns``, labels): it can be
+        handed to ``interpolate_finish`` and ``interpolate_grid_finish`` any number of times -- one search, several consumers."""
         kind, q, h = handle
+        if kind == "sims":
+            return handle
         dists, knns, kvals = h.result() if kind == "pending" else h
-        sims = self._sims(dists, knns, q).contiguous()
-        return ops.knn_interp(lm_logp.contiguous(), sims, knns.contiguous(), targets.long().contiguous(), t, lmbda,
+        return ("sims", q, (self._sims(dists, knns, q).contiguous(), knns.contiguous(), None if kvals is None else kvals.contiguous()))
+
+    def interpolate_finish(self, handle, targets, lm_logp, t, lmbda):
+        sims, knns, kvals = self.search_finish(handle)[2]
+        return ops.knn_interp(lm_logp.contiguous(), sims, knns, targets.long().contiguous(), t, lmbda,
                               vals=self.vals_device() if kvals is None else None, n_store=self.dstore_size,
-                              knn_vals=None if kvals is None else kvals.contiguous())
+                              knn_vals=kvals)
+
+    def interpolate_grid_finish(self, handle, targets, lm_logp, ks, temperatures, lmbdas):
+        """The sweep form of ``interpolate_finish``: every point of ``ks x temperatures x lmbdas`` (``ops.grid_points`` order) from the
+        search that was begun at the model's own ``k``, which bounds every k' -> (logp [G, n], p_knn, recall)."""
+        sims, knns, kvals = self.search_finish(handle)[2]
+        return ops.knn_interp_grid(lm_logp.contiguous(), sims, knns, targets.long().contiguous(), ks, temperatures, lmbdas,
+                                   vals=self.vals_device() if kvals is None else None, n_store=self.dstore_size, knn_vals=kvals)
 
     def interpolate(self, queries, targets, lm_logp, t, lmbda, k=0):
         """Fused hot-path form: search -> (interpolated log-prob [n], p_knn [n], recall [n])."""
         sims, knns, kvals = self.search_sims(queries, k, with_vals=True)
         return ops.knn_interp(lm_logp.contiguous(), sims, knns, targets.long().contiguous(), t, lmbda,
                               vals=self.vals_device() if kvals is None else None, n_store=self.dstore_size, knn_vals=kvals)
+
+    def interpolate_grid(self, queries, targets, lm_logp, ks, temperatures, lmbdas, k=0):
+        """One search, every point of the grid (the reference runs the whole evaluation once per setting,
+        gnnlm_scripts/wiki103/hgt_lm_wiki103_reproduce.sh:137): -> (logp [G, n], p_knn [len(ks) * len(temperatures), n], recall [len(ks), n])."""
+        return self.interpolate_grid_finish(self.interpolate_begin(queries, k), targets, lm_logp, ks, temperatures, lmbdas)

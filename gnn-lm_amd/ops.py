@@ -354,6 +354,53 @@ def knn_interp(lm_logp, sims, ids, targets, temperature, lmbda, vals=None, n_sto
     return out, pk, rec
 
 
+def grid_points(ks, temperatures, lmbdas):
+    """The points of a sweep in the one order every layer uses: k slowest, then temperature, lmbda fastest
+    (row g of ``knn_interp_grid``'s result, ``gnnlm_knn_interp_grid_t``)."""
+    return [(int(k), float(t), float(l)) for k in ks for t in temperatures for l in lmbdas]
+
+
+def knn_interp_grid(lm_logp, sims, ids, targets, ks, temperatures, lmbdas, vals=None, n_store=None, row0=0, knn_vals=None):
+    """Every point of ``ks x temperatures x lmbdas`` from one read of the search result (``gnnlm_knn_interp_grid``):
+    -> (logp [G, n] f32 in :func:`grid_points` order, p_knn [len(ks) * len(temperatures), n] f32, recall [len(ks), n] i64).
+    A point with 0 < lmbda < 1 equals ``knn_interp`` on the first k' columns bit for bit; lmbda 0 / 1 are allowed.  The label
+    table is read by the plain gather (no tag table, no routed look-ups); k <= 1024."""
+    _dev(lm_logp, sims, ids, targets, vals, knn_vals)
+    _f32(lm_logp, sims)
+    _dtype(ids, torch.int64, "ids"), _dtype(targets, torch.int64, "targets"), _dtype(knn_vals, torch.int32, "knn_vals")
+    if vals is not None and vals.dtype not in (torch.int16, torch.int32):
+        raise TypeError(f"vals: expected int16 / int32, got {vals.dtype}")
+    for t in (lm_logp, sims, ids, targets, vals, knn_vals):
+        if t is not None and not t.is_contiguous():
+            raise _lib.GnnlmError("knn_interp_grid needs contiguous tensors")
+    ks, temperatures, lmbdas = [int(v) for v in ks], [float(v) for v in temperatures], [float(v) for v in lmbdas]
+    n, k = sims.shape
+    dev = sims.device
+    d = _lib.gnnlm_knn_interp_grid_t()
+    d.lm_logp, d.sims, d.ids, d.targets = lm_logp.data_ptr(), sims.data_ptr(), ids.data_ptr(), targets.data_ptr()
+    d.vals_itemsize = 4
+    if vals is not None:
+        d.vals, d.vals_itemsize = vals.data_ptr(), vals.element_size()
+        d.n_local = vals.shape[0]
+        d.n_store = n_store if n_store is not None else vals.shape[0]
+        d.row0 = row0
+    if knn_vals is not None:
+        d.knn_vals = knn_vals.data_ptr()
+    d.n, d.k = n, k
+    # the counts go in as given: a list longer than the descriptor's array is refused by the library, never cut short
+    d.n_ks, d.n_temperatures, d.n_lmbdas = len(ks), len(temperatures), len(lmbdas)
+    for dst, src in ((d.ks, ks), (d.temperatures, temperatures), (d.lmbdas, lmbdas)):
+        for j, v in enumerate(src[:len(dst)]):
+            dst[j] = v
+    G = len(ks) * len(temperatures) * len(lmbdas)
+    out = torch.empty(G, n, device=dev, dtype=torch.float32)
+    pk = torch.empty(len(ks) * len(temperatures), n, device=dev, dtype=torch.float32)
+    rec = torch.empty(len(ks), n, device=dev, dtype=torch.int64)
+    d.out_logp, d.out_pknn, d.out_recall = out.data_ptr(), pk.data_ptr(), rec.data_ptr()
+    call_desc("gnnlm_knn_interp_grid", d)
+    return out, pk, rec
+
+
 def topk_merge(scores, best_val, best_id, col0=0, col_ids=None, col_scale=None, col_bias=None, alpha=1.0, largest=True,
                init=False, row_ncols=None, ids=None):
     """Fold the score chunk ``scores`` [n, ncols] into the running top-k state (``best_val`` f32 / ``best_id`` i64
@@ -415,3 +462,16 @@ def masked_sum_f64(x, mask=None, acc=None):
         acc = torch.zeros(1, device=x.device, dtype=torch.float64)
     call("gnnlm_masked_sum_f64", ptr(x), ptr(mask), x.numel(), ptr(acc), stream())
     return acc
+
+
+def rows_sum_f64(x, out):
+    """out[g] += sum(x[g, :]) in float64 for every row of ``x`` [G, n] in one launch (``gnnlm_rows_sum_f64``); row g is added
+    up in ``masked_sum_f64``'s order."""
+    _dev(x, out)
+    _f32(x)
+    _dtype(out, torch.float64, "out")
+    if x.dim() != 2 or out.dim() != 1 or out.shape[0] != x.shape[0] or not out.is_contiguous():
+        raise ValueError("rows_sum_f64: x [G, n] float32, out [G] float64")
+    x = x.contiguous()
+    call("gnnlm_rows_sum_f64", ptr(x), x.shape[1], x.shape[0], x.shape[1], ptr(out), stream())
+    return out

@@ -2,7 +2,9 @@
 
 Same constructor, same ``generate(models, sample, knn_dstore=..., temperature=...)`` call, same
 hypothesis dicts (``tokens, score, attention, alignment, positional_scores, dstore_keys, knn_recall``,
-:185-193).  What differs is only where the arithmetic runs: the dense ``[B, T, V]`` log-prob tensor and
+:185-193).  (This build) with ``args.sweep = (ks, temperatures, lmbdas)`` ``generate_finish`` also leaves
+``handle["sweep_logp"]`` [G, scored tokens]: every point of the kNN-LM tuning grid, from the batch's one search.
+What differs is only where the arithmetic runs: the dense ``[B, T, V]`` log-prob tensor and
 the host-side kNN gathers are replaced by the HIP kernels behind ``model.target_log_probs`` and
 ``KNNModel.interpolate``.
 
@@ -49,8 +51,11 @@ class SequenceScorer(object):
         bsz, tsz = orig_target.shape
         lmbda = getattr(self.args, "lmbda", 0.0)
         use_knn = "knn_dstore" in kwargs and lmbda > 0.0
+        # (this build) args.sweep = (ks, temperatures, lmbdas): the tuning grid is scored from this batch's one search -- which therefore
+        # runs with --lmbda 0 too (the hypotheses then stay the LM's)
+        sweep = getattr(self.args, "sweep", None) if "knn_dstore" in kwargs else None
         pending = None
-        if use_knn:
+        if use_knn or sweep:
             # (the reference's precondition is about ITS batch: with the driver's --batch-blocks the launch holds several of the recipe's
             # one-block batches, each of which must fit -- the recipe passes --softmax-batch 3072 for 256-token batches)
             assert (tsz if sample.get("blockwise_knn") else bsz * tsz) < self.softmax_batch, "kNN scoring needs B*T < --softmax-batch (sequence_scorer.py:105)"
@@ -65,7 +70,7 @@ class SequenceScorer(object):
                 pending = knn_model.interpolate_begin(queries.contiguous().view(-1, hidden))
         probs = model.target_log_probs(decoder_out, orig_target.clamp(min=0))
         return dict(sample=sample, decoder_out=decoder_out, probs=probs, use_knn=use_knn, pending=pending, lmbda=lmbda, temperature=temperature,
-                    knn_model=kwargs.get("knn_dstore"), queries=(queries if use_knn else None))
+                    knn_model=kwargs.get("knn_dstore"), queries=(queries if use_knn or sweep else None), sweep=sweep)
 
     @torch.no_grad()
     def generate_finish(self, h):
@@ -74,7 +79,20 @@ class SequenceScorer(object):
         orig_target = sample["target"]
         bsz, tsz = orig_target.shape
         recall = None
-        if use_knn:
+        sweep, grid = h.get("sweep"), None
+        if sweep:
+            # one search result, two consumers: the hypotheses' own setting and the grid (same targets, same pairing)
+            queries = h["queries"]
+            seq_len, b2, hidden = queries.shape
+            tq = (orig_target.transpose(0, 1) if sample.get("blockwise_knn") else orig_target.permute(0, 1)).reshape(seq_len * b2)
+            lm_flat = probs.transpose(0, 1).reshape(-1)
+            found = knn_model.search_finish(pending if pending is not None else knn_model.interpolate_begin(queries.contiguous().view(-1, hidden)))
+            grid = knn_model.interpolate_grid_finish(found, tq.clamp(min=0), lm_flat, *sweep)[0].view(-1, seq_len, b2).transpose(1, 2)   # [G, B, T]
+            if use_knn:
+                mixed, _, rec = knn_model.interpolate_finish(found, tq.clamp(min=0), lm_flat, temperature, lmbda)
+                probs = mixed.view(seq_len, b2).transpose(0, 1)
+                recall = rec.view(seq_len, b2).transpose(0, 1)
+        elif use_knn:
             queries = h["queries"]
             seq_len, b2, hidden = queries.shape
             # as written (:117): targets in [B, T] order against queries in [T, B] order -- only right for B = 1, the recipe.
@@ -101,6 +119,17 @@ class SequenceScorer(object):
             no_pad = not bool(sample["target"].eq(self.pad).any())
         hypos = []
         starts = [int(v) for v in start_idxs]
+        if grid is not None:
+            # the grid's log-probs of exactly the positions the hypotheses score, in the hypotheses' order: [G, scored tokens]
+            if no_pad and len(set(starts)) == 1:
+                h["sweep_logp"] = grid[:, :, starts[0]:].reshape(grid.shape[0], -1)
+            else:
+                keep = torch.zeros(bsz, tsz, dtype=torch.bool, device=grid.device)
+                for i in range(bsz):
+                    keep[i, starts[i]:] = True
+                if not no_pad:
+                    keep &= sample["target"].ne(self.pad)
+                h["sweep_logp"] = grid[:, keep]
         # one reduction for the whole batch instead of a sum and a division per hypothesis (64 launches per 32-block batch)
         score_all = probs[:, starts[0]:].sum(dim=1) / (tsz - starts[0]) if no_pad and len(set(starts)) == 1 and tsz > starts[0] else None
         for i in range(bsz):

@@ -261,6 +261,33 @@ typedef struct gnnlm_knn_interp {
 } gnnlm_knn_interp_t;
 int gnnlm_knn_interp(const gnnlm_knn_interp_t* desc, void* stream);
 size_t gnnlm_knn_interp_scratch_bytes(int64_t n, int32_t k, int64_t n_local);
+/* The tuning grid of kNN-LM in one call: every point of ks x temperatures x lmbdas from ONE read of the search result.
+ * Replaces: one whole `fairseq-eval-lm ... --lmbda $a` per setting (gnnlm_scripts/wiki103/hgt_lm_wiki103_reproduce.sh:137),
+ * i.e. get_knn_prob (knn/knn_model.py:192-217) + combine_knn_and_vocab_probs (fairseq/sequence_scorer.py:55-68,121) once per
+ * point.  Point (k', t, l), 1 <= k' <= k, t > 0, 0 <= l <= 1, is computed over the FIRST k' columns of sims / ids / knn_vals
+ * (the search returns neighbours best first: what a k'-search returns) and is bit-identical to gnnlm_knn_interp on those
+ * columns where that call is defined (0 < l < 1); l = 0 gives lm_logp back, l = 1 gives logf(p_knn + 1e-10f).
+ * The grid values are HOST data inside the descriptor (the call neither allocates nor copies); more values than the arrays
+ * hold, k > 1024 (gnnlm_knn_interp serves it, one setting per call) or a value out of range is GNNLM_E_INVALID and nothing is
+ * launched.  Labels as in gnnlm_knn_interp_t (knn_vals, or vals with n_store / row0 / n_local); no tag table, no routed
+ * look-ups.  Point index g = (ik * n_temperatures + it) * n_lmbdas + il: k slowest, lmbda fastest. */
+typedef struct gnnlm_knn_interp_grid {
+    const float* lm_logp;      /* [n] */
+    const float* sims;         /* [n, k] */
+    const int64_t* ids;        /* [n, k], -1 = padding */
+    const void* vals;  int32_t vals_itemsize;  int64_t n_store, row0, n_local;
+    const int32_t* knn_vals;   /* optional [n, k]: vals[ids] delivered by the search */
+    const int64_t* targets;    /* [n] */
+    int64_t n;  int32_t k;     /* k <= 1024 */
+    int32_t n_ks, n_temperatures, n_lmbdas;
+    int32_t ks[8];
+    float temperatures[16];
+    double lmbdas[16];
+    float* out_logp;           /* [n_ks * n_temperatures * n_lmbdas, n]: a point's tokens are contiguous */
+    float* out_pknn;           /* optional [n_ks * n_temperatures, n] */
+    int64_t* out_recall;       /* optional [n_ks, n] */
+} gnnlm_knn_interp_grid_t;
+int gnnlm_knn_interp_grid(const gnnlm_knn_interp_grid_t* desc, void* stream);
 /* tag[r] = (uint32(vals[r]) * 2654435761) >> 24 for the n rows of a label table (int16 / int32) */
 int gnnlm_label_tags(const void* vals, int32_t vals_itemsize, int64_t n, uint8_t* tag, void* stream);
 
@@ -430,6 +457,10 @@ int gnnlm_ivfpq_rescore(const gnnlm_ivfpq_rescore_t* desc, void* stream);
 /* out[0] += sum_i x[i] * (mask ? mask[i] != 0 : 1), accumulated in f64 (score_sum of
  * fairseq_cli/eval_lm.py:273; the reference accumulates in f32 on the CPU) */
 int gnnlm_masked_sum_f64(const float* x, const uint8_t* mask, int64_t n, double* out, void* stream);
+/* out[g] += sum_i x[g * ld + i], i < n, for the `rows` rows of a matrix (ld >= n), accumulated in f64: the score_sum of every
+ * point of a gnnlm_knn_interp_grid result in ONE launch.  Each row is added up in gnnlm_masked_sum_f64's order, so out[g]
+ * equals what that call gives for the row, bit for bit. */
+int gnnlm_rows_sum_f64(const float* x, int64_t ld, int64_t rows, int64_t n, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * HGT forward over the implicit token/neighbour graph
