@@ -129,7 +129,7 @@ def lib():
         L.gnnlm_hgt_workspace_bytes.argtypes = [vp, vp]
         L.gnnlm_hgt_forward.argtypes = [vp, vp, vp, ctypes.c_size_t, vp]
         for nm in ("gnnlm_gemm_nt", "gnnlm_pq_gather_decode", "gnnlm_star_attn", "gnnlm_chain_attn",
-                   "gnnlm_knn_interp", "gnnlm_knn_interp_grid", "gnnlm_topk_merge", "gnnlm_ivfpq_scan", "gnnlm_gather_rows_peer",
+                   "gnnlm_knn_interp", "gnnlm_knn_interp_grid", "gnnlm_knn_recompute_sims", "gnnlm_topk_merge", "gnnlm_ivfpq_scan", "gnnlm_gather_rows_peer",
                    "gnnlm_ivfpq_scan8", "gnnlm_ivfpq_rescore", "gnnlm_ivfpq_tau", "gnnlm_group_assign",
                    "gnnlm_ivfpq_tables"):
             getattr(L, nm).argtypes = [vp, vp]

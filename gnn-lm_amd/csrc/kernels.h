@@ -173,6 +173,8 @@ bool knn_interp_bucketed_eligible(const KnnInterpParams& p);
 int knn_interp_bucketed(const KnnInterpParams& p, float log_1ml, float log_l, hipStream_t stream);
 // every point of ks x temperatures x lmbdas from one read of the search result (knn_grid.hip)
 int knn_interp_grid(const gnnlm_knn_interp_grid_t& d, hipStream_t stream);
+// similarities recomputed from the stored keys, one wave per (query, run of 64 neighbours) (knn_resim.hip)
+int knn_recompute_sims(const gnnlm_knn_resim_t& d, hipStream_t stream);
 
 // sum of x[start[b] : ] per ... simple masked sum in double: out[0] += sum(x[i] * (mask?mask[i]:1))
 int masked_sum_f64(const float* x, const uint8_t* mask, int64_t n, double* out, hipStream_t stream);

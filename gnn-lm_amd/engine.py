@@ -59,7 +59,8 @@ class GnnLmEngine:
                           max_intra_context=self.max_intra_context, fetcher=self.fetcher if batch.fetched_codes is None else None)
         return self.hgt(G, features={"tgt": tgt})["tgt"]
 
-    def score(self, batch: BlockBatch, lmbda: float = 0.0, temperature: float = 1.0, knn_index=None, k: int = 0, sweep=None):
+    def score(self, batch: BlockBatch, lmbda: float = 0.0, temperature: float = 1.0, knn_index=None, k: int = 0, sweep=None,
+              knn_keys=None, knn_sim_func: str = "do_not_recomp_ip"):
         """Per-token log-probabilities.  Returns dict(gcn_feat, lm_logp, logp[, p_knn, recall]).
 
         ``sweep = (ks, temperatures, lmbdas)``: additionally ``sweep_logp`` [G, n], every point of the kNN-LM tuning grid
@@ -68,26 +69,40 @@ class GnnLmEngine:
         ``knn_index`` (an ``ivfpq.IVFPQIndex`` with the labels attached): the kNN search of the step's own queries -- the
         L2-normalised gcn_feat rows, knn_model.py:100,181-184 -- runs on the device inside the step, as it runs inside the
         reference's timer (fairseq_cli/eval_lm.py:214-219 around sequence_scorer.py:115-120); the batch's ``knn_*`` fields are
-        then not read.  The softmax is enqueued between the search and the host's one look at its survivor counts."""
-        return self.score_finish(self.score_begin(batch, lmbda, temperature, knn_index, k, sweep))
+        then not read.  The softmax is enqueued between the search and the host's one look at its survivor counts.
 
-    def score_begin(self, batch: BlockBatch, lmbda: float = 0.0, temperature: float = 1.0, knn_index=None, k: int = 0, sweep=None):
+        ``knn_keys`` (the key table in HBM, fp16 / f32 [n_store, d]) with ``knn_sim_func`` "ip" / "l2" (``--knn-sim-func``,
+        knn_model.py:161-175): the index's distances are replaced by the similarities recomputed from the full-precision keys
+        (``ops.knn_recompute_sims``; "ip" divides by |key| as the reference does for the cosine index this search stands for) before
+        the interpolation and the sweep, and come back as ``knn_sims``."""
+        return self.score_finish(self.score_begin(batch, lmbda, temperature, knn_index, k, sweep, knn_keys, knn_sim_func))
+
+    def score_begin(self, batch: BlockBatch, lmbda: float = 0.0, temperature: float = 1.0, knn_index=None, k: int = 0, sweep=None,
+                    knn_keys=None, knn_sim_func: str = "do_not_recomp_ip"):
         """Enqueue the step up to the search's host read (features, search, softmax) and return a handle for ``score_finish``:
         several batches can be in flight (one per stream), the host looks at a search's survivor counts only when it comes back
         to that batch."""
+        if knn_sim_func not in ("do_not_recomp_ip", "ip", "l2"):
+            raise ValueError("knn_sim_func: do_not_recomp_ip, ip or l2 (the in-step search is an inner-product one)")
+        if knn_sim_func != "do_not_recomp_ip" and knn_keys is None:
+            raise ValueError(f"knn_sim_func={knn_sim_func!r} needs knn_keys (the key table in HBM)")
         x = self.features(batch)
-        pending = None
+        pending = qn = None
         if (lmbda > 0.0 or sweep) and knn_index is not None:
             qn = x / (x ** 2).sum(-1, keepdim=True).sqrt()
             pending = knn_index.search_begin(qn.contiguous(), k, return_vals=True)
         lm_logp = self.asm.target_log_prob(x, batch.targets)
-        return batch, lmbda, temperature, x, lm_logp, pending, sweep
+        resim = (qn, knn_keys, knn_sim_func) if pending is not None and knn_sim_func != "do_not_recomp_ip" else None
+        return batch, lmbda, temperature, x, lm_logp, pending, sweep, resim
 
     def score_finish(self, handle):
-        batch, lmbda, temperature, x, lm_logp, pending, sweep = handle
+        batch, lmbda, temperature, x, lm_logp, pending, sweep, resim = handle
         out = {"gcn_feat": x, "lm_logp": lm_logp, "logp": lm_logp}
         if pending is not None:
             sims, ids, vals = pending.result()
+            if resim is not None:                                # knn_model.py:161-175 on the step's own normalised queries
+                qn, keys, fn = resim
+                sims = ops.knn_recompute_sims(qn.contiguous(), ids.contiguous(), keys, fn, normalize_keys=(fn == "ip"))
             if lmbda > 0.0:
                 logp, p_knn, recall = ops.knn_interp(lm_logp, sims, ids, batch.targets, temperature, lmbda,
                                                      n_store=self.store.n_store, knn_vals=vals)

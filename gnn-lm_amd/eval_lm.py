@@ -484,6 +484,10 @@ def main(args, tables=None, model=None):
                               no_load_keys=("do_not_recomp" in args.knn_sim_func), use_memory=True,
                               metric_type=args.knn_sim_func, device=device) if not getattr(args, "knn_model", None) \
             else args.knn_model
+        if args.knn_sim_func in ("ip", "l2") and hasattr(knn_dstore, "keys_home"):
+            # the key table goes to HBM here, once, before the lanes fork; the batches then stay two-phase (search_begin ... result(),
+            # the recompute enqueued behind it) exactly as with the default sim func
+            logger.info(knn_dstore.keys_home())
     # --save-knnlm-dstore (fairseq_cli/eval_lm.py:103-104,178-205,222-242): the keys the scorer hands back per hypothesis
     # (`--knn-keytype`, here the HGT output "gcn_feat") and the target tokens, written as the split's datastore
     save = None

@@ -180,6 +180,8 @@ class KNNModel(object):
         if isinstance(self.keys, torch.Tensor):
             return self.keys
         need = self.dstore_size * self.hidden_size * (2 if self.dstore_fp16 else 4)
+        if getattr(self.data_store, "_device_keys", None) is not None and need <= self.max_hbm_key_bytes:
+            return self.data_store.keys_to_device(self.device)     # uploaded before: the free-memory test below is for the upload
         free = torch.cuda.mem_get_info(self.device)[0]
         if need > min(0.9 * free, self.max_hbm_key_bytes):
             return None                               # the key table stays where the reference keeps it: _sims gathers rows from the host
@@ -214,36 +216,55 @@ class KNNModel(object):
             return -1 * dists
         if fn == "do_not_recomp_ip":
             return dists
-        # the recomputed similarities gather key rows: from HBM (the exact index's table, or the store's keys uploaded
-        # once -- the reference's per-query np.memmap gather on the host, :163,170, is what this replaces); numpy's
-        # negative-index wrap of the -1 padding is kept (row N - 1)
+        # the recomputed similarities read the key rows where they are: one kernel (ops.knn_recompute_sims) gathers them from
+        # HBM (the exact index's table, or the store's keys uploaded once -- the reference's per-query np.memmap gather on the
+        # host, :163,170, is what this replaces); numpy's negative-index wrap of the -1 padding is kept (row N - 1).  No
+        # [n, k, d] tensor exists on either path.
         if fn not in ("l2", "ip"):
             raise ValueError("Invalid knn similarity function!")
         keys_dev = self._keys_device()
-
-        def sims_of(vecs, q):
-            if fn == "l2":
-                return -1 * torch.sum((q[:, None, :] - vecs) ** 2, dim=2)
-            if self.cosine:
-                vecs = vecs / (vecs ** 2).sum(-1, keepdims=True).sqrt()
-            return (vecs * q[:, None, :]).sum(dim=-1)
-
+        normalize = fn == "ip" and self.cosine                                          # :172-173; l2 never normalises keys
         if keys_dev is not None:
-            idx = torch.where(knns < 0, knns + keys_dev.shape[0], knns)
-            return sims_of(keys_dev[idx].float(), queries)
+            return ops.knn_recompute_sims(queries.contiguous(), knns.contiguous(), keys_dev, fn, normalize)
         # A key table larger than the free HBM (WikiText-103 train: 211 GB of fp16 keys next to everything else): the k rows of
         # every query are gathered from the host table exactly as the reference does (`self.keys[knns]` on the np.memmap,
-        # :163,170) -- in blocks of queries, through pinned memory -- and the arithmetic runs on the device.  Slow by
-        # construction (n k random 2-KB host reads: the recipes use do_not_recomp_ip for that reason); same numbers.
+        # :163,170) -- in blocks of queries, into pinned memory -- and each staged block goes to the same kernel in direct mode,
+        # in the stored dtype.  Slow by construction (n k random 2-KB host reads: the recipes use do_not_recomp_ip for that
+        # reason); same numbers as the in-HBM path, bit for bit.
         n, k = knns.shape
         host_idx = torch.where(knns < 0, knns + self.dstore_size, knns).cpu().numpy()
-        rows_per_block = max(1, self.host_gather_bytes // max(1, k * self.hidden_size * 4))
+        rows_per_block = self._host_gather_rows(k)
+        queries = queries.contiguous()
         out = torch.empty(n, k, device=queries.device, dtype=torch.float32)
+        if n == 0:
+            return out
+        fp16 = self.keys.dtype == np.float16
+        stage = torch.empty(min(n, rows_per_block) * k, self.hidden_size, dtype=torch.float16 if fp16 else torch.float32).pin_memory()
+        stage_np = stage.numpy()
         for r0 in range(0, n, rows_per_block):
             blk = host_idx[r0:r0 + rows_per_block]
-            vecs = torch.from_numpy(np.ascontiguousarray(self.keys[blk.reshape(-1)])).to(queries.device).float()
-            out[r0:r0 + blk.shape[0]] = sims_of(vecs.reshape(blk.shape[0], k, self.hidden_size), queries[r0:r0 + blk.shape[0]])
+            m = blk.shape[0] * k
+            if self.keys.dtype == stage_np.dtype:
+                np.take(self.keys, blk.reshape(-1), axis=0, out=stage_np[:m])
+            else:
+                stage_np[:m] = self.keys[blk.reshape(-1)]
+            vecs = stage[:m].to(queries.device, non_blocking=True)
+            ops.knn_recompute_sims(queries[r0:r0 + blk.shape[0]], None, vecs, fn, normalize, out=out[r0:r0 + blk.shape[0]])
+            torch.cuda.current_stream(queries.device).synchronize()                     # the staging buffer is reused
         return out
+
+    def _host_gather_rows(self, k):
+        return max(1, self.host_gather_bytes // max(1, k * self.hidden_size * 4))
+
+    def keys_home(self):
+        """Where `ip` / `l2` read the key rows from, as one line for the log; uploads the table when it goes to HBM."""
+        keys_dev = self._keys_device()
+        if keys_dev is not None:
+            return "kNN sim func %s: similarities recomputed from the keys in HBM (%d x %d %s, %.2f GB on %s)" % (
+                self.metric_type, keys_dev.shape[0], keys_dev.shape[1], str(keys_dev.dtype).replace("torch.", ""),
+                keys_dev.numel() * keys_dev.element_size() / 1e9, keys_dev.device)
+        return "kNN sim func %s: the key table stays on the host; rows gathered through pinned memory in blocks of %d queries " \
+               "(%d rows per block at k = %d)" % (self.metric_type, self._host_gather_rows(self.k), self._host_gather_rows(self.k) * self.k, self.k)
 
     def search_sims(self, queries, k=0, with_vals=False):
         """queries [n, d] (device) -> (sims [n,k] f32, knns [n,k] i64[, knn_vals [n,k] i32 or None]), before the -1 masking."""
@@ -286,7 +307,9 @@ class KNNModel(object):
         q = queries.float()
         if self.cosine:                                                                 # :181-184
             q = q / (q ** 2).sum(-1, keepdims=True).sqrt()
-        if getattr(self.index, "has_vals", False) and hasattr(self.index, "search_begin") and self.metric_type.startswith("do_not_recomp"):
+        # `ip` / `l2` stay two-phase as long as the keys are in HBM: search_finish enqueues the recompute behind result()
+        if getattr(self.index, "has_vals", False) and hasattr(self.index, "search_begin") and \
+                (self.metric_type.startswith("do_not_recomp") or self._keys_device() is not None):
             return ("pending", q, self.index.search_begin(q.contiguous(), k, return_vals=True))
         dists, knns, kvals = self._search(q, k)
         return ("done", q, (dists, knns, kvals))

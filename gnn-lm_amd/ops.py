@@ -401,6 +401,58 @@ def knn_interp_grid(lm_logp, sims, ids, targets, ks, temperatures, lmbdas, vals=
     return out, pk, rec
 
 
+def knn_recompute_sims(queries, ids, keys, metric, normalize_keys=False, out=None):
+    """Similarities recomputed from the stored keys (``gnnlm_knn_recompute_sims``; knn_model.py:161-175) -> ``out`` [n, k] f32.
+
+    ``queries`` [n, d] f32 (already normalised for a cosine index); ``keys`` [n_rows, d] fp16 / f32; ``ids`` [n, k] int64, or
+    None for direct mode, where neighbour (i, j) is row ``i * k + j`` of ``keys`` (``keys`` is then [n * k, d] or [n, k, d]).
+    ``metric``: "ip" / 0 = key . q, "l2" / 1 = -|q - key|^2; ``normalize_keys`` divides an ip result by |key|.  Row strides
+    wider than the rows are taken as they are (no copy).  An id < 0 reads row id + n_rows, an id out of range gives -FLT_MAX.
+    A result depends on its query row and its key row only."""
+    _dev(queries, ids, out)
+    if not keys.is_cuda:
+        raise _lib.GnnlmError("gnnlm_amd kernels need contiguous device (HIP) tensors; there is no CPU fallback")
+    _f32(queries, out)
+    _dtype(ids, torch.int64, "ids")
+    if keys.dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"keys: expected float16 / float32, got {keys.dtype}")
+    metric = {"ip": 0, "l2": 1}.get(metric, metric)
+    if queries.dim() != 2:
+        raise ValueError("knn_recompute_sims: queries [n, d]")
+    n, d = queries.shape
+    if ids is None:
+        if keys.dim() == 3:
+            if keys.shape[0] != n or not keys.is_contiguous():
+                raise ValueError("knn_recompute_sims: direct mode takes keys [n, k, d] contiguous or [n * k, d]")
+            k = keys.shape[1]
+            keys = keys.view(n * k, keys.shape[2])
+        else:
+            k = keys.shape[0] // n if n else 1
+            if keys.dim() != 2 or k < 1 or keys.shape[0] != n * k:
+                raise ValueError("knn_recompute_sims: direct mode takes keys [n, k, d] contiguous or [n * k, d]")
+    else:
+        if ids.dim() != 2 or ids.shape[0] != n:
+            raise ValueError("knn_recompute_sims: ids [n, k]")
+        k = ids.shape[1]
+    if keys.dim() != 2 or keys.shape[1] != d or (keys.shape[0] > 1 and keys.stride(1) != 1):
+        raise ValueError("knn_recompute_sims: keys [n_rows, d] with unit element stride")
+    if out is None:
+        out = torch.empty(n, k, device=queries.device, dtype=torch.float32)
+    elif out.shape != (n, k):
+        raise ValueError("knn_recompute_sims: out [n, k]")
+    r = _lib.gnnlm_knn_resim_t()
+    r.queries, r.ldq = queries.data_ptr(), max(queries.stride(0), d)
+    if ids is not None:
+        r.ids, r.ld_ids = ids.data_ptr(), max(ids.stride(0), k)
+    r.keys, r.keys_itemsize = keys.data_ptr(), keys.element_size()
+    r.ld_keys, r.n_rows = max(keys.stride(0), d), keys.shape[0]
+    r.d, r.n, r.k = d, n, k
+    r.metric, r.normalize_keys = metric, int(bool(normalize_keys))
+    r.out, r.ld_out = out.data_ptr(), max(out.stride(0), k)
+    call_desc("gnnlm_knn_recompute_sims", r)
+    return out
+
+
 def topk_merge(scores, best_val, best_id, col0=0, col_ids=None, col_scale=None, col_bias=None, alpha=1.0, largest=True,
                init=False, row_ncols=None, ids=None):
     """Fold the score chunk ``scores`` [n, ncols] into the running top-k state (``best_val`` f32 / ``best_id`` i64

@@ -288,6 +288,26 @@ typedef struct gnnlm_knn_interp_grid {
     int64_t* out_recall;       /* optional [n_ks, n] */
 } gnnlm_knn_interp_grid_t;
 int gnnlm_knn_interp_grid(const gnnlm_knn_interp_grid_t* desc, void* stream);
+/* Exact similarities: the similarity of every retrieved neighbour recomputed from its stored key in one kernel.
+ * Replaces: the `ip` / `l2` branches of KNNModel.get_knn_prob's sim_func dispatch (knn/knn_model.py:161-175:
+ * `self.keys[knns]` gathered on the host, then `-sum((q - key)^2)` or `sum(key * q)`, the keys divided by their norm when the
+ * index file name says "cosine").  out[i, j] is a function of query row i and of the key row of neighbour (i, j) ONLY: one
+ * fixed summation order per row, whatever n, k, the column, the strides, the mode.  fp16 / f32 values are widened exactly, the
+ * sums (and the division by the key norm) run in float64 and a result is rounded to float32 once: within half a float32 ulp
+ * of the exact value, where the reference's own float32 sums carry an error that grows with d and with what cancels.
+ * An id < 0 reads row id + n_rows (numpy's wrap: -1 is the last row, as for the reference); an id outside [-n_rows, n_rows)
+ * touches no memory and yields -FLT_MAX.  No scratch, no allocation, only enqueues on `stream` (graph-capturable). */
+typedef struct gnnlm_knn_resim {
+    const float* queries;  int64_t ldq;     /* [n, d], row stride in elements; already normalised for a cosine index (:181-184) */
+    const int64_t* ids;  int64_t ld_ids;    /* [n, k]; NULL = direct mode: neighbour (i, j) is row i * k + j of keys (staged rows) */
+    const void* keys;  int32_t keys_itemsize;   /* [n_rows, d] fp16 (2) or f32 (4) */
+    int64_t ld_keys, n_rows;                /* row stride in elements; byte offsets are 64-bit */
+    int32_t d;  int64_t n;  int32_t k;      /* d >= 1, n >= 0, k >= 1 */
+    int32_t metric;                         /* 0: sum_e key[e] * q[e];  1: -sum_e (q[e] - key[e])^2   (:166-167) */
+    int32_t normalize_keys;                 /* metric 0 only: divide by sqrt(sum_e key[e]^2) of the same row, same pass (:172-173) */
+    float* out;  int64_t ld_out;            /* [n, k] */
+} gnnlm_knn_resim_t;
+int gnnlm_knn_recompute_sims(const gnnlm_knn_resim_t* desc, void* stream);
 /* tag[r] = (uint32(vals[r]) * 2654435761) >> 24 for the n rows of a label table (int16 / int32) */
 int gnnlm_label_tags(const void* vals, int32_t vals_itemsize, int64_t n, uint8_t* tag, void* stream);
 
