@@ -92,6 +92,8 @@ def lib():
         L.gnnlm_target_arch.restype = ctypes.c_char_p
         L.gnnlm_adaptive_workspace_bytes.restype = ctypes.c_size_t
         L.gnnlm_hgt_workspace_bytes.restype = ctypes.c_size_t
+        L.gnnlm_hgt_workspace_bytes_ragged.restype = ctypes.c_size_t
+        L.gnnlm_ragged_tiles.restype = ctypes.c_int64
         L.gnnlm_sizeof.restype = ctypes.c_size_t
         L.gnnlm_sizeof.argtypes = [ctypes.c_char_p]
         L.gnnlm_kernel_name.restype = ctypes.c_char_p
@@ -128,6 +130,10 @@ def lib():
         L.gnnlm_ivfpq_split_payload.argtypes = [vp, i64, i32, i32, vp, vp]
         L.gnnlm_hgt_workspace_bytes.argtypes = [vp, vp]
         L.gnnlm_hgt_forward.argtypes = [vp, vp, vp, ctypes.c_size_t, vp]
+        L.gnnlm_hgt_workspace_bytes_ragged.argtypes = [vp, vp, vp]
+        L.gnnlm_hgt_forward_ragged.argtypes = [vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.gnnlm_ragged_tiles.argtypes = [vp, i32, vp]
+        L.gnnlm_causal_attn_varlen.argtypes = [vp, vp, vp, i64, vp, i64, vp, i32, i32, i32, vp]
         for nm in ("gnnlm_gemm_nt", "gnnlm_pq_gather_decode", "gnnlm_star_attn", "gnnlm_chain_attn",
                    "gnnlm_knn_interp", "gnnlm_knn_interp_grid", "gnnlm_knn_recompute_sims", "gnnlm_topk_merge", "gnnlm_ivfpq_scan", "gnnlm_gather_rows_peer",
                    "gnnlm_ivfpq_scan8", "gnnlm_ivfpq_rescore", "gnnlm_ivfpq_tau", "gnnlm_group_assign",

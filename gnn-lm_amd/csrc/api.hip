@@ -141,17 +141,26 @@ bool row_keyed_kv(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io) {
     return w0.wq_n0 && w0.bq_n0 && w0.wk_n0 && w0.bk_n0 && w0.wv_n0 && w0.bv_n0 && m.n_layers - 2 < std::max(m.left, m.right);
 }
 
-void carve_hgt(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, Carver& c, HgtBufs& b) {
+void carve_hgt(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, Carver& c, HgtBufs& b, bool ragged = false) {
     const int64_t Tt = (int64_t)io.n_blocks * io.T, d = m.d, H = m.n_heads;
     const int64_t dpq = (int64_t)m.M * m.dsub, dmax = std::max<int64_t>(dpq, d);
     b.Tp = (io.T + 3) & ~3;
     b.slot_row = b.urows = nullptr; b.slot_u = b.row_cnt = b.win_counts_u = nullptr; b.uvalid = nullptr; b.xu = nullptr;
     b.ht[0] = c.take<float>(Tt * d);
     b.ht[1] = c.take<float>(Tt * d);
-    b.q = c.take<float>(Tt * d);
-    b.k = c.take<float>(Tt * d);
-    b.vt = c.take<float>((int64_t)io.n_blocks * d * b.Tp);
-    b.scores = c.take<float>((int64_t)io.n_blocks * H * io.T * b.Tp);
+    if (ragged) {
+        // packed blocks of unequal length: q | k' | v' row-major back to back (one 3d-wide GEMM writes them whatever the token
+        // count), no V^T and no [n_blocks, H, T, T] score buffer -- the varlen kernel keeps one tile of scores in registers
+        b.q = c.take<float>(3 * Tt * d);
+        b.k = b.q + Tt * d;
+        b.vt = b.k + Tt * d;
+        b.scores = nullptr;
+    } else {
+        b.q = c.take<float>(Tt * d);
+        b.k = c.take<float>(Tt * d);
+        b.vt = c.take<float>((int64_t)io.n_blocks * d * b.Tp);
+        b.scores = c.take<float>((int64_t)io.n_blocks * H * io.T * b.Tp);
+    }
     b.mc = c.take<float>(Tt * d);
     b.U = c.take<float>(Tt * H * dmax);
     b.Z = c.take<float>(Tt * H * dmax);
@@ -256,7 +265,7 @@ int linear_rows_windows(const GroupWindows& w, const float* A, int64_t lda, cons
     return OK;
 }
 
-int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, size_t ws_bytes, hipStream_t s) {
+int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, size_t ws_bytes, hipStream_t s, const gnnlm_ragged_t* rg = nullptr) {
     GNNLM_REQUIRE(m.layers && m.n_layers >= 1, "hgt: no layers");
     GNNLM_REQUIRE(m.gemm_precision >= 0 && m.gemm_precision <= 2, "hgt: gemm_precision must be 0, 1 or 2");
     GemmPrecisionScope prec_scope(m.gemm_precision);
@@ -301,9 +310,16 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
     GNNLM_REQUIRE(dk % 4 == 0 && d % 4 == 0 && dpq % 4 == 0, "hgt: d_k and the PQ dimension must be multiples of 4");
     GNNLM_REQUIRE(dense0 || m.opq_at || dpq == d, "hgt: without OPQ the PQ dimension must equal d");
 
+    // a ragged batch (gnnlm_hgt_forward_ragged): the packed tokens are one run of io.T rows, cut into blocks by rg
+    GNNLM_REQUIRE(!rg || (nb == 1 && rg->n_tok == Tt && rg->n_blocks >= 1 && rg->block_off && rg->tiles),
+                  "hgt: a ragged batch needs io.n_blocks == 1, io.T == blocks.n_tok and the block / tile tables");
+    GNNLM_REQUIRE(!rg || causal_attn_varlen_ok(dk), "hgt: ragged batches need d / n_heads in {16, 32, 64, 128}");
+    // the causal branch in one kernel that adds itself into the message sum: the recipe shape's, or the varlen one
+    const bool fusedc = rg != nullptr || causal_attn_fused_ok(T, dk);
+
     Carver c(ws, ws_bytes);
     HgtBufs b;
-    carve_hgt(m, io, c, b);
+    carve_hgt(m, io, c, b, rg != nullptr);
     GNNLM_REQUIRE(ws && c.fits(), "hgt: workspace too small (see gnnlm_hgt_workspace_bytes)");
     const int64_t Tp = b.Tp;
 
@@ -367,7 +383,7 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
         }
     }
     // V^T buffer of the GEMM path: its padding columns (t >= T) are read by the P.V GEMM against zero probabilities
-    if (!causal_attn_fused_ok(T, dk)) GNNLM_HIP(hipMemsetAsync(b.vt, 0, sizeof(float) * (size_t)nb * d * Tp, s));
+    if (!fusedc) GNNLM_HIP(hipMemsetAsync(b.vt, 0, sizeof(float) * (size_t)nb * d * Tp, s));
 
     const float* ht_in = io.tgt_feats;
     for (int l = 0; l < m.n_layers; ++l) {
@@ -382,7 +398,7 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
         // q, k', v' of the batch: [Tt, ldq] with the three at column offsets 0 / d / 2d when they come out of one GEMM
         const float *qp = b.q, *kp = b.k, *vp = b.vt;
         int64_t ldq = d;
-        const bool qkv_one = causal_attn_fused_ok(T, dk) && w.bq_t && w.wk_t == w.wq_t + (int64_t)d * d &&
+        const bool qkv_one = fusedc && w.bq_t && w.wk_t == w.wq_t + (int64_t)d * d &&
                              w.wv_t == w.wk_t + (int64_t)d * d && w.bk_t == w.bq_t + d && w.bv_t == w.bk_t + d &&
                              b.k == b.q + Tt * d && b.vt == b.k + Tt * d;
         if (qkv_one) {
@@ -395,7 +411,7 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
             TRY(linear(ht_in, d, w.wk_t, w.bk_t, b.k, Tt, d, d, nullptr, 1.f, s));
         }
         if (qkv_one) {
-        } else if (causal_attn_fused_ok(T, dk)) {
+        } else if (fusedc) {
             // recipe shape: V' row-major, then scores + masked softmax + P.V in one kernel (attn.hip)
             // (the kernel itself runs after the star branch and adds its result into the message sum, see below)
             TRY(linear(ht_in, d, w.wv_t, w.bv_t, b.vt, Tt, d, d, nullptr, 1.f, s));
@@ -471,14 +487,15 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
             GemmParams g{};
             g.A = b.Z; g.lda = (int64_t)H * din; g.W = w.wvz_t; g.ldw = din; g.C = b.ms; g.ldc = d;
             g.bias = w.bvz; g.bias_mode = 1; g.gate = b.has_nb;
-            const bool fused = causal_attn_fused_ok(T, dk);
+            const bool fused = fusedc;
             if (!fused) { g.R = b.mc; g.ldr = d; }
             g.M = (int)Tt; g.N = dk; g.K = din; g.batch1 = H;
             g.sA1 = din; g.sW1 = (int64_t)dk * din; g.sC1 = dk; g.sB1 = dk; g.sR1 = dk;
             TRY(gemm_nt(g, s));
             // recipe shape: the causal branch adds itself into the sum with coalesced row accesses -- cheaper than
             // the residual loads of the GEMM epilogue (same value: star + causal, fp32 addition commutes)
-            if (fused) TRY(causal_attn_fused(qp, kp, vp, ldq, b.ms, d, nb, T, H, dk, m.max_intra_context, s, true));
+            if (rg) TRY(causal_attn_varlen(qp, kp, vp, ldq, b.ms, d, *rg, H, dk, m.max_intra_context, s, true));
+            else if (fused) TRY(causal_attn_fused(qp, kp, vp, ldq, b.ms, d, nb, T, H, dk, m.max_intra_context, s, true));
         }
         // a_linear on the cross-type mean (0.5 folded into alpha) + residual, then LayerNorm (hgt.py:397-405)
         TRY(linear(b.ms, d, w.wa_t, w.ba_t, b.aout, Tt, d, d, nullptr, 0.5f, s));
@@ -673,7 +690,7 @@ size_t gnnlm_sizeof(const char* name) {
 #define GNNLM_SZ(t) if (!strcmp(name, #t)) return sizeof(t);
     GNNLM_SZ(gnnlm_group_assign_t) GNNLM_SZ(gnnlm_gemm_t) GNNLM_SZ(gnnlm_gather_t) GNNLM_SZ(gnnlm_star_attn_t) GNNLM_SZ(gnnlm_chain_attn_t)
     GNNLM_SZ(gnnlm_adaptive_softmax_t) GNNLM_SZ(gnnlm_knn_interp_t) GNNLM_SZ(gnnlm_knn_interp_grid_t) GNNLM_SZ(gnnlm_knn_resim_t) GNNLM_SZ(gnnlm_hgt_layer_t)
-    GNNLM_SZ(gnnlm_hgt_t) GNNLM_SZ(gnnlm_hgt_io_t) GNNLM_SZ(gnnlm_profile_entry_t) GNNLM_SZ(gnnlm_topk_t) GNNLM_SZ(gnnlm_ivfpq_scan_t) GNNLM_SZ(gnnlm_ivfpq_scan8_t) GNNLM_SZ(gnnlm_ivfpq_rescore_t) GNNLM_SZ(gnnlm_ivfpq_tau_t) GNNLM_SZ(gnnlm_ivfpq_tables_t) GNNLM_SZ(gnnlm_peer_gather_t) GNNLM_SZ(gnnlm_shards_t)
+    GNNLM_SZ(gnnlm_hgt_t) GNNLM_SZ(gnnlm_hgt_io_t) GNNLM_SZ(gnnlm_profile_entry_t) GNNLM_SZ(gnnlm_topk_t) GNNLM_SZ(gnnlm_ivfpq_scan_t) GNNLM_SZ(gnnlm_ivfpq_scan8_t) GNNLM_SZ(gnnlm_ivfpq_rescore_t) GNNLM_SZ(gnnlm_ivfpq_tau_t) GNNLM_SZ(gnnlm_ivfpq_tables_t) GNNLM_SZ(gnnlm_peer_gather_t) GNNLM_SZ(gnnlm_shards_t) GNNLM_SZ(gnnlm_ragged_t)
 #undef GNNLM_SZ
     return 0;
 }
@@ -717,6 +734,12 @@ int gnnlm_causal_softmax(float* S, int64_t n_mats, int32_t T, int64_t ld, int32_
 int gnnlm_causal_attn(const float* Q, const float* K, const float* V, int64_t ld, float* out, int64_t ldo,
                       int32_t n_blocks, int32_t T, int32_t H, int32_t dk, int32_t max_ctx, void* stream) {
     return causal_attn_fused(Q, K, V, ld, out, ldo, n_blocks, T, H, dk, max_ctx, (hipStream_t)stream);
+}
+int64_t gnnlm_ragged_tiles(const int32_t* block_off, int32_t n_blocks, int32_t* tiles) { return ragged_tiles(block_off, n_blocks, tiles); }
+int gnnlm_causal_attn_varlen(const float* Q, const float* K, const float* V, int64_t ld, float* out, int64_t ldo,
+                             const gnnlm_ragged_t* blocks, int32_t H, int32_t dk, int32_t max_ctx, void* stream) {
+    GNNLM_DESC(blocks);
+    return causal_attn_varlen(Q, K, V, ld, out, ldo, *blocks, H, dk, max_ctx, (hipStream_t)stream);
 }
 int gnnlm_layernorm(const float* x, int64_t ldx, const float* gamma, const float* beta, float* out, int64_t ldo,
                     int64_t rows, int32_t d, float eps, const uint8_t* valid, void* stream) {
@@ -793,6 +816,20 @@ int gnnlm_hgt_forward(const gnnlm_hgt_t* m, const gnnlm_hgt_io_t* io, void* work
     GNNLM_DESC(m);
     GNNLM_DESC(io);
     return hgt_forward_impl(*m, *io, workspace, workspace_bytes, (hipStream_t)stream);
+}
+size_t gnnlm_hgt_workspace_bytes_ragged(const gnnlm_hgt_t* m, const gnnlm_hgt_io_t* io, const gnnlm_ragged_t* blocks) {
+    if (!m || !io || !blocks) return 0;
+    Carver c(nullptr, 0);
+    HgtBufs b;
+    carve_hgt(*m, *io, c, b, true);
+    return c.off + 256;
+}
+int gnnlm_hgt_forward_ragged(const gnnlm_hgt_t* m, const gnnlm_hgt_io_t* io, const gnnlm_ragged_t* blocks, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    GNNLM_DESC(m);
+    GNNLM_DESC(io);
+    GNNLM_DESC(blocks);
+    return hgt_forward_impl(*m, *io, workspace, workspace_bytes, (hipStream_t)stream, blocks);
 }
 
 static const char* kKernelNames[K_COUNT] = {"gemm_nt_f32_kernel", "gather_decode_kernel", "star_attn_kernel",

@@ -109,6 +109,13 @@ bool causal_attn_fused_ok(int T, int dk);
 int causal_attn_fused(const float* Q, const float* K, const float* V, int64_t ld, float* out, int64_t ldo,
                       int n_blocks, int T, int H, int dk, int max_ctx, hipStream_t stream, bool accumulate = false);
 
+// the same attention over packed blocks of unequal length (causal_varlen.hip): one launch for any lengths, d_k in {16, 32, 64, 128}
+bool causal_attn_varlen_ok(int dk);
+int causal_attn_varlen(const float* Q, const float* K, const float* V, int64_t ld, float* out, int64_t ldo, const gnnlm_ragged_t& rg,
+                       int H, int dk, int max_ctx, hipStream_t stream, bool accumulate = false);
+// host: the (block, query tile) table of block_off [n_blocks + 1], heaviest tiles first; tiles == nullptr only counts.  -1: an empty block
+int64_t ragged_tiles(const int32_t* block_off, int n_blocks, int32_t* tiles);
+
 // out[r,:] = LayerNorm(x[r,:]) * gamma + beta ; optional row validity (invalid rows -> 0)
 int layernorm(const float* x, int64_t ldx, const float* gamma, const float* beta, float* out, int64_t ldo,
               int64_t rows, int d, float eps, const uint8_t* valid, hipStream_t stream,

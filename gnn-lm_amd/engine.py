@@ -37,6 +37,8 @@ class BlockBatch:
     fetched_valid: Optional[torch.Tensor] = None
     fetched_centres_only: bool = False
     fetched_index: Optional[torch.Tensor] = None
+    # blocks of unequal length packed back to back: a ragged.RaggedBatch or offsets [n_blocks + 1]; None = n_blocks x T (T is then read)
+    block_off: Optional[object] = None
 
 
 class GnnLmEngine:
@@ -56,7 +58,8 @@ class GnnLmEngine:
         G = NeighborGraph(ids=batch.ids, n_blocks=batch.n_blocks, T=batch.T, left=self.left, right=self.right,
                           store=self.store, fetched_codes=batch.fetched_codes, fetched_valid=batch.fetched_valid,
                           fetched_centres_only=batch.fetched_centres_only, fetched_index=batch.fetched_index,
-                          max_intra_context=self.max_intra_context, fetcher=self.fetcher if batch.fetched_codes is None else None)
+                          max_intra_context=self.max_intra_context, fetcher=self.fetcher if batch.fetched_codes is None else None,
+                          block_off=batch.block_off)
         return self.hgt(G, features={"tgt": tgt})["tgt"]
 
     def score(self, batch: BlockBatch, lmbda: float = 0.0, temperature: float = 1.0, knn_index=None, k: int = 0, sweep=None,

@@ -42,6 +42,7 @@ from .knn_model import KNNModel
 from .model import GnnLmModel
 from .path_utils import dstore_path, feature_path, neighbor_path, quantized_feature_path, value_path
 from .sequence_scorer import SequenceScorer
+from . import token_blocks
 
 logger = logging.getLogger("gnnlm_amd.eval_lm")
 
@@ -59,7 +60,10 @@ def get_parser():
     p.add_argument("--gcn-k", default=1024, type=int)
     p.add_argument("--gcn-context-window", default=0, type=int)
     p.add_argument("--intra-context", default=0, type=int)
-    p.add_argument("--sample-break-mode", default="none")
+    p.add_argument("--sample-break-mode", default="none",
+                   help="none | complete | complete_doc | eos (fairseq/data/token_block_dataset.py:24-33).  The last three cut the split at "
+                        "sentence boundaries (DATA/<split>.idx holds the sentence sizes): a batch is then a run of blocks of UNEQUAL length, "
+                        "packed back to back up to the token budget the equal-length path would have used")
     p.add_argument("--tokens-per-sample", default=1024, type=int)
     p.add_argument("--max-tokens", default=None, type=int)
     p.add_argument("--max-sentences", default=None, type=int)
@@ -297,6 +301,41 @@ def block_ranges(n_tokens, block, context_window=0):
 _MMAP_IDX_DTYPES = {1: np.uint8, 2: np.int8, 3: np.int16, 4: np.int32, 5: np.int64, 6: np.float64, 7: np.float64, 8: np.uint16}
 
 
+def fairseq_sentence_sizes(data, split):
+    """The sentence sizes (int32) of ``DATA/{split}.idx`` (same header as below; the ``.bin`` is not needed), or None when the
+    file is absent or in another format."""
+    idx = os.path.join(data, split + ".idx")
+    if not os.path.exists(idx):
+        return None
+    with open(idx, "rb") as f:
+        if f.read(9) != b"MMIDIDX\x00\x00":
+            return None
+        version, code, n_sent = struct.unpack("<QBQ", f.read(17))
+        if version != 1 or code not in _MMAP_IDX_DTYPES:
+            return None
+        return np.frombuffer(f.read(4 * n_sent), dtype=np.int32)
+
+
+def sample_blocks(data, split, break_mode, block, n_tokens, context_window=0):
+    """``(context_start, start, end)`` of every sample of the split under ``--sample-break-mode`` (host only).  ``none`` is
+    :func:`block_ranges` and needs nothing but the token count; ``complete`` / ``complete_doc`` / ``eos`` cut at the sentence
+    boundaries of ``DATA/{split}.idx`` (token_blocks.py) and raise ``FileNotFoundError`` without it; anything else is the
+    reference's ``ValueError('Invalid break_mode: ...')`` (token_block_utils_fast.pyx:102)."""
+    mode = "none" if break_mode is None else break_mode
+    if mode not in token_blocks.BREAK_MODES:
+        raise ValueError("Invalid break_mode: " + str(break_mode))
+    if mode == "none":
+        return block_ranges(n_tokens, block, context_window)
+    sizes = fairseq_sentence_sizes(data, split)
+    if sizes is None:
+        raise FileNotFoundError(f"--sample-break-mode {mode} cuts the split at sentence boundaries and needs the sentence sizes of "
+                                f"{os.path.join(data, split + '.idx')} (fairseq's mmap index): not found or not in that format")
+    total = int(sizes.astype(np.int64).sum())
+    if total != n_tokens:
+        raise ValueError(f"{os.path.join(data, split + '.idx')}: its sentences hold {total} tokens, the split's datastore {n_tokens}")
+    return token_blocks.block_ranges(sizes, mode, block, context_window)
+
+
 def fairseq_token_stream(data, split):
     """The split's token stream as fairseq binarised it (``DATA/{split}.bin/.idx``, MMapIndexedDataset:
     fairseq/data/indexed_dataset.py:350-420): header ``MMIDIDX\0\0`` + <Q version 1 + <B dtype code + <Q n_sentences, then
@@ -394,6 +433,15 @@ def main(args, tables=None, model=None):
         raise ValueError("Cannot use knnlm while trying to build the datastore!")
     sweep = parse_sweep(args)
     args.sweep = sweep                                                                     # (read by the scorer)
+    break_mode = getattr(args, "sample_break_mode", None) or "none"
+    if break_mode not in token_blocks.BREAK_MODES:
+        raise ValueError("Invalid break_mode: " + str(break_mode))                         # token_block_utils_fast.pyx:102
+    ragged = break_mode != "none"                                                          # blocks of unequal length, packed
+    if ragged and getattr(args, "graph_capture", False):
+        raise ValueError(f"--graph-capture replays one graph per batch shape; the batches of --sample-break-mode {break_mode} all differ")
+    if ragged and args.save_knnlm_dstore and break_mode == "complete_doc":
+        raise ValueError("--save-knnlm-dstore writes one row per token of the split in corpus order; --sample-break-mode complete_doc "
+                         "drops the document separators")
     if args.context_window > 0:
         # LMContextWindowDataset (fairseq/data/lm_context_window_dataset.py) prepends context tokens and scores only the
         # new ones; shrinking the block without the prefix would silently give another ppl
@@ -450,7 +498,7 @@ def main(args, tables=None, model=None):
         else:
             fetcher = ShardedFetcher(store, shard, mode=args.exchange)
     T = args.tokens_per_sample - args.context_window
-    blocks = [r + (bid,) for bid, r in enumerate(block_ranges(tabs["n_tok"], T, args.gcn_context_window))]   # (context start, start, end, sample id)
+    blocks = [r + (bid,) for bid, r in enumerate(sample_blocks(args.data, args.gen_subset, break_mode, T, tabs["n_tok"], args.gcn_context_window))]   # (context start, start, end, sample id)
     if args.first > 0:
         blocks = blocks[:args.first]
     blocks = blocks[args.shard_id::args.num_shards]                                        # eval_lm.py:131-132
@@ -533,13 +581,35 @@ def main(args, tables=None, model=None):
     timers = []             # gen_timer (eval_lm.py:214-219) as HIP event pairs on the stream: no per-batch host sync
     # the batches of this rank: runs of equally long blocks, up to per_batch of them
     batches_, i = [], 0
-    while i < len(blocks):
+    while i < len(blocks) and not ragged:
         group = [blocks[i]]
         while len(group) < per_batch and i + len(group) < len(blocks) and \
                 (blocks[i + len(group)][2] - blocks[i + len(group)][0]) == (group[0][2] - group[0][0]):
             group.append(blocks[i + len(group)])
         i += len(group)
         batches_.append(group)
+    rtab = None
+    if ragged and blocks:
+        # ragged modes: consecutive blocks in corpus order up to the token budget the equal-length path would have packed (a block
+        # longer than the budget is a batch of its own).  The split's tables go to the device ONCE: block offsets and the causal
+        # kernel's tile lists of every batch (ragged.BlockTable), where each block's rows start in the split, how many of them are
+        # context, where its scored tokens start among the scored ones -- a batch is views into them, nothing per batch over PCIe
+        from .ragged import BlockTable, packed_rows
+        budget, bounds, b0, tok = per_batch * T, [], 0, 0
+        for j, blk in enumerate(blocks):
+            n = blk[2] - blk[0]
+            if j > b0 and (tok + n > budget or (args.max_sentences and j - b0 >= args.max_sentences)):
+                bounds.append((b0, j))
+                b0, tok = j, 0
+            tok += n
+        bounds.append((b0, len(blocks)))
+        batches_ = [blocks[a:b] for a, b in bounds]
+        barr = np.asarray([blk[:3] for blk in blocks], dtype=np.int64)
+        rtab = {"table": BlockTable(barr[:, 2] - barr[:, 0], device, batches=bounds), "bounds": bounds,
+                "first": torch.from_numpy(np.ascontiguousarray(barr[:, 0])).to(device),
+                "ctx": torch.from_numpy(np.ascontiguousarray(barr[:, 1] - barr[:, 0])).to(device),
+                "scored_off": torch.from_numpy(np.concatenate([[0], np.cumsum(barr[:, 2] - barr[:, 1])])).to(device)}
+    batch_tokens = lambda g_: sum(b_[2] - b_[0] for b_ in g_)
     idle_steps = 0
     if fetcher is not None and world > 1:
         # the exchange is a collective: every rank takes part in as many of them as the rank with the most batches
@@ -548,7 +618,7 @@ def main(args, tables=None, model=None):
         idle_steps = int(t.item()) - len(batches_)
         if args.exchange == "padded":
             # equal-split all-to-alls: every rank sizes its buckets from the SAME request count, the largest batch of any rank
-            t = torch.tensor([max((len(g_) * (g_[0][2] - g_[0][0]) for g_ in batches_), default=0) * args.gcn_k], dtype=torch.int64, device=t.device)
+            t = torch.tensor([max((batch_tokens(g_) for g_ in batches_), default=0) * args.gcn_k], dtype=torch.int64, device=t.device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             fetcher.fixed_requests = int(t.item())
     deep = getattr(getattr(model, "hgt_decoder", None), "n_layers", 1) > 1
@@ -592,15 +662,20 @@ def main(args, tables=None, model=None):
             save["keys"][sl] = keys[:n_new].to(torch.float16 if save["keys"].dtype == np.float16 else torch.float32).cpu().numpy()
             save["vals"][sl, 0] = toks[:n_new].cpu().numpy().astype(save["vals"].dtype)
             save["idx"] += n_new
-        pos = torch.cat([h[0]["positional_scores"].float().reshape(-1) for h in hypos])     # one launch per batch
+        scored = handle.get("scored_pos") if handle is not None else None                   # ragged batch: the scorer's flat view and sums
+        pos = scored.float().reshape(-1) if scored is not None else \
+            torch.cat([h[0]["positional_scores"].float().reshape(-1) for h in hypos])     # one launch per batch
         ops.masked_sum_f64(pos, None, acc)                                                  # score_sum (:273), in f64
         if sweep:
             ops.rows_sum_f64(handle["sweep_logp"], sweep_accs[id(acc)])                     # the same positions, every grid point
         # ... and as the reference adds it up: one float32 sum per hypothesis (`pos_scores.sum()`), accumulated in a float32 scalar
         # (`score_sum += ...cpu()`, :273) -- the per-hypothesis sums are kept on the device and chained on the host at the end
-        lens = [h[0]["positional_scores"].numel() for h in hypos]
-        hyp_sums.append(pos.view(len(hypos), -1).sum(dim=1) if len(set(lens)) == 1 and lens[0] > 0 else
-                        torch.stack([h[0]["positional_scores"].float().sum() for h in hypos]))
+        if scored is not None:
+            hyp_sums.append(handle["hyp_sums"])                                             # (one segmented sum per batch)
+        else:
+            lens = [h[0]["positional_scores"].numel() for h in hypos]
+            hyp_sums.append(pos.view(len(hypos), -1).sum(dim=1) if len(set(lens)) == 1 and lens[0] > 0 else
+                            torch.stack([h[0]["positional_scores"].float().sum() for h in hypos]))
         state["count"] += pos.numel()                                                                # :274
         if want_words or bpe_toks is not None:
             state["count"] -= word_outputs(args, hypos, sample["id"], symbols, bpe_toks, bpe_len, word_stats)     # skipped_toks (:274)
@@ -612,23 +687,37 @@ def main(args, tables=None, model=None):
             torch.cuda.set_stream(lanes[bi % n_streams])
             acc = accs[bi % n_streams]
         L = group[0][2] - group[0][0]
+        rb = None
+        if ragged:
+            rb = rtab["table"].batch(bi)
+            b0, b1 = rtab["bounds"][bi]
         if all(group[j + 1][0] == group[j][2] for j in range(len(group) - 1)):
             idx = slice(group[0][0], group[-1][2])           # back-to-back blocks (no --gcn-context-window): plain views, no gather
+        elif ragged:
+            idx = packed_rows(rb.block_off, rtab["first"][b0:b1], rb.n_tok)                 # (device arithmetic on the resident tables)
         else:
             idx = torch.cat([torch.arange(g_[0], g_[2], device=device) for g_ in group])
-        target = tabs["targets"][idx].view(len(group), L)
+        target = tabs["targets"][idx].view(len(group), L) if not ragged else tabs["targets"][idx].view(1, rb.n_tok)
         nb_ids = tabs["nbrs"][idx].contiguous()
         if invalid_ctx > 0:
             tok_pos = torch.arange(idx.start, idx.stop, device=device) if isinstance(idx, slice) else idx     # global offsets in the split
             nb_ids = ops.filter_neighbors(nb_ids, tok_pos.contiguous(), invalid_ctx)
         graph = NeighborGraph(ids=nb_ids, n_blocks=len(group), T=L, left=left, right=right,
-                              store=store, tgt_h=tabs["feats"][idx].contiguous(), max_intra_context=args.intra_context, fetcher=fetcher)
-        sample = {"id": torch.tensor([g_[3] for g_ in group]), "nsentences": len(group), "ntokens": len(group) * L,
-                  "net_input": {"src_tokens": target, "src_lengths": torch.full((len(group),), L), "graph": graph},
+                              store=store, tgt_h=tabs["feats"][idx].contiguous(), max_intra_context=args.intra_context, fetcher=fetcher,
+                              block_off=rb)
+        sample = {"id": torch.tensor([g_[3] for g_ in group]), "nsentences": len(group), "ntokens": batch_tokens(group),
+                  "net_input": {"src_tokens": target, "src_lengths": torch.full((len(group),), L) if not ragged else torch.from_numpy(rb.lengths),
+                                "graph": graph},
                   "target": target, "start_indices": [g_[1] - g_[0] for g_ in group]}
+        if ragged:
+            sample["ragged"] = rb
+            sample["scored_off"] = rtab["scored_off"][b0:b1 + 1]
+            if any(sample["start_indices"]):                 # context tokens in front of the blocks: the scored rows, from the tables
+                sample["scored_rows"] = packed_rows(sample["scored_off"], (rb.block_off[:-1] - rb.block_off[0]) + rtab["ctx"][b0:b1],
+                                                    sum(g_[2] - g_[1] for g_ in group))
         if tabs.get("no_pad") is not None:
             sample["no_pad_in_target"] = tabs["no_pad"]
-        if args.batch_blocks > 0:
+        if args.batch_blocks > 0 and not ragged:
             sample["blockwise_knn"] = True                       # kNN pairing of one-block batches (sequence_scorer.py)
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         if pipelined:
@@ -640,8 +729,9 @@ def main(args, tables=None, model=None):
             order[lane] = bi
             continue
         ev0.record()
-        if sweep:                                               # (the handle carries the grid's log-probs to consume)
-            hypos = scorer.generate_begin([model], sample, knn_dstore=knn_dstore, temperature=args.temperature)
+        if sweep or ragged:                                     # (the handle carries the grid's log-probs / the ragged batch's flat scores to consume)
+            hypos = scorer.generate_begin([model], sample, knn_dstore=knn_dstore, temperature=args.temperature) if args.knnlm \
+                else scorer.generate_begin([model], sample)
         else:
             hypos = scorer.generate([model], sample, knn_dstore=knn_dstore, temperature=args.temperature) if args.knnlm \
                 else scorer.generate([model], sample)

@@ -86,6 +86,9 @@ class NeighborGraph:
     # fetch_codes(ids, left, right, centres_only), fetch_groups(centres, left, right, counters)).  HGT.forward then fetches itself
     # -- for a multi-layer model AFTER merging equal context groups, so every distinct centre row is requested once.
     fetcher: Optional[object] = None
+    # blocks of UNEQUAL length packed back to back (--sample-break-mode eos / complete / complete_doc): a ragged.RaggedBatch, or
+    # offsets [n_blocks + 1] (host sequence / tensor; uploaded per call).  None: n_blocks blocks of T tokens.  With it, T is not read.
+    block_off: Optional[object] = None
 
     @property
     def kg(self):
@@ -484,6 +487,18 @@ class HGT(nn.Module):
         io = _lib.gnnlm_hgt_io_t()
         io.n_blocks, io.T, io.kg = G.n_blocks, G.T, G.kg
         ids = G.ids.contiguous()
+        ragged = None
+        if G.block_off is not None:
+            # a ragged batch is ONE run of packed tokens to everything per token / per slot; the block table reaches the causal branch
+            from .ragged import as_ragged
+            ragged = as_ragged(G.block_off, tgt.device)
+            if ragged.n_blocks != G.n_blocks or ragged.n_tok != ids.shape[0] or tgt.shape[0] != ids.shape[0]:
+                raise ValueError(f"NeighborGraph.block_off describes {ragged.n_blocks} blocks / {ragged.n_tok} tokens, the graph has "
+                                 f"{G.n_blocks} blocks / {ids.shape[0]} id rows / {tgt.shape[0]} feature rows")
+            if torch.cuda.is_current_stream_capturing():
+                raise ValueError("a ragged batch cannot be captured into a HIP graph (its shapes differ per batch)")
+            io.n_blocks, io.T = 1, ragged.n_tok
+            rdesc = ragged.desc()
         io.tgt_feats, io.ids = tgt.data_ptr(), ids.data_ptr()
         fetched = (G.fetched_codes, G.fetched_valid, G.fetched_index, G.fetched_centres_only)
         st, fetcher = G.store, G.fetcher
@@ -556,7 +571,8 @@ class HGT(nn.Module):
                 out_ntgt = torch.empty(S, self.hidden_dim, device=tgt.device, dtype=torch.float32)
                 out_valid = torch.empty(S, device=tgt.device, dtype=torch.uint8)
                 io.out_ntgt, io.out_valid = out_ntgt.data_ptr(), out_valid.data_ptr()
-            need = L.gnnlm_hgt_workspace_bytes(ctypes.byref(m), ctypes.byref(io))
+            need = L.gnnlm_hgt_workspace_bytes(ctypes.byref(m), ctypes.byref(io)) if ragged is None else \
+                L.gnnlm_hgt_workspace_bytes_ragged(ctypes.byref(m), ctypes.byref(io), ctypes.byref(rdesc))
             # one arena per stream: concurrent forwards on different streams must not share scratch
             key = _lib.raw_stream()
             if prep["ws"] is None:
@@ -565,8 +581,12 @@ class HGT(nn.Module):
             if ws is None or ws.numel() < need or ws.device != tgt.device:
                 prep["ws"][key] = ws = None
                 ws = prep["ws"][key] = torch.empty(need, device=tgt.device, dtype=torch.uint8)
-            _lib.check(L.gnnlm_hgt_forward(ctypes.byref(m), ctypes.byref(io), _lib.ptr(ws), ws.numel(),
-                                           _lib.stream()), "gnnlm_hgt_forward")
+            if ragged is None:
+                _lib.check(L.gnnlm_hgt_forward(ctypes.byref(m), ctypes.byref(io), _lib.ptr(ws), ws.numel(),
+                                               _lib.stream()), "gnnlm_hgt_forward")
+            else:
+                _lib.check(L.gnnlm_hgt_forward_ragged(ctypes.byref(m), ctypes.byref(io), ctypes.byref(rdesc), _lib.ptr(ws), ws.numel(),
+                                                      _lib.stream()), "gnnlm_hgt_forward_ragged")
         except Exception:
             if cache is not None:             # the new rows own slots whose states were never written: nothing cached survives
                 cache.clear()

@@ -39,6 +39,8 @@ class GnnLmModel(torch.nn.Module):
 
     def forward(self, src_tokens, src_lengths=None, graph: NeighborGraph = None, **unused):
         """-> (x [bsz, tgt_len, d], extra) like TokenGraphTransformerDecoder.forward (:943-1009)."""
+        if self.graph_capture and graph is not None and graph.block_off is not None:
+            raise ValueError("--graph-capture replays one graph per batch SHAPE: a ragged batch (blocks of unequal length) has its own")
         if self.graph_capture and graph is not None and graph.tgt_h is not None and graph.fetcher is None \
                 and graph.fetched_codes is None and not torch.cuda.is_current_stream_capturing():
             return self._forward_replayed(src_tokens, graph)
@@ -102,7 +104,10 @@ class GnnLmModel(torch.nn.Module):
         if graph is None or graph.tgt_h is None:
             raise ValueError("graph.tgt_h (precomputed tgt features) is required: the base LM is not built "
                              "(--use-precompute-feat path, transformer.py:974-976)")
-        assert graph.n_blocks == bsz and graph.T == tgt_len
+        if graph.block_off is not None:                    # a ragged batch: one run of packed tokens, cut into blocks by graph.block_off
+            assert bsz == 1 and tgt_len == graph.ids.shape[0]
+        else:
+            assert graph.n_blocks == bsz and graph.T == tgt_len
         h = graph.tgt_h
         if h.dtype != torch.float32:
             from . import ops

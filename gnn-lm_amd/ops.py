@@ -224,6 +224,31 @@ def causal_attn(Q, K, V, n_blocks, T, H, max_ctx=0):
     return out
 
 
+def causal_attn_varlen(Q, K, V, block_off, H, max_ctx=0, out=None):
+    """Causal attention over packed blocks of unequal length in one launch: Q, K', V' [n_tok, H*dk] (row stride may exceed it),
+    ``block_off`` a :class:`ragged.RaggedBatch` or offsets [n_blocks + 1] -> [n_tok, H*dk].  d_k in {16, 32, 64, 128}."""
+    from .ragged import as_ragged
+    _f32(Q), _f32(K), _f32(V), _f32(out)
+    _dev(Q, K, V, out)
+    rg = as_ragged(block_off, Q.device)
+    if rg.n_tok != Q.shape[0] or K.shape != Q.shape or V.shape != Q.shape or K.stride(0) != Q.stride(0) or V.stride(0) != Q.stride(0):
+        raise ValueError("causal_attn_varlen: Q, K, V must share shape and row stride, with block_off[-1] - block_off[0] rows")
+    d = Q.shape[1]
+    if out is None:
+        out = torch.empty(Q.shape, device=Q.device, dtype=torch.float32)
+    desc = rg.desc()
+    call("gnnlm_causal_attn_varlen", ptr_strided(Q), ptr_strided(K), ptr_strided(V), Q.stride(0), ptr_strided(out), out.stride(0),
+         ctypes.byref(desc), H, d // H, max_ctx, stream())
+    return out
+
+
+def ptr_strided(t):
+    """Device pointer of a 2-D tensor whose rows are contiguous (row stride >= width)."""
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise _lib.GnnlmError("expected a 2-D tensor with contiguous rows")
+    return ctypes.c_void_p(t.data_ptr())
+
+
 def causal_softmax_(S, T, max_ctx=0):
     """In place over S [n_mats, T, ld]."""
     n_mats, T_, ld = S.shape

@@ -107,9 +107,11 @@ class SequenceScorer(object):
                                                       lm_flat, temperature, lmbda)
             probs = mixed.view(seq_len, b2).transpose(0, 1)
             recall = rec.view(seq_len, b2).transpose(0, 1)
-        start_idxs = sample["start_indices"] if "start_indices" in sample else [0] * bsz
         kt = getattr(self.args, "knn_keytype", None)
         feat = decoder_out[1][kt] if kt in decoder_out[1] else decoder_out[1]["inner_states"][-1]
+        if sample.get("ragged") is not None:
+            return self._finish_ragged(h, probs, recall, grid, feat)
+        start_idxs = sample["start_indices"] if "start_indices" in sample else [0] * bsz
         # strip_pad / the [mask] selections of the reference (:156-191) are boolean indexings: each one synchronises the
         # stream (nonzero).  LM eval targets carry no padding (--sample-break-mode none), so ask ONCE per batch -- or not
         # at all when the driver already knows (sample["no_pad_in_target"], set by eval_lm from the whole split) -- and
@@ -155,5 +157,55 @@ class SequenceScorer(object):
                 "positional_scores": p_i,
                 "dstore_keys": keys_i,
                 "knn_recall": rec_i,
+            }])
+        return hypos
+
+    def _finish_ragged(self, h, probs, recall, grid, feat):
+        """(this build) The hypotheses of a RAGGED batch: ``sample["ragged"]`` (a ragged.RaggedBatch) cuts the batch's one row of
+        packed tokens into blocks; one hypothesis per block, ``tokens`` / ``positional_scores`` of the block's own scored length
+        (``start_indices`` tokens of context in front are not scored) -- what ``strip_pad`` leaves of the reference's padded rows
+        (:156-191).  Everything per hypothesis is a view; the per-hypothesis sums are ONE segmented sum.  Optional device tables of
+        the driver (built once per split): ``sample["scored_rows"]`` (int64, the scored rows of the batch in order; None = every
+        row) and ``sample["scored_off"]`` (int, [n_blocks + 1] offsets of the hypotheses inside them).  Also left on the handle:
+        ``scored_pos`` (the scored positions' scores, flat), ``hyp_sums`` (float32, one per hypothesis), ``sweep_logp``."""
+        from .ragged import packed_rows
+        sample = h["sample"]
+        rb = sample["ragged"]
+        no_pad = sample.get("no_pad_in_target")
+        if no_pad is None:
+            no_pad = not bool(sample["target"].eq(self.pad).any())
+        if not no_pad:
+            raise NotImplementedError("padding symbols inside the targets of a ragged batch (the blocks are packed, not padded)")
+        off = rb.offsets
+        starts = [int(v) for v in sample.get("start_indices", [0] * rb.n_blocks)]
+        p, tgt = probs[0], sample["target"][0]
+        rows, scored_off = sample.get("scored_rows"), sample.get("scored_off")
+        if rows is None and any(starts):                      # (a caller without the driver's tables: built from the host lists)
+            import numpy as np
+            lens = off[1:] - off[:-1] - np.asarray(starts)
+            scored_off = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)])).to(p.device)
+            rows = packed_rows(scored_off, torch.from_numpy(off[:-1] + np.asarray(starts)).to(p.device), int(lens.sum()))
+        if scored_off is None:
+            scored_off = rb.block_off
+        scored_off = (scored_off - scored_off[0]).to(torch.int64)
+        pos = p if rows is None else p[rows]
+        if grid is not None:
+            h["sweep_logp"] = grid[:, 0] if rows is None else grid[:, 0][:, rows]
+        # segmented sum: differences of a float64 running sum at the hypotheses' boundaries (deterministic, one pass)
+        cs = torch.cat([torch.zeros(1, dtype=torch.float64, device=p.device), pos.double().cumsum(0)])
+        sums = (cs[scored_off[1:]] - cs[scored_off[:-1]]).float()
+        score_all = sums / (scored_off[1:] - scored_off[:-1]).float()
+        h["scored_pos"], h["hyp_sums"] = pos, sums
+        hypos = []
+        for b in range(rb.n_blocks):
+            a, e = int(off[b]) + starts[b], int(off[b + 1])
+            hypos.append([{
+                "tokens": tgt[a:e],
+                "score": score_all[b],
+                "attention": None,
+                "alignment": None,
+                "positional_scores": p[a:e],
+                "dstore_keys": feat[a:e, 0, :],
+                "knn_recall": recall[0, a:e] if recall is not None else None,
             }])
         return hypos

@@ -192,6 +192,33 @@ int gnnlm_causal_softmax(float* S, int64_t n_mats, int32_t T, int64_t ld, int32_
 int gnnlm_causal_attn(const float* Q, const float* K, const float* V, int64_t ld, float* out, int64_t ldo,
                       int32_t n_blocks, int32_t T, int32_t H, int32_t dk, int32_t max_ctx, void* stream);
 
+/* Packed blocks of UNEQUAL length (`--sample-break-mode eos | complete | complete_doc`: a sample is a run of sentences,
+ * fairseq/data/token_block_utils_fast.pyx:50-103; the collater batches the ragged samples' graphs as a disjoint union,
+ * fairseq/data/monolingual_dataset.py:261).  Additive to ABI 12: no existing struct changes.
+ *   block_off (DEVICE int32 [n_blocks + 1], ascending): block b holds the rows block_off[b] - block_off[0] ..
+ *       block_off[b + 1] - block_off[0] of the call's operands.  Only differences are read, so a caller keeps ONE table for a
+ *       whole split on the device and hands every batch a pointer into it (nothing per batch over PCIe).
+ *   tiles (DEVICE int32 [n_tiles][2]): the (block, tile of 32 queries) work items of the causal attention, heaviest first --
+ *       what gnnlm_ragged_tiles writes (host arrays: the lengths are host-known); n_tok = block_off[n_blocks] - block_off[0].
+ * A table entry that does not describe rows of [0, n_tok) is skipped by the kernel, never followed. */
+typedef struct gnnlm_ragged {
+    const int32_t* block_off;
+    const int32_t* tiles;
+    int32_t n_blocks, n_tiles;
+    int64_t n_tok;
+} gnnlm_ragged_t;
+/* HOST arrays.  Writes the tile table of block_off [n_blocks + 1] into tiles [n_tiles][2] (NULL: only counts) and returns
+ * n_tiles = sum_b ceil(len_b / 32); -1 if a block is empty.  Order: descending query tile (a tile's work is the number of key
+ * tiles below its diagonal), blocks in order among equals -- one 3000-token block beside a thousand sentences starts first. */
+int64_t gnnlm_ragged_tiles(const int32_t* block_off, int32_t n_blocks, int32_t* tiles);
+/* gnnlm_causal_attn for packed blocks of any length >= 1 in ONE launch: Q, K', V' are [n_tok, ld] f32 with head h at columns
+ * [h*dk, (h+1)*dk), out[w, h*dk + :] = sum_{u in block(w), u <= w, (max_ctx == 0 or w-u < max_ctx)} softmax_u(Q_w . K'_u) V'_u.
+ * f32 MFMA, running maximum / sum over tiles of 32 keys: no score matrix in memory.  d_k in {16, 32, 64, 128}, else -EINVAL.
+ * Replaces fn.v_dot_u + edge_softmax + u_mul_e/sum on ('tgt','intra','tgt') (hgt.py:354-356,383-385) over the batched graph
+ * of ragged samples (monolingual_dataset.py:261). */
+int gnnlm_causal_attn_varlen(const float* Q, const float* K, const float* V, int64_t ld, float* out, int64_t ldo,
+                             const gnnlm_ragged_t* blocks, int32_t H, int32_t dk, int32_t max_ctx, void* stream);
+
 /* LayerNorm epilogue of HGTLayer (fairseq/models/hgt.py:404-405).  valid (optional): rows with 0 -> zeros */
 int gnnlm_layernorm(const float* x, int64_t ldx, const float* gamma, const float* beta, float* out,
                     int64_t ldo, int64_t rows, int32_t d, float eps, const uint8_t* valid, void* stream);
@@ -608,6 +635,15 @@ int gnnlm_gelu(float* x, int64_t n, void* stream);
 size_t gnnlm_hgt_workspace_bytes(const gnnlm_hgt_t* model, const gnnlm_hgt_io_t* io);
 int gnnlm_hgt_forward(const gnnlm_hgt_t* model, const gnnlm_hgt_io_t* io, void* workspace,
                       size_t workspace_bytes, void* stream);
+/* The same forward for a RAGGED batch (gnnlm_ragged_t above): `io` describes the packed tokens as ONE run -- io->n_blocks = 1,
+ * io->T = blocks->n_tok, every per-token / per-slot array of io sized by that count -- and `blocks` cuts it into the blocks the
+ * causal ('tgt','intra','tgt') attention stays inside.  Everything else of the step is per token or per slot and runs as in
+ * gnnlm_hgt_forward (group merge, row-keyed layer-0 K / V, centre-state cache, fetched_* included); the causal branch is
+ * gnnlm_causal_attn_varlen, so the workspace has no [n_blocks, H, T, T] score and no V^T buffer.  d / n_heads must be one of
+ * the d_k that kernel is built for. */
+size_t gnnlm_hgt_workspace_bytes_ragged(const gnnlm_hgt_t* model, const gnnlm_hgt_io_t* io, const gnnlm_ragged_t* blocks);
+int gnnlm_hgt_forward_ragged(const gnnlm_hgt_t* model, const gnnlm_hgt_io_t* io, const gnnlm_ragged_t* blocks, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Sharded store, requester side: bucket the requested global rows by owning rank
