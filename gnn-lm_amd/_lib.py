@@ -119,6 +119,8 @@ def lib():
         L.gnnlm_adaptive_target_logp.argtypes = [vp, vp, i64, vp, i64, vp, vp, ctypes.c_size_t, vp]
         L.gnnlm_masked_sum_f64.argtypes = [vp, vp, i64, vp, vp]
         L.gnnlm_rows_sum_f64.argtypes = [vp, i64, i64, i64, vp, vp]
+        L.gnnlm_knn_interp_grid_lm.argtypes = [vp, i32, i64, vp]
+        L.gnnlm_logp_mix.argtypes = [vp, vp, i64, vp, i32, vp, vp]
         L.gnnlm_ivfpq_pack_codes.argtypes = [vp, i64, i32, vp, vp]
         L.gnnlm_ivfpq_pack_lut.argtypes = [vp, i64, i64, i32, vp, vp]
         L.gnnlm_ivfpq_pack_tiles.argtypes = [vp, i64, i32, vp, vp]

@@ -770,7 +770,14 @@ int gnnlm_adaptive_target_logp(const gnnlm_adaptive_softmax_t* w, const float* x
     return adaptive_impl(*w, x, ldx, target, n, lm_logp, workspace, workspace_bytes, (hipStream_t)stream);
 }
 int gnnlm_knn_interp(const gnnlm_knn_interp_t* d, void* stream) { GNNLM_DESC(d); return knn_interp(*d, (hipStream_t)stream); }
-int gnnlm_knn_interp_grid(const gnnlm_knn_interp_grid_t* d, void* stream) { GNNLM_DESC(d); return knn_interp_grid(*d, (hipStream_t)stream); }
+int gnnlm_knn_interp_grid(const gnnlm_knn_interp_grid_t* d, void* stream) { GNNLM_DESC(d); return knn_interp_grid(*d, 1, 0, (hipStream_t)stream); }
+int gnnlm_knn_interp_grid_lm(const gnnlm_knn_interp_grid_t* d, int32_t n_lm, int64_t ld_lm, void* stream) {
+    GNNLM_DESC(d);
+    return knn_interp_grid(*d, n_lm, ld_lm, (hipStream_t)stream);
+}
+int gnnlm_logp_mix(const float* gnn_logp, const float* base_logp, int64_t n, const double* alphas, int32_t n_alphas, float* out, void* stream) {
+    return logp_mix(gnn_logp, base_logp, n, alphas, n_alphas, out, (hipStream_t)stream);
+}
 int gnnlm_knn_recompute_sims(const gnnlm_knn_resim_t* d, void* stream) { GNNLM_DESC(d); return knn_recompute_sims(*d, (hipStream_t)stream); }
 size_t gnnlm_knn_interp_scratch_bytes(int64_t n, int32_t k, int64_t n_local) { return knn_interp_scratch_bytes(n, k, n_local); }
 int gnnlm_label_tags(const void* vals, int32_t vals_itemsize, int64_t n, uint8_t* tag, void* stream) { return label_tags(vals, vals_itemsize, n, tag, (hipStream_t)stream); }

@@ -179,7 +179,10 @@ size_t knn_interp_scratch_bytes(int64_t n, int k, int64_t n_local);
 bool knn_interp_bucketed_eligible(const KnnInterpParams& p);
 int knn_interp_bucketed(const KnnInterpParams& p, float log_1ml, float log_l, hipStream_t stream);
 // every point of ks x temperatures x lmbdas from one read of the search result (knn_grid.hip)
-int knn_interp_grid(const gnnlm_knn_interp_grid_t& d, hipStream_t stream);
+// lm_logp read as [n_lm, n] (row stride ld_lm), out_logp as [n_lm * G, n]; n_lm = 1 is the plain grid
+int knn_interp_grid(const gnnlm_knn_interp_grid_t& d, int n_lm, int64_t ld_lm, hipStream_t stream);
+// out[a, :] = logsumexp(log(alphas[a]) + base, log(1 - alphas[a]) + gnn) for up to 8 ratios from one read (logp_mix.hip)
+int logp_mix(const float* gnn_logp, const float* base_logp, int64_t n, const double* alphas, int n_alphas, float* out, hipStream_t stream);
 // similarities recomputed from the stored keys, one wave per (query, run of 64 neighbours) (knn_resim.hip)
 int knn_recompute_sims(const gnnlm_knn_resim_t& d, hipStream_t stream);
 

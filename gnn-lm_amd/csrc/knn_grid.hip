@@ -11,6 +11,11 @@
 // gather with the n_store / row0 / n_local rules of the single-setting kernel.  The tag table and the routed look-ups of
 // knn_bucket.hip are NOT part of this kernel: a sweep over a label table of hundreds of MB pays the one-by-one gathers.
 //
+// Several language-model rows (gnnlm_knn_interp_grid_lm: the base-LM / GNN mixture at n_lm ratios, transformer.py:1056-1077):
+// nothing of a (k', t) pair but its final mixes depends on the lm row, so the exponentials, the prefix sums and the wave
+// reductions are computed once per pair and the n_lm * n_l mixes are spread over the lanes (lane a * n_l + l mixes lm row a
+// with lmbda l; more than 64 of them take a second round).  n_lm = 1 is the plain grid, lane for lane.
+//
 // rows_sum_f64_kernel adds up every row of the [G, n] result in one launch, each row in masked_sum_f64_kernel's order.
 #include "kernels.h"
 
@@ -21,7 +26,7 @@ namespace {
 constexpr int GRID_KS = 8, GRID_T = 16, GRID_L = 16;      // capacities of gnnlm_knn_interp_grid_t
 
 struct KnnGridParams {
-    const float* lm_logp;  const float* sims;  const int64_t* ids;
+    const float* lm_logp;  int n_lm;  int64_t ld_lm;  const float* sims;  const int64_t* ids;
     const void* vals;  int vals_itemsize;  int64_t n_store, row0, n_local;
     const int32_t* knn_vals;  const int64_t* targets;
     int64_t n;  int k;
@@ -71,11 +76,23 @@ __global__ __launch_bounds__(256) void knn_interp_grid_kernel(KnnGridParams p) {
         sv[t] = id[t] == -1 ? -1e10f : sv[t];
         if (lane + 64 * t < p.k && val[t] == tgt) hits |= 1u << t;
     }
-    // the lane that mixes lmbda `lane` keeps that lmbda's two coefficients
-    float c_1ml = 0.f, c_l = 0.f;
-    for (int li = 0; li < p.n_l; ++li)
-        if (lane == li) { c_1ml = p.log_1ml[li]; c_l = p.log_l[li]; }
-    const float lm = p.lm_logp[i];
+    // mix `m` = a * n_l + l (lm row a, lmbda l) belongs to lane m % 64 in round m / 64: the lane keeps that lmbda's two coefficients,
+    // that row's log-prob of the token and the mix's row of the result (without the (k', t) pair's offset)
+    const int n_mix = p.n_lm * p.n_l;                      // <= 8 * 16: two rounds at most
+    const int G = p.n_ks * p.n_t * p.n_l;
+    float c_1ml[2] = {0.f, 0.f}, c_l[2] = {0.f, 0.f}, lm[2] = {0.f, 0.f};
+    int out_row[2] = {0, 0};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int m = lane + 64 * r;
+        if (m < n_mix) {
+            const int a = m / p.n_l, my_l = m - a * p.n_l;
+            for (int li = 0; li < p.n_l; ++li)
+                if (my_l == li) { c_1ml[r] = p.log_1ml[li]; c_l[r] = p.log_l[li]; }
+            lm[r] = p.lm_logp[(int64_t)a * p.ld_lm + i];
+            out_row[r] = a * G + my_l;
+        }
+    }
 
     if (p.out_recall)
         for (int ki = 0; ki < p.n_ks; ++ki) {
@@ -115,13 +132,16 @@ __global__ __launch_bounds__(256) void knn_interp_grid_kernel(KnnGridParams p) {
             const float pk = num / den;
             const int64_t kt = (int64_t)ki * p.n_t + ti;
             if (lane == 0 && p.out_pknn) p.out_pknn[kt * p.n + i] = pk;
-            if (lane < p.n_l) {
-                // sequence_scorer.py:55-68 with knn_probs = log(p + 1e-10) (:121)
-                const float a = lm + c_1ml;
-                const float b = logf(pk + 1e-10f) + c_l;
-                const float m = fmaxf(a, b);
-                p.out_logp[(kt * p.n_l + lane) * p.n + i] = m + logf(expf(a - m) + expf(b - m));
-            }
+            const float lpk = logf(pk + 1e-10f);
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+                if (lane + 64 * r < n_mix) {
+                    // sequence_scorer.py:55-68 with knn_probs = log(p + 1e-10) (:121)
+                    const float a = lm[r] + c_1ml[r];
+                    const float b = lpk + c_l[r];
+                    const float m = fmaxf(a, b);
+                    p.out_logp[(kt * p.n_l + out_row[r]) * p.n + i] = m + logf(expf(a - m) + expf(b - m));
+                }
         }
     }
 }
@@ -142,7 +162,9 @@ __global__ __launch_bounds__(1024) void rows_sum_f64_kernel(const float* x, int6
 
 }  // namespace
 
-int knn_interp_grid(const gnnlm_knn_interp_grid_t& d, hipStream_t stream) {
+int knn_interp_grid(const gnnlm_knn_interp_grid_t& d, int n_lm, int64_t ld_lm, hipStream_t stream) {
+    GNNLM_REQUIRE(n_lm >= 1 && n_lm <= 8, "knn_interp_grid: 1 .. 8 lm rows per call");
+    GNNLM_REQUIRE(n_lm == 1 || ld_lm >= d.n, "knn_interp_grid: the lm rows overlap (ld_lm < n)");
     GNNLM_REQUIRE(d.lm_logp && d.sims && d.ids && d.targets && d.out_logp, "knn_interp_grid: null operand");
     GNNLM_REQUIRE(d.knn_vals || d.vals, "knn_interp_grid: need vals or pre-fetched knn_vals");
     GNNLM_REQUIRE(d.knn_vals || (d.n_local > 0 && d.n_store > 0 && d.row0 >= 0), "knn_interp_grid: vals needs n_store / row0 / n_local");
@@ -169,15 +191,15 @@ int knn_interp_grid(const gnnlm_knn_interp_grid_t& d, hipStream_t stream) {
     }
     if (d.n == 0) return OK;
     GNNLM_REQUIRE(cdiv(d.n, 4) < (1ll << 31), "knn_interp_grid: too many tokens for one launch");
-    p.lm_logp = d.lm_logp, p.sims = d.sims, p.ids = d.ids;
+    p.lm_logp = d.lm_logp, p.n_lm = n_lm, p.ld_lm = n_lm == 1 ? 0 : ld_lm, p.sims = d.sims, p.ids = d.ids;
     p.vals = d.vals, p.vals_itemsize = d.vals_itemsize, p.n_store = d.n_store, p.row0 = d.row0, p.n_local = d.n_local;
     p.knn_vals = d.knn_vals, p.targets = d.targets;
     p.n = d.n, p.k = d.k;
     p.n_ks = d.n_ks, p.n_t = d.n_temperatures, p.n_l = d.n_lmbdas;
     p.out_logp = d.out_logp, p.out_pknn = d.out_pknn, p.out_recall = d.out_recall;
-    const double G = (double)d.n_ks * d.n_temperatures * d.n_lmbdas;
+    const double G = (double)n_lm * d.n_ks * d.n_temperatures * d.n_lmbdas;
     ProfScope prof(K_KNN_GRID, stream, 0.0,
-                   (double)d.n * d.k * (12.0 + (d.knn_vals ? 4.0 : d.vals_itemsize)) + (12.0 + 4.0 * G) * d.n);
+                   (double)d.n * d.k * (12.0 + (d.knn_vals ? 4.0 : d.vals_itemsize)) + (8.0 + 4.0 * n_lm + 4.0 * G) * d.n);
     const dim3 grid((unsigned)cdiv(d.n, 4)), block(256);
     if (d.k <= 256) hipLaunchKernelGGL(knn_interp_grid_kernel<4>, grid, block, 0, stream, p);
     else hipLaunchKernelGGL(knn_interp_grid_kernel<16>, grid, block, 0, stream, p);

@@ -63,8 +63,15 @@ class GnnLmEngine:
         return self.hgt(G, features={"tgt": tgt})["tgt"]
 
     def score(self, batch: BlockBatch, lmbda: float = 0.0, temperature: float = 1.0, knn_index=None, k: int = 0, sweep=None,
-              knn_keys=None, knn_sim_func: str = "do_not_recomp_ip"):
+              knn_keys=None, knn_sim_func: str = "do_not_recomp_ip", orig_prob_ratio: float = 0.0):
         """Per-token log-probabilities.  Returns dict(gcn_feat, lm_logp, logp[, p_knn, recall]).
+
+        ``orig_prob_ratio`` = alpha in (0, 1) (transformer.py:987-1005,1056-1062,1075-1077): ``lm_logp`` is the mixture
+        logsumexp(log(alpha) + ``lm_logp_base``, log(1 - alpha) + ``lm_logp_gnn``) of the tied softmax over the batch's precomputed
+        features and over the HGT output (both returned), ``logp`` the kNN mix of that.  <= 0: off (``lm_logp`` is ``lm_logp_gnn``);
+        >= 1: ValueError, as the reference's math.log(1 - alpha).  A sweep may carry a fourth element ``alphas`` (each in 0 .. 1, at most
+        8): ``sweep_logp`` is then [len(alphas) * G, n] with alpha slowest (``ops.grid_points(ks, ts, ls, alphas)``), from one more
+        softmax pass whatever the number of alphas; ``(None, None, None, alphas)`` sweeps the ratio alone.
 
         ``sweep = (ks, temperatures, lmbdas)``: additionally ``sweep_logp`` [G, n], every point of the kNN-LM tuning grid
         (``ops.grid_points`` order) from the step's one forward and one search (which then runs with ``lmbda`` 0 too).
@@ -78,10 +85,10 @@ class GnnLmEngine:
         knn_model.py:161-175): the index's distances are replaced by the similarities recomputed from the full-precision keys
         (``ops.knn_recompute_sims``; "ip" divides by |key| as the reference does for the cosine index this search stands for) before
         the interpolation and the sweep, and come back as ``knn_sims``."""
-        return self.score_finish(self.score_begin(batch, lmbda, temperature, knn_index, k, sweep, knn_keys, knn_sim_func))
+        return self.score_finish(self.score_begin(batch, lmbda, temperature, knn_index, k, sweep, knn_keys, knn_sim_func, orig_prob_ratio))
 
     def score_begin(self, batch: BlockBatch, lmbda: float = 0.0, temperature: float = 1.0, knn_index=None, k: int = 0, sweep=None,
-                    knn_keys=None, knn_sim_func: str = "do_not_recomp_ip"):
+                    knn_keys=None, knn_sim_func: str = "do_not_recomp_ip", orig_prob_ratio: float = 0.0):
         """Enqueue the step up to the search's host read (features, search, softmax) and return a handle for ``score_finish``:
         several batches can be in flight (one per stream), the host looks at a search's survivor counts only when it comes back
         to that batch."""
@@ -89,18 +96,42 @@ class GnnLmEngine:
             raise ValueError("knn_sim_func: do_not_recomp_ip, ip or l2 (the in-step search is an inner-product one)")
         if knn_sim_func != "do_not_recomp_ip" and knn_keys is None:
             raise ValueError(f"knn_sim_func={knn_sim_func!r} needs knn_keys (the key table in HBM)")
+        if orig_prob_ratio >= 1:
+            raise ValueError(f"math domain error: orig_prob_ratio = {orig_prob_ratio} needs log(1 - orig_prob_ratio) (transformer.py:1060)")
+        alpha = float(orig_prob_ratio) if orig_prob_ratio > 0 else 0.0
+        alphas = list(sweep[3]) if sweep and len(sweep) > 3 else None
+        sweep = tuple(sweep[:3]) if sweep and sweep[0] is not None else None
         x = self.features(batch)
         pending = qn = None
         if (lmbda > 0.0 or sweep) and knn_index is not None:
             qn = x / (x ** 2).sum(-1, keepdim=True).sqrt()
             pending = knn_index.search_begin(qn.contiguous(), k, return_vals=True)
-        lm_logp = self.asm.target_log_prob(x, batch.targets)
+        branches = lm_rows = None
+        if alpha > 0 or alphas:
+            # the base branch: the same softmax over the precomputed features (the "orig_x" of transformer.py:988 under
+            # --use-precompute-feat), one more pass whatever the number of alphas.  Two n-row calls, not one over the stacked [2n, d]
+            # rows: the GEMMs take the same time either way and the stacked form pays for its two concatenations
+            h = batch.tgt_feats
+            h = ops.half_to_float(h.contiguous()) if h.dtype == torch.float16 else h.float()
+            lm_logp = self.asm.target_log_prob(x, batch.targets)
+            branches = (lm_logp, self.asm.target_log_prob(h, batch.targets))
+            if alphas:
+                lm_rows = ops.logp_mix(*branches, alphas)                  # [A, n]: the grid's language-model rows
+            if alpha > 0:
+                lm_logp = ops.logp_mix(*branches, [alpha])[0]
+        else:
+            lm_logp = self.asm.target_log_prob(x, batch.targets)
         resim = (qn, knn_keys, knn_sim_func) if pending is not None and knn_sim_func != "do_not_recomp_ip" else None
-        return batch, lmbda, temperature, x, lm_logp, pending, sweep, resim
+        return batch, lmbda, temperature, x, lm_logp, pending, sweep, resim, branches, lm_rows
 
     def score_finish(self, handle):
-        batch, lmbda, temperature, x, lm_logp, pending, sweep, resim = handle
+        batch, lmbda, temperature, x, lm_logp, pending, sweep, resim, branches, lm_rows = handle
         out = {"gcn_feat": x, "lm_logp": lm_logp, "logp": lm_logp}
+        if branches is not None:
+            out.update(lm_logp_gnn=branches[0], lm_logp_base=branches[1])
+        if lm_rows is not None and not sweep:
+            out["sweep_logp"] = lm_rows                                   # the ratio alone: one point per alpha
+        grid_lm = lm_rows if lm_rows is not None else lm_logp
         if pending is not None:
             sims, ids, vals = pending.result()
             if resim is not None:                                # knn_model.py:161-175 on the step's own normalised queries
@@ -112,7 +143,7 @@ class GnnLmEngine:
                 out.update(logp=logp, p_knn=p_knn, recall=recall)
             out.update(knn_sims=sims, knn_ids=ids, knn_vals=vals)
             if sweep:
-                out["sweep_logp"] = ops.knn_interp_grid(lm_logp, sims, ids, batch.targets, *sweep, n_store=self.store.n_store, knn_vals=vals)[0]
+                out["sweep_logp"] = ops.knn_interp_grid(grid_lm, sims, ids, batch.targets, *sweep, n_store=self.store.n_store, knn_vals=vals)[0]
         elif lmbda > 0.0 or sweep:                               # sequence_scorer.py:102
             if batch.knn_sims is None or batch.knn_ids is None:
                 raise ValueError("lmbda > 0 needs knn_sims / knn_ids (results of the kNN search)")
@@ -124,5 +155,5 @@ class GnnLmEngine:
                 logp, p_knn, recall = ops.knn_interp(lm_logp, batch.knn_sims, batch.knn_ids, batch.targets, temperature, lmbda, **labels)
                 out.update(logp=logp, p_knn=p_knn, recall=recall)
             if sweep:
-                out["sweep_logp"] = ops.knn_interp_grid(lm_logp, batch.knn_sims, batch.knn_ids, batch.targets, *sweep, **labels)[0]
+                out["sweep_logp"] = ops.knn_interp_grid(grid_lm, batch.knn_sims, batch.knn_ids, batch.targets, *sweep, **labels)[0]
         return out

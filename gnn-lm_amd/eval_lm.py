@@ -20,7 +20,9 @@ Output: the reference's two final lines (eval_lm.py:325-331).
 Tuning in one pass (this build): ``--sweep-lmbda 0,0.1,0.25 --sweep-temperature 1,0.1 --sweep-k 256,1024`` scores every point
 of the grid from the run's one forward and one search (the reference runs the whole evaluation once per setting,
 gnnlm_scripts/wiki103/hgt_lm_wiki103_reproduce.sh:137) and prints one ``sweep k=.. temperature=.. lmbda=.. loss=.. ppl=..``
-line per point after the two result lines.
+line per point after the two result lines.  ``--sweep-orig-prob-ratio 0,0.3,1`` adds the base-LM / GNN mixture ratio
+(``--model-overrides "{'orig_prob_ratio': a}"``, transformer.py:987-1005,1056-1077) as the grid's outer axis -- or, without
+``--knnlm``, sweeps it alone (``sweep orig_prob_ratio=.. loss=.. ppl=..``): the base branch is one more softmax pass for every ratio.
 """
 import argparse
 import ast
@@ -130,6 +132,12 @@ def get_parser():
     p.add_argument("--sweep-temperature", default=None, help="(this build) comma-separated softmax temperatures (> 0), see --sweep-lmbda")
     p.add_argument("--sweep-k", default=None, help="(this build) comma-separated neighbour counts, each 1 <= k' <= --k (the first k' of the search's "
                                                    "result: what a k'-search returns), see --sweep-lmbda")
+    p.add_argument("--sweep-orig-prob-ratio", default=None,
+                   help="(this build) comma-separated ratios of the base-LM / GNN mixture (at most 8 distinct values, each 0 <= a <= 1; the "
+                        "model's own is --model-overrides \"{'orig_prob_ratio': a}\"): every ratio is scored from the run's one forward and ONE "
+                        "more softmax pass (over the precomputed features) where the reference runs the whole evaluation per value; 1 is the base "
+                        "LM's own perplexity.  With --knnlm it is the outer axis of the --sweep-* grid (a list not given is the run's own value), "
+                        "without it the ratio is swept alone")
     p.add_argument("--result-json", default=None,
                    help="(this build) write the run's figures (score_sum, count, ppl, tokens, seconds, per-rank sums, xGMI bytes) to this "
                         "file as JSON; in a multi-process run rank r writes PATH.rank<r> and rank 0 also PATH")
@@ -232,15 +240,48 @@ def word_outputs(args, hypos, sample_ids, symbols, bpe_toks, bpe_len, word_stats
 
 
 SWEEP_MAX = {"k": 8, "temperature": 16, "lmbda": 16}     # capacities of gnnlm_knn_interp_grid_t
+SWEEP_MAX_ALPHAS = 8                                      # lm rows of gnnlm_knn_interp_grid_lm / ratios of gnnlm_logp_mix
+
+
+def parse_sweep_alphas(args):
+    """The ratios of --sweep-orig-prob-ratio as a list of floats, or None when the flag is not given (host only, ``ValueError``)."""
+    raw = getattr(args, "sweep_orig_prob_ratio", None)
+    if raw is None:
+        return None
+    if getattr(args, "save_knnlm_dstore", False):
+        raise ValueError("--sweep-* cannot be combined with --save-knnlm-dstore")
+    try:
+        alphas = [float(v.strip()) for v in str(raw).split(",")]
+    except ValueError:
+        raise ValueError(f"--sweep-orig-prob-ratio: expected a comma-separated list of numbers, got {raw!r}")
+    if len(alphas) > SWEEP_MAX_ALPHAS:
+        raise ValueError(f"--sweep-orig-prob-ratio: at most {SWEEP_MAX_ALPHAS} values per run, got {len(alphas)}")
+    if len(set(alphas)) != len(alphas):
+        raise ValueError(f"--sweep-orig-prob-ratio: repeated value in {raw!r}")
+    if any(not 0.0 <= v <= 1.0 for v in alphas):
+        raise ValueError("--sweep-orig-prob-ratio: every ratio must lie in 0 .. 1")
+    return alphas
 
 
 def parse_sweep(args):
     """The run's tuning grid ``(ks, temperatures, lmbdas)`` from --sweep-k / --sweep-temperature / --sweep-lmbda, or None when none of
     them is given.  A list not given is the run's own value.  Host-only: raises ``ValueError`` before any device work.  The options are
-    read with getattr: callers that build their own namespace (bench.py) do not know them."""
+    read with getattr: callers that build their own namespace (bench.py) do not know them.  With --sweep-orig-prob-ratio the result
+    is ``(ks, temperatures, lmbdas, alphas)``: the ratio is the outer axis of the grid -- or, without --knnlm, the only one:
+    ``(None, None, None, alphas)``."""
     raw = {"k": getattr(args, "sweep_k", None), "temperature": getattr(args, "sweep_temperature", None), "lmbda": getattr(args, "sweep_lmbda", None)}
+    alphas = parse_sweep_alphas(args)
+    if alphas is not None:
+        if not getattr(args, "knnlm", False) and all(v is None for v in raw.values()):
+            return None, None, None, alphas
+        knn = _parse_knn_sweep(args, raw)
+        return knn + (alphas,)
     if all(v is None for v in raw.values()):
         return None
+    return _parse_knn_sweep(args, raw)
+
+
+def _parse_knn_sweep(args, raw):
     if not getattr(args, "knnlm", False):
         raise ValueError("--sweep-lmbda / --sweep-temperature / --sweep-k need --knnlm (there is no kNN term to tune otherwise)")
     if getattr(args, "save_knnlm_dstore", False):
@@ -272,19 +313,28 @@ def parse_sweep(args):
 
 
 def sweep_table(sweep, sums, count):
-    """One dict per grid point in ``ops.grid_points`` order (k slowest, lmbda fastest) from the points' score sums."""
+    """One dict per grid point in ``ops.grid_points`` order (k slowest, lmbda fastest; with a fourth element ``alphas``,
+    ``orig_prob_ratio`` slowest of all) from the points' score sums.  The ``orig_prob_ratio`` key is there only with that axis."""
     rows = []
-    for (k, t, l), ssum in zip(ops.grid_points(*sweep), sums):
+    for pt, ssum in zip(ops.grid_points(*sweep), sums):
         loss = -ssum / count / math.log(2) if count else float("nan")
-        rows.append({"k": k, "temperature": t, "lmbda": l, "score_sum": ssum, "loss": loss, "ppl": 2 ** loss})
+        row = {"orig_prob_ratio": pt[0]} if len(sweep) > 3 else {}
+        if len(pt) >= 3:
+            row.update(zip(("k", "temperature", "lmbda"), pt[-3:]))
+        row.update(score_sum=ssum, loss=loss, ppl=2 ** loss)
+        rows.append(row)
     return rows
 
 
 def sweep_lines(rows):
     """The printed form of :func:`sweep_table`: one line per point, the lowest perplexity marked."""
     best = min(range(len(rows)), key=lambda i: rows[i]["ppl"]) if rows else -1
-    return ["sweep k={} temperature={:g} lmbda={:g} loss={:.4f} ppl={:.2f}{}".format(r["k"], r["temperature"], r["lmbda"], r["loss"], r["ppl"],
-                                                                                   "  <- best" if i == best else "") for i, r in enumerate(rows)]
+    lines = []
+    for i, r in enumerate(rows):
+        head = "sweep" + (" orig_prob_ratio={:g}".format(r["orig_prob_ratio"]) if "orig_prob_ratio" in r else "") + \
+            (" k={} temperature={:g} lmbda={:g}".format(r["k"], r["temperature"], r["lmbda"]) if "k" in r else "")
+        lines.append(head + " loss={:.4f} ppl={:.2f}{}".format(r["loss"], r["ppl"], "  <- best" if i == best else ""))
+    return lines
 
 
 def block_ranges(n_tokens, block, context_window=0):
@@ -484,6 +534,8 @@ def main(args, tables=None, model=None):
     overrides = ast.literal_eval(args.model_overrides)
     if model is None:
         model, margs = GnnLmModel.from_checkpoint(args.path, device, overrides, vocab_size=tabs["vocab"])
+    # a sweep over the ratio runs the base branch even when the run's own ratio is 0 (the model leaves both unmixed rows per batch)
+    model.keep_branches = bool(sweep and len(sweep) > 3)
     fetcher = None
     if shard is None:
         store = model.make_store(tabs["codes"], tabs["n_store"], device)

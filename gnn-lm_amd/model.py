@@ -21,13 +21,22 @@ from .pq_wrapper import TorchPQCodec
 class GnnLmModel(torch.nn.Module):
     graph_capture = False              # (class defaults: subclasses that script forward() need not call __init__)
     _graphs, _static_x = None, frozenset()
+    orig_prob_ratio, keep_branches, short_cut = 0.0, False, False
 
     def __init__(self, hgt: HGT, asm: AdaptiveSoftmax, quantizer: TorchPQCodec = None, orig_prob_ratio: float = 0.0,
                  short_cut: bool = False):
         super().__init__()
-        if orig_prob_ratio > 0:
-            raise NotImplementedError("orig_prob_ratio > 0 needs the base-LM logits (transformer.py:987-1005); "
-                                      "the GNN-LM recipes evaluate with 0.0")
+        # orig_prob_ratio = alpha > 0 (transformer.py:987-1005,1056-1062,1075-1077): every token is scored with
+        #   logsumexp(log(alpha) + log p_asm(target | h), log(1 - alpha) + log p_asm(target | x))
+        # h the base LM's feature, x the GNN output, both through the same tied adaptive softmax.  Under --use-precompute-feat h is
+        # graph.tgt_h, which the step already holds: no base LM is involved.  alpha <= 0 is off (the reference tests `> 0`);
+        # alpha >= 1 is where the reference's math.log(1 - p1_coeff) raises ValueError("math domain error")
+        if orig_prob_ratio >= 1:
+            raise ValueError(f"math domain error: orig_prob_ratio = {orig_prob_ratio} needs log(1 - orig_prob_ratio) "
+                             "(transformer.py:1060); use a ratio below 1 (eval_lm --sweep-orig-prob-ratio scores the base LM alone as its point 1)")
+        self.orig_prob_ratio = float(orig_prob_ratio) if orig_prob_ratio > 0 else 0.0
+        # a driver that sweeps the ratio wants the two unmixed branches of every batch whatever the model's own ratio is
+        self.keep_branches = False
         self.hgt_decoder, self.adaptive_softmax, self.tgt_quantizer = hgt, asm, quantizer
         self.short_cut = short_cut
         # `eval_lm --graph-capture`: the launches of forward() and of target_log_probs() replayed from HIP graphs, one pair per
@@ -116,6 +125,9 @@ class GnnLmModel(torch.nn.Module):
         x = h if self.short_cut else self.hgt_decoder(graph, features={"tgt": h})["tgt"]
         x = x.view(bsz, tgt_len, -1)
         extra["gcn_feat"] = x.transpose(0, 1)                               # :997
+        if self.orig_prob_ratio > 0 or self.keep_branches:
+            extra["orig_x"] = h.view(bsz, tgt_len, -1)                      # :1004 (with an adaptive softmax output_layer is the identity)
+            extra["orig_ratio"] = self.orig_prob_ratio                      # :1005
         return x, extra
 
     def target_log_probs(self, net_output, target):
@@ -123,6 +135,9 @@ class GnnLmModel(torch.nn.Module):
         (transformer.py:1064-1079, sequence_scorer.py:48-53,89) without the dense [T, V] tensor."""
         x = net_output[0]
         bsz, T, d = x.shape
+        extra = net_output[1] if len(net_output) > 1 and isinstance(net_output[1], dict) else {}
+        if "orig_x" in extra:
+            return self._target_log_probs_mixed(x, extra, target)
         if self.graph_capture and x.data_ptr() in self._static_x and not torch.cuda.is_current_stream_capturing():
             key = ("asm", x.data_ptr(), bsz, T, d)                # x is a replayed forward's static output: its address names the shape's graph
             e = self._graphs.get(key)
@@ -139,6 +154,46 @@ class GnnLmModel(torch.nn.Module):
             e["graph"].replay()
             return e["out"]
         return self.adaptive_softmax.target_log_prob(x.reshape(-1, d).contiguous(), target.reshape(-1)).view(bsz, T)
+
+    def _branches(self, x2, h2, tgt):
+        """-> (gnn, base, mixed), each [n]: the softmax of the GNN output, of the base LM's feature, and their mixture at the model's
+        own ratio (the GNN branch itself when that is 0).  The GNN branch is the same call as without a ratio.  With short_cut the
+        GNN output IS the feature (both branches on h): one call serves both."""
+        from . import ops
+        asm = self.adaptive_softmax
+        if self.short_cut:
+            gnn = base = asm.target_log_prob(x2, tgt)
+        else:                   # two n-row calls (one call over the stacked [2n, d] rows was measured and is no faster: DESIGN.md 7.9)
+            gnn, base = asm.target_log_prob(x2, tgt), asm.target_log_prob(h2, tgt)
+        mixed = ops.logp_mix(gnn, base, [self.orig_prob_ratio])[0] if self.orig_prob_ratio > 0 else gnn
+        return gnn, base, mixed
+
+    def _target_log_probs_mixed(self, x, extra, target):
+        """target_log_probs with the base branch (get_normalized_probs, transformer.py:1075-1077): the mixture [bsz, tgt_len]; the
+        two unmixed rows are left in ``extra["branch_logp"] = (gnn, base)`` for a sweep over the ratio."""
+        bsz, T, d = x.shape
+        h = extra["orig_x"]
+        x2, h2 = x.reshape(-1, d).contiguous(), h.reshape(-1, h.shape[-1]).contiguous()
+        if self.graph_capture and x.data_ptr() in self._static_x and not torch.cuda.is_current_stream_capturing():
+            # both branches and the mix inside the shape's "asm" graph (x and orig_x are the replayed forward's static outputs)
+            key = ("asm", x.data_ptr(), bsz, T, d)
+            e = self._graphs.get(key)
+            if e is None:
+                tgt = target.reshape(-1).clone()
+                self._branches(x2, h2, tgt)
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                cap = self._capture_stream()
+                with torch.cuda.graph(g, stream=cap):                          # (the lane's own stream: see _forward_replayed)
+                    out = tuple(t.view(bsz, T) for t in self._branches(x2, h2, tgt))
+                e = self._graphs[key] = {"graph": g, "target": tgt, "out": out, "x": x, "h": h2, "capture_stream": cap}
+            e["target"].copy_(target.reshape(-1))
+            e["graph"].replay()
+            gnn, base, mixed = e["out"]
+        else:
+            gnn, base, mixed = (t.view(bsz, T) for t in self._branches(x2, h2, target.reshape(-1)))
+        extra["branch_logp"] = (gnn, base)
+        return mixed
 
     def get_normalized_probs(self, net_output, log_probs, sample):
         raise NotImplementedError("the dense [B, T, V] tensor is never materialised; use target_log_probs()")

@@ -379,17 +379,46 @@ def knn_interp(lm_logp, sims, ids, targets, temperature, lmbda, vals=None, n_sto
     return out, pk, rec
 
 
-def grid_points(ks, temperatures, lmbdas):
+def grid_points(ks, temperatures, lmbdas, alphas=None):
     """The points of a sweep in the one order every layer uses: k slowest, then temperature, lmbda fastest
-    (row g of ``knn_interp_grid``'s result, ``gnnlm_knn_interp_grid_t``)."""
-    return [(int(k), float(t), float(l)) for k in ks for t in temperatures for l in lmbdas]
+    (row g of ``knn_interp_grid``'s result, ``gnnlm_knn_interp_grid_t``).  With ``alphas`` (the ``orig_prob_ratio`` axis) the points
+    are ``(alpha, k, temperature, lmbda)`` and alpha is slowest of all (``gnnlm_knn_interp_grid_lm``); a sweep of alphas alone
+    (``ks`` None: no kNN term) has the points ``(alpha,)``."""
+    if alphas is None:
+        return [(int(k), float(t), float(l)) for k in ks for t in temperatures for l in lmbdas]
+    if ks is None:
+        return [(float(a),) for a in alphas]
+    return [(float(a), int(k), float(t), float(l)) for a in alphas for k in ks for t in temperatures for l in lmbdas]
+
+
+def logp_mix(gnn_logp, base_logp, alphas, out=None):
+    """The ``orig_prob_ratio`` mixture of two target log-probabilities (``gnnlm_logp_mix``; transformer.py:1056-1062,1075-1077):
+    ``out[a] = logsumexp(log(alphas[a]) + base_logp, log(1 - alphas[a]) + gnn_logp)`` -> [len(alphas), n] f32 from one read of the
+    two inputs.  1 .. 8 ratios, each in 0 .. 1; 0 gives ``gnn_logp`` back bit for bit and 1 ``base_logp``."""
+    _dev(gnn_logp, base_logp, out)
+    _f32(gnn_logp, base_logp, out)
+    alphas = [float(a) for a in alphas]
+    if gnn_logp.dim() != 1 or gnn_logp.shape != base_logp.shape or not (gnn_logp.is_contiguous() and base_logp.is_contiguous()):
+        raise ValueError("logp_mix: gnn_logp, base_logp [n] contiguous")
+    n = gnn_logp.shape[0]
+    if out is None:
+        out = torch.empty(len(alphas), n, device=gnn_logp.device, dtype=torch.float32)
+    elif out.shape != (len(alphas), n) or not out.is_contiguous():
+        raise ValueError("logp_mix: out [len(alphas), n] contiguous")
+    # the count goes in as given: more ratios than the kernel takes are refused by the library, never cut short
+    call("gnnlm_logp_mix", ptr(gnn_logp), ptr(base_logp), n, (ctypes.c_double * max(1, len(alphas)))(*alphas), len(alphas), ptr(out), stream())
+    return out
 
 
 def knn_interp_grid(lm_logp, sims, ids, targets, ks, temperatures, lmbdas, vals=None, n_store=None, row0=0, knn_vals=None):
     """Every point of ``ks x temperatures x lmbdas`` from one read of the search result (``gnnlm_knn_interp_grid``):
     -> (logp [G, n] f32 in :func:`grid_points` order, p_knn [len(ks) * len(temperatures), n] f32, recall [len(ks), n] i64).
     A point with 0 < lmbda < 1 equals ``knn_interp`` on the first k' columns bit for bit; lmbda 0 / 1 are allowed.  The label
-    table is read by the plain gather (no tag table, no routed look-ups); k <= 1024."""
+    table is read by the plain gather (no tag table, no routed look-ups); k <= 1024.
+
+    A 2-D ``lm_logp`` [A, n] (1 <= A <= 8 language-model rows: the ``orig_prob_ratio`` axis) goes through
+    ``gnnlm_knn_interp_grid_lm``: logp is then [A * G, n] with the lm row slowest, and row block a equals the 1-D call with
+    ``lm_logp[a]`` bit for bit; p_knn and recall do not depend on the lm row."""
     _dev(lm_logp, sims, ids, targets, vals, knn_vals)
     _f32(lm_logp, sims)
     _dtype(ids, torch.int64, "ids"), _dtype(targets, torch.int64, "targets"), _dtype(knn_vals, torch.int32, "knn_vals")
@@ -400,6 +429,9 @@ def knn_interp_grid(lm_logp, sims, ids, targets, ks, temperatures, lmbdas, vals=
             raise _lib.GnnlmError("knn_interp_grid needs contiguous tensors")
     ks, temperatures, lmbdas = [int(v) for v in ks], [float(v) for v in temperatures], [float(v) for v in lmbdas]
     n, k = sims.shape
+    if lm_logp.dim() not in (1, 2) or lm_logp.shape[-1] != n:
+        raise ValueError("knn_interp_grid: lm_logp [n] or [A, n]")
+    n_lm = lm_logp.shape[0] if lm_logp.dim() == 2 else None
     dev = sims.device
     d = _lib.gnnlm_knn_interp_grid_t()
     d.lm_logp, d.sims, d.ids, d.targets = lm_logp.data_ptr(), sims.data_ptr(), ids.data_ptr(), targets.data_ptr()
@@ -418,11 +450,14 @@ def knn_interp_grid(lm_logp, sims, ids, targets, ks, temperatures, lmbdas, vals=
         for j, v in enumerate(src[:len(dst)]):
             dst[j] = v
     G = len(ks) * len(temperatures) * len(lmbdas)
-    out = torch.empty(G, n, device=dev, dtype=torch.float32)
+    out = torch.empty((n_lm or 1) * G, n, device=dev, dtype=torch.float32)
     pk = torch.empty(len(ks) * len(temperatures), n, device=dev, dtype=torch.float32)
     rec = torch.empty(len(ks), n, device=dev, dtype=torch.int64)
     d.out_logp, d.out_pknn, d.out_recall = out.data_ptr(), pk.data_ptr(), rec.data_ptr()
-    call_desc("gnnlm_knn_interp_grid", d)
+    if n_lm is None:
+        call_desc("gnnlm_knn_interp_grid", d)
+    else:
+        call("gnnlm_knn_interp_grid_lm", ctypes.byref(d), n_lm, n, stream())
     return out, pk, rec
 
 

@@ -2,8 +2,9 @@
 
 Same constructor, same ``generate(models, sample, knn_dstore=..., temperature=...)`` call, same
 hypothesis dicts (``tokens, score, attention, alignment, positional_scores, dstore_keys, knn_recall``,
-:185-193).  (This build) with ``args.sweep = (ks, temperatures, lmbdas)`` ``generate_finish`` also leaves
-``handle["sweep_logp"]`` [G, scored tokens]: every point of the kNN-LM tuning grid, from the batch's one search.
+:185-193).  (This build) with ``args.sweep = (ks, temperatures, lmbdas[, alphas])`` ``generate_finish`` also leaves
+``handle["sweep_logp"]`` [G, scored tokens]: every point of the kNN-LM tuning grid, from the batch's one search (``alphas``: the
+``orig_prob_ratio`` axis, slowest, from the model's two softmax branches; ``(None, None, None, alphas)`` sweeps the ratio alone).
 What differs is only where the arithmetic runs: the dense ``[B, T, V]`` log-prob tensor and
 the host-side kNN gathers are replaced by the HIP kernels behind ``model.target_log_probs`` and
 ``KNNModel.interpolate``.
@@ -53,7 +54,11 @@ class SequenceScorer(object):
         use_knn = "knn_dstore" in kwargs and lmbda > 0.0
         # (this build) args.sweep = (ks, temperatures, lmbdas): the tuning grid is scored from this batch's one search -- which therefore
         # runs with --lmbda 0 too (the hypotheses then stay the LM's)
-        sweep = getattr(self.args, "sweep", None) if "knn_dstore" in kwargs else None
+        sweep = getattr(self.args, "sweep", None)
+        # a fourth element is the orig_prob_ratio axis (alphas): the model's two unmixed branches are mixed at every alpha, and each
+        # mixture is one language-model row of the grid -- or, without a kNN term (ks None / no knn_dstore), a point of its own
+        alphas = sweep[3] if sweep and len(sweep) > 3 else None
+        sweep = tuple(sweep[:3]) if sweep and sweep[0] is not None and "knn_dstore" in kwargs else None
         pending = None
         if use_knn or sweep:
             # (the reference's precondition is about ITS batch: with the driver's --batch-blocks the launch holds several of the recipe's
@@ -70,7 +75,7 @@ class SequenceScorer(object):
                 pending = knn_model.interpolate_begin(queries.contiguous().view(-1, hidden))
         probs = model.target_log_probs(decoder_out, orig_target.clamp(min=0))
         return dict(sample=sample, decoder_out=decoder_out, probs=probs, use_knn=use_knn, pending=pending, lmbda=lmbda, temperature=temperature,
-                    knn_model=kwargs.get("knn_dstore"), queries=(queries if use_knn or sweep else None), sweep=sweep)
+                    knn_model=kwargs.get("knn_dstore"), queries=(queries if use_knn or sweep else None), sweep=sweep, alphas=alphas)
 
     @torch.no_grad()
     def generate_finish(self, h):
@@ -79,7 +84,12 @@ class SequenceScorer(object):
         orig_target = sample["target"]
         bsz, tsz = orig_target.shape
         recall = None
-        sweep, grid = h.get("sweep"), None
+        sweep, grid, alphas = h.get("sweep"), None, h.get("alphas")
+        if alphas:
+            from . import ops
+            if "branch_logp" not in decoder_out[1]:
+                raise ValueError("a sweep over orig_prob_ratio needs the model's two branches (GnnLmModel.keep_branches)")
+            gnn, base = decoder_out[1]["branch_logp"]                                   # [B, T] each, unmixed
         if sweep:
             # one search result, two consumers: the hypotheses' own setting and the grid (same targets, same pairing)
             queries = h["queries"]
@@ -87,12 +97,16 @@ class SequenceScorer(object):
             tq = (orig_target.transpose(0, 1) if sample.get("blockwise_knn") else orig_target.permute(0, 1)).reshape(seq_len * b2)
             lm_flat = probs.transpose(0, 1).reshape(-1)
             found = knn_model.search_finish(pending if pending is not None else knn_model.interpolate_begin(queries.contiguous().view(-1, hidden)))
-            grid = knn_model.interpolate_grid_finish(found, tq.clamp(min=0), lm_flat, *sweep)[0].view(-1, seq_len, b2).transpose(1, 2)   # [G, B, T]
+            lm_rows = lm_flat if not alphas else \
+                ops.logp_mix(gnn.transpose(0, 1).reshape(-1), base.transpose(0, 1).reshape(-1), alphas)   # [A, T*B]: alpha is the grid's slowest axis
+            grid = knn_model.interpolate_grid_finish(found, tq.clamp(min=0), lm_rows, *sweep)[0].view(-1, seq_len, b2).transpose(1, 2)   # [G, B, T]
             if use_knn:
                 mixed, _, rec = knn_model.interpolate_finish(found, tq.clamp(min=0), lm_flat, temperature, lmbda)
                 probs = mixed.view(seq_len, b2).transpose(0, 1)
                 recall = rec.view(seq_len, b2).transpose(0, 1)
-        elif use_knn:
+        elif alphas:                                            # the ratio alone: one point per alpha, no kNN term
+            grid = ops.logp_mix(gnn.reshape(-1), base.reshape(-1), alphas).view(-1, bsz, tsz)
+        if use_knn and not sweep:
             queries = h["queries"]
             seq_len, b2, hidden = queries.shape
             # as written (:117): targets in [B, T] order against queries in [T, B] order -- only right for B = 1, the recipe.

@@ -315,6 +315,25 @@ typedef struct gnnlm_knn_interp_grid {
     int64_t* out_recall;       /* optional [n_ks, n] */
 } gnnlm_knn_interp_grid_t;
 int gnnlm_knn_interp_grid(const gnnlm_knn_interp_grid_t* desc, void* stream);
+/* The same grid for n_lm language-model rows at once, 1 <= n_lm <= 8: desc->lm_logp is read as [n_lm, n] with row stride ld_lm
+ * (>= n) and desc->out_logp is [n_lm * G, n], G = n_ks * n_temperatures * n_lmbdas; the lm row varies slowest (row a * G + g).
+ * Replaces: one whole `fairseq-eval-lm ... --model-overrides "{'orig_prob_ratio': $alpha, ...}" --lmbda $a` per (alpha, setting)
+ * (gnnlm_scripts/wiki103/hgt_lm_wiki103_reproduce.sh:79-86,137): the kNN interpolation of fairseq/sequence_scorer.py:135 applied
+ * on top of the base-LM / GNN mixture of fairseq/models/transformer.py:1056-1062,1075-1077 (gnnlm_logp_mix) at every ratio.
+ * The exponentials, prefix sums and wave reductions of a (k', t) pair are computed once and serve every lm row; out_pknn and
+ * out_recall do not depend on the lm row and keep their shapes.  Row block a equals gnnlm_knn_interp_grid called with lm row a,
+ * bit for bit; gnnlm_knn_interp_grid is the n_lm = 1 call of this entry.  n_lm outside 1 .. 8 is GNNLM_E_INVALID. */
+int gnnlm_knn_interp_grid_lm(const gnnlm_knn_interp_grid_t* desc, int32_t n_lm, int64_t ld_lm, void* stream);
+/* out[a, i] = logsumexp(log(alphas[a]) + base_logp[i], log(1 - alphas[a]) + gnn_logp[i]) in float32, a < n_alphas <= 8: the
+ * `orig_prob_ratio` mixture of the two target log-probabilities the tied adaptive softmax gives for the base-LM feature and for
+ * the GNN output.  Replaces: TokenGraphTransformerDecoder.combinetow_probs (fairseq/models/transformer.py:1056-1062) as called
+ * by get_normalized_probs (:1075-1077) on the gathered target column, once per ratio; here one read of the two inputs serves
+ * every ratio.  The ratios are HOST data (the call neither allocates nor copies; graph-capturable, no scratch); the logs are
+ * taken in float64 and rounded to float32, as math.log lands in the reference's float32 coeffs.  alphas[a] = 0 returns gnn_logp
+ * and alphas[a] = 1 returns base_logp bit for bit (log 0 = -inf drops the term).  out is [n_alphas, n], rows contiguous.
+ * A ratio outside 0 .. 1 or n_alphas outside 1 .. 8 is GNNLM_E_INVALID and nothing is launched. */
+int gnnlm_logp_mix(const float* gnn_logp, const float* base_logp, int64_t n, const double* alphas, int32_t n_alphas, float* out,
+                   void* stream);
 /* Exact similarities: the similarity of every retrieved neighbour recomputed from its stored key in one kernel.
  * Replaces: the `ip` / `l2` branches of KNNModel.get_knn_prob's sim_func dispatch (knn/knn_model.py:161-175:
  * `self.keys[knns]` gathered on the host, then `-sum((q - key)^2)` or `sum(key * q)`, the keys divided by their norm when the
