@@ -40,7 +40,7 @@ class AdaptiveSoftmax:
             w.dim[i] = self.emb[i].shape[1]
         self._w = w
         self._ws = None
-        self.gemm_precision = 0     # 0 exact f32 MFMA | 1 bf16x3 | 2 bf16x6
+        self.gemm_precision = 0     # 0 exact f32 MFMA | 1 bf16x3 | 2 bf16x6 | 3 fp16 operands, f32 accumulate (--fp16)
 
     @classmethod
     def from_state_dict(cls, sd, cutoff, vocab, device, prefix="decoder."):

@@ -267,7 +267,7 @@ int linear_rows_windows(const GroupWindows& w, const float* A, int64_t lda, cons
 
 int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, size_t ws_bytes, hipStream_t s, const gnnlm_ragged_t* rg = nullptr) {
     GNNLM_REQUIRE(m.layers && m.n_layers >= 1, "hgt: no layers");
-    GNNLM_REQUIRE(m.gemm_precision >= 0 && m.gemm_precision <= 2, "hgt: gemm_precision must be 0, 1 or 2");
+    GNNLM_REQUIRE(m.gemm_precision >= 0 && m.gemm_precision <= 3, "hgt: gemm_precision must be 0, 1, 2 or 3");
     GemmPrecisionScope prec_scope(m.gemm_precision);
     GNNLM_REQUIRE(m.d > 0 && m.n_heads > 0 && m.d % m.n_heads == 0, "hgt: d must be divisible by n_heads");
     GNNLM_REQUIRE(io.n_blocks >= 0 && io.T >= 0 && io.kg > 0, "hgt: bad io shape");
@@ -613,7 +613,7 @@ void carve_asm(const gnnlm_adaptive_softmax_t& w, int64_t n, Carver& c, AsmBufs&
 int adaptive_impl(const gnnlm_adaptive_softmax_t& w, const float* x, int64_t ldx, const int64_t* target, int64_t n,
                   float* lm_logp, void* ws, size_t ws_bytes, hipStream_t s) {
     GNNLM_REQUIRE(w.n_bands >= 1 && w.n_bands <= 8 && w.head_w && w.d > 0 && w.d % 4 == 0, "adaptive: bad weights");
-    GNNLM_REQUIRE(w.gemm_precision >= 0 && w.gemm_precision <= 2, "adaptive: gemm_precision must be 0, 1 or 2");
+    GNNLM_REQUIRE(w.gemm_precision >= 0 && w.gemm_precision <= 3, "adaptive: gemm_precision must be 0, 1, 2 or 3");
     GemmPrecisionScope prec_scope(w.gemm_precision);
     GNNLM_REQUIRE(x && target && lm_logp, "adaptive: null io");
     if (n == 0) return OK;

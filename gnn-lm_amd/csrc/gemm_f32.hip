@@ -37,6 +37,7 @@ namespace gnnlm {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 constexpr int BK = 32, LDS_LD = BK + 4;
@@ -58,6 +59,9 @@ __device__ __forceinline__ float bf16_to_f32(unsigned h) { return __uint_as_floa
 //   operand is split while staged into NS bf16 planes (x = x0 + x1 (+ x2)) and the product is assembled from the 3 (NS=2: x0y0, x0y1, x1y0; ~2^-16 relative
 //   per product) or 6 (NS=3: adds x0y2, x1y1, x2y0; ~2^-24, i.e. f32-level) cross terms with
 //   v_mfma_f32_32x32x16_bf16, f32 accumulate.  3/16 resp. 6/16 of the f32-MFMA cycles per flop.
+// NS = 1: float16 operands (precision 3 = fp16, `eval_lm --fp16`): both operands are rounded to IEEE half by
+//   round-to-nearest-even while staged (v_cvt_pk_f16_f32 under the default rounding mode; beyond +-65504 -> +-inf, as
+//   torch.Tensor.half()), one plane, one v_mfma_f32_32x32x16_f16 per 16 k: exact products, f32 accumulate.
 template <int BM, int BN, int EPI, int NS>
 __global__ __launch_bounds__(256, 3) void gemm_nt_f32_kernel(const GemmParams p) {
     constexpr int TM = BM / 64, TN = BN / 64;            // 32x32 accumulators per wave
@@ -169,7 +173,10 @@ __global__ __launch_bounds__(256, 3) void gemm_nt_f32_kernel(const GemmParams p)
     {                                                                                        \
         char* dst_ = reinterpret_cast<char*>(lds) + (row_) * (SPLIT_LD * 4) + kq * 2;        \
         float r0_ = (v_).x, r1_ = (v_).y, r2_ = (v_).z, r3_ = (v_).w;                        \
-        if constexpr (NS == 3) {                                                             \
+        if constexpr (NS == 1) {                                                             \
+            typedef _Float16 f16x4_ __attribute__((ext_vector_type(4)));                     \
+            *reinterpret_cast<f16x4_*>(dst_) = f16x4_{(_Float16)r0_, (_Float16)r1_, (_Float16)r2_, (_Float16)r3_}; \
+        } else if constexpr (NS == 3) {                                                             \
             _Pragma("unroll") for (int pl_ = 0; pl_ < 3; ++pl_) {                            \
                 *reinterpret_cast<uint2*>(dst_ + pl_ * (PLANE * 4)) =                        \
                     make_uint2(GNNLM_PK_TRUNC(r0_, r1_), GNNLM_PK_TRUNC(r2_, r3_));          \
@@ -207,7 +214,20 @@ __global__ __launch_bounds__(256, 3) void gemm_nt_f32_kernel(const GemmParams p)
             acc[i][j] = EPI == EPI_LSE ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[PB][j], fa[PA][i], acc[i][j], 0, 0, 0)  \
                                        : __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA][i], fb[PB][j], acc[i][j], 0, 0, 0);
 #define GNNLM_COMPUTE(buf)                                                                   \
-    if constexpr (NS != 0) {                                                                 \
+    if constexpr (NS == 1) {                                                                 \
+        const char* base_ = reinterpret_cast<const char*>(lds);                              \
+        _Pragma("unroll") for (int ks_ = 0; ks_ < BK / 16; ++ks_) {                          \
+            f16x8 ha[TM], hb[TN];                                                            \
+            _Pragma("unroll") for (int i = 0; i < TM; ++i)                                   \
+                ha[i] = *reinterpret_cast<const f16x8*>(base_ + (wm * (BM / 2) + 32 * i + l32) * SPLIT_LD * 4 + 32 * ks_ + 16 * half); \
+            _Pragma("unroll") for (int j = 0; j < TN; ++j)                                   \
+                hb[j] = *reinterpret_cast<const f16x8*>(base_ + (BM + wn * (BN / 2) + 32 * j + l32) * SPLIT_LD * 4 + 32 * ks_ + 16 * half); \
+            _Pragma("unroll") for (int i = 0; i < TM; ++i)                                   \
+                _Pragma("unroll") for (int j = 0; j < TN; ++j)                               \
+                    acc[i][j] = EPI == EPI_LSE ? __builtin_amdgcn_mfma_f32_32x32x16_f16(hb[j], ha[i], acc[i][j], 0, 0, 0)  \
+                                               : __builtin_amdgcn_mfma_f32_32x32x16_f16(ha[i], hb[j], acc[i][j], 0, 0, 0); \
+        }                                                                                    \
+    } else if constexpr (NS != 0) {                                                                 \
         const char* base_ = reinterpret_cast<const char*>(lds);                              \
         _Pragma("unroll") for (int ks_ = 0; ks_ < BK / 16; ++ks_) {                          \
             bf16x8 fa[NS][TM], fb[NS][TN];                                                   \
@@ -355,6 +375,7 @@ template <int BM, int BN>
 void launch(const GemmParams& p, dim3 grid, hipStream_t stream) {
     if (p.precision == 1) launch_ns<BM, BN, 2>(p, grid, stream);
     else if (p.precision == 2) launch_ns<BM, BN, 3>(p, grid, stream);
+    else if (p.precision == 3) launch_ns<BM, BN, 1>(p, grid, stream);
     else launch_ns<BM, BN, 0>(p, grid, stream);
 }
 }  // namespace
@@ -373,7 +394,7 @@ int gemm_nt(const GemmParams& desc, hipStream_t stream) {
     GNNLM_REQUIRE(((uintptr_t)p.A % 16 == 0) && ((uintptr_t)p.W % 16 == 0), "gemm: operands must be 16-byte aligned");
     GNNLM_REQUIRE(p.sA1 % 4 == 0 && p.sA2 % 4 == 0 && p.sW1 % 4 == 0 && p.sW2 % 4 == 0, "gemm: batch strides must be multiples of 4");
     GNNLM_REQUIRE(p.batch1 >= 1 && p.batch2 >= 1, "gemm: bad batch");
-    GNNLM_REQUIRE(p.precision >= 0 && p.precision <= 2, "gemm: precision must be 0 (f32 MFMA), 1 (bf16x3) or 2 (bf16x6)");
+    GNNLM_REQUIRE(p.precision >= 0 && p.precision <= 3, "gemm: precision must be 0 (f32 MFMA), 1 (bf16x3), 2 (bf16x6) or 3 (fp16)");
     GNNLM_REQUIRE(!p.lse_part || p.batch1 * p.batch2 == 1, "gemm: the LSE epilogue does not support batches");
     GNNLM_REQUIRE(!p.lse_part || p.alpha > 0.f, "gemm: the LSE epilogue needs alpha > 0");
     GNNLM_REQUIRE(p.tile_order >= 0 && p.tile_order <= 66, "gemm: tile_order must be 0 (auto), 1 (n fastest), 2 (m fastest) or 2+GM (bands of GM m-tiles)");

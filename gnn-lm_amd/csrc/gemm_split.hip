@@ -1,5 +1,10 @@
 // Split-bf16 emulation of the f32 "NT" GEMM on the CDNA4 bf16 matrix cores, big-tile version
-// (precision 1 = bf16x3, 2 = bf16x6 of gnnlm_gemm_t; same contract and epilogues as gemm_f32.hip).
+// (precision 1 = bf16x3, 2 = bf16x6 of gnnlm_gemm_t; same contract and epilogues as gemm_f32.hip), and the float16
+// GEMM of precision 3 = fp16 through the same two kernels: ONE plane (NS = 1) holding the operand rounded to IEEE
+// half (round-to-nearest-even, beyond +-65504 -> +-inf as torch.Tensor.half()), one v_mfma_f32_32x32x16_f16 per
+// 16-k step, f32 accumulate.  A stage is then 4 steps (64 k: 32 MFMAs per wave of the 256x256 tile between two
+// barriers, the same LDS footprint as bf16x3), the MFMAs of a step issued in two halves with a wave's DMA pair of
+// the next stage between them.
 //
 // Two kernels per call:
 //
@@ -31,6 +36,7 @@ namespace gnnlm {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void glb_void_t;
 
@@ -47,6 +53,12 @@ __device__ __forceinline__ unsigned bf16_rn(float x) {
 // (NS = 2) by round-to-nearest of the value and of the residual (unbiased, 2^-18 |x| left over).
 template <int NS>
 __device__ __forceinline__ void split8(float (&v)[8], uint4 (&out)[NS]) {
+    if constexpr (NS == 1) {                             // fp16: the value itself, rounded to nearest even
+        const f16x8 h = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3],
+                         (_Float16)v[4], (_Float16)v[5], (_Float16)v[6], (_Float16)v[7]};
+        out[0] = __builtin_bit_cast(uint4, h);
+        return;
+    }
 #pragma unroll
     for (int pl = 0; pl < NS; ++pl) {
         unsigned h[8];
@@ -102,7 +114,7 @@ void gemm_planes_kernel(const GemmParams p, const uint4* __restrict__ Ap, const 
     constexpr int RB = T / 64;                           // 64-row blocks per operand per tile
     constexpr int PH = 2 * NS;                           // (plane, k half) slabs of a 16-k step
     constexpr int OPU = PH * T;                          // 16-B units per operand per 16-k step
-    constexpr int KSTEPS = NS == 2 ? 2 : 1;              // 16-k steps per stage (bf16x3: 2, so that a stage is 48 MFMAs too)
+    constexpr int KSTEPS = NS == 1 ? 4 : NS == 2 ? 2 : 1; // 16-k steps per stage (bf16x3: 2, so that a stage is 48 MFMAs too; fp16: 4 = 32 MFMAs)
     constexpr int STAGE_U = KSTEPS * 2 * OPU;            // units per stage
     static_assert(2 * RB == 2 * WAVES_N, "one (operand, row block) per wave");
     __shared__ uint4 lds[2][STAGE_U];                    // [buffer][k step][operand][plane][k half][row]
@@ -172,6 +184,17 @@ void gemm_planes_kernel(const GemmParams p, const uint4* __restrict__ Ap, const 
             acc[i][j] = EPI == EPI_LSE ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[PB][j], fa[PA][i], acc[i][j], 0, 0, 0)  \
                                        : __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA][i], fb[PB][j], acc[i][j], 0, 0, 0);
 
+    // fp16: half hf_ (of the TM accumulator rows) of step st's MFMAs; the wave's one DMA pair of step q of the NEXT stage
+    // goes out after half 2q (waves 0..n/2-1) or 2q+1 (the other waves)
+#define GNNLM_F16_HALF(hf_)                                                                  \
+    {                                                                                        \
+        _Pragma("unroll") for (int i = (hf_) * (TM / 2); i < ((hf_) + 1) * (TM / 2); ++i)    \
+            _Pragma("unroll") for (int j = 0; j < TN; ++j)                                   \
+                acc[i][j] = EPI == EPI_LSE ? __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fb[0][j]), __builtin_bit_cast(f16x8, fa[0][i]), acc[i][j], 0, 0, 0)  \
+                                           : __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[0][i]), __builtin_bit_cast(f16x8, fb[0][j]), acc[i][j], 0, 0, 0); \
+        if ((hf_) == late) GNNLM_ISSUE2(ks + KSTEPS + st, buf ^ 1, st, 0)                    \
+    }
+
     f32x16 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -182,7 +205,8 @@ void gemm_planes_kernel(const GemmParams p, const uint4* __restrict__ Ap, const 
 
 #pragma unroll
     for (int st = 0; st < KSTEPS; ++st) {
-        GNNLM_ISSUE2(st, 0, st, 0) GNNLM_ISSUE2(st, 0, st, 2)
+        GNNLM_ISSUE2(st, 0, st, 0)
+        if constexpr (NS >= 2) GNNLM_ISSUE2(st, 0, st, 2)
         if constexpr (NS == 3) GNNLM_ISSUE2(st, 0, st, 4)
     }
     __syncthreads();                                     // carries the vmcnt(0) of the DMA
@@ -198,7 +222,11 @@ void gemm_planes_kernel(const GemmParams p, const uint4* __restrict__ Ap, const 
 #pragma unroll
         for (int st = 0; st < KSTEPS; ++st) {
             bf16x8 fa[NS][TM], fb[NS][TN];
-            GNNLM_READ_A(0) GNNLM_READ_W(0) GNNLM_READ_A(1) GNNLM_READ_W(1)
+            GNNLM_READ_A(0) GNNLM_READ_W(0)
+            if constexpr (NS == 1) {
+                GNNLM_F16_HALF(0) GNNLM_F16_HALF(1)
+            } else {
+            GNNLM_READ_A(1) GNNLM_READ_W(1)
             if constexpr (NS == 3) { GNNLM_READ_A(2) GNNLM_READ_W(2) }
             GNNLM_SPLIT_MFMA(0, 0)
             GNNLM_ISSUE_SLOT(st * (NS == 3 ? 6 : 3) + 0)
@@ -213,10 +241,12 @@ void gemm_planes_kernel(const GemmParams p, const uint4* __restrict__ Ap, const 
                 GNNLM_ISSUE_SLOT(4)
                 GNNLM_SPLIT_MFMA(1, 1)
             }
+            }
         }
         __syncthreads();                                 // next stage landed; buffer `buf` is free for the one after
     }
 #undef GNNLM_SPLIT_MFMA
+#undef GNNLM_F16_HALF
 #undef GNNLM_READ_A
 #undef GNNLM_READ_W
 #undef GNNLM_ISSUE_SLOT
@@ -274,14 +304,15 @@ bool gemm_split_eligible(const GemmParams& p) {
 // p is normalised by gemm_nt (alpha, batch, tile_order resolved)
 int gemm_nt_split(const GemmParams& p_in, hipStream_t stream) {
     GemmParams p = p_in;
-    const int NS = p.precision == 1 ? 2 : 3;
+    const int NS = p.precision == 3 ? 1 : p.precision == 1 ? 2 : 3;      // planes: fp16 one (the rounded value), bf16x3 two, bf16x6 three
     // 256x256 tiles when they still give every CU >= 2 workgroups over the launch.  A device-side M is a small fraction of its bound
     // where the bound is a token count (the softmax tails: 128-tiles), and of the order of the bound where it counts the slot rows
     // of a batch's context groups (ABI 9: the ntgt projections of a multi-layer step, M >= 2^17 -- merged groups are a good
     // third of all groups or more): those keep the big tiles (round 5: 22.2 k -> 25 k tokens/s on the 3-layer recipe under bf16x3)
     const bool big = (!p.m_dev || p.M >= (1 << 17)) && cdiv(p.M, 256) * cdiv(p.N, 256) >= 512;
     const int T = big ? 256 : 128;
-    const int KS = (int)cdiv(p.K, SK * 2) * 2;           // 16-k steps, zero-padded to a whole number of stages
+    const int KPAD = NS == 1 ? 4 : 2;                    // 16-k steps per stage of the widest kernel variant of this precision
+    const int KS = (int)cdiv(p.K, SK * KPAD) * KPAD;     // 16-k steps, zero-padded to a whole number of stages
     const int64_t rbA = cdiv(p.M, T) * (T / 64), rbW = cdiv(p.N, T) * (T / 64);
     const size_t unit_bytes = 16, per_rb = (size_t)KS * NS * 2 * 64 * unit_bytes;
     void* ws = nullptr;
@@ -291,7 +322,10 @@ int gemm_nt_split(const GemmParams& p_in, hipStream_t stream) {
     uint4* Wp = Ap + (size_t)rbA * per_rb / unit_bytes;
     {
         ProfScope prof(K_SPLIT, stream, 0.0, (4.0 + 2.0 * NS) * ((double)p.M + (double)p.N) * p.K);
-        if (NS == 2) {
+        if (NS == 1) {
+            launch_split<1>(p.A, p.lda, p.a_rows, p.M, p.m_dev, p.K, KS, (int)rbA, Ap, stream);
+            launch_split<1>(p.W, p.ldw, nullptr, p.N, nullptr, p.K, KS, (int)rbW, Wp, stream);
+        } else if (NS == 2) {
             launch_split<2>(p.A, p.lda, p.a_rows, p.M, p.m_dev, p.K, KS, (int)rbA, Ap, stream);
             launch_split<2>(p.W, p.ldw, nullptr, p.N, nullptr, p.K, KS, (int)rbW, Wp, stream);
         } else {
@@ -306,8 +340,8 @@ int gemm_nt_split(const GemmParams& p_in, hipStream_t stream) {
     const double work = 2.0 * p.M * (double)p.N * p.K;
     ProfScope prof(K_GEMM, stream, work, 4.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N), p.m_dev, (double)p.M, true);
     if (prof.slot) p.m_out = prof.slot;
-    if (big) { if (NS == 2) launch_planes<256, 2>(p, Ap, Wp, KS, grid, stream); else launch_planes<256, 3>(p, Ap, Wp, KS, grid, stream); }
-    else     { if (NS == 2) launch_planes<128, 2>(p, Ap, Wp, KS, grid, stream); else launch_planes<128, 3>(p, Ap, Wp, KS, grid, stream); }
+    if (big) { if (NS == 1) launch_planes<256, 1>(p, Ap, Wp, KS, grid, stream); else if (NS == 2) launch_planes<256, 2>(p, Ap, Wp, KS, grid, stream); else launch_planes<256, 3>(p, Ap, Wp, KS, grid, stream); }
+    else     { if (NS == 1) launch_planes<128, 1>(p, Ap, Wp, KS, grid, stream); else if (NS == 2) launch_planes<128, 2>(p, Ap, Wp, KS, grid, stream); else launch_planes<128, 3>(p, Ap, Wp, KS, grid, stream); }
     GNNLM_LAUNCH_CHECK();
     return OK;
 }

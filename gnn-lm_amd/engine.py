@@ -43,12 +43,25 @@ class BlockBatch:
 
 class GnnLmEngine:
     def __init__(self, hgt: HGT, asm: AdaptiveSoftmax, store: CodeStore, left: int, right: int,
-                 max_intra_context: int = 0, fetcher=None, fetch_vals: bool = False):
+                 max_intra_context: int = 0, fetcher=None, fetch_vals: bool = False, precision=None):
         self.hgt, self.asm, self.store = hgt, asm, store
+        if precision is not None:                    # None: whatever hgt / asm already carry
+            self.precision = precision
         self.left, self.right, self.max_intra_context = left, right, max_intra_context
         # range-sharded store (dist.ShardedFetcher): the code rows -- and, with fetch_vals, the labels of the kNN ids -- are
         # fetched from their owners inside the step (batches that bring their own fetched_* / knn_vals keep them)
         self.fetcher, self.fetch_vals = fetcher, fetch_vals
+
+    @property
+    def precision(self) -> str:
+        """Arithmetic of the GEMMs of the HGT and of the adaptive softmax, a name of ``ops.PRECISIONS``: "f32" (default), "fp16"
+        (what ``eval_lm --fp16`` sets: float16 operands rounded to nearest even, f32 accumulation; everything else stays f32),
+        "bf16x3" / "bf16x6".  Setting it sets both modules; cached centre states of another precision are dropped (hgt.py)."""
+        return ops.precision_name(self.hgt.gemm_precision, self.asm.gemm_precision)
+
+    @precision.setter
+    def precision(self, value):
+        self.hgt.gemm_precision = self.asm.gemm_precision = ops.precision_value(value)
 
     def features(self, batch: BlockBatch) -> torch.Tensor:
         """gcn_feat: HGT output for every token [n_blocks*T, d] (transformer.py:997)."""

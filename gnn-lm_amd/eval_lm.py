@@ -496,8 +496,6 @@ def main(args, tables=None, model=None):
         # LMContextWindowDataset (fairseq/data/lm_context_window_dataset.py) prepends context tokens and scores only the
         # new ones; shrinking the block without the prefix would silently give another ppl
         raise NotImplementedError("--context-window > 0 is not built (the GNN-LM recipes use --gcn-context-window)")
-    if args.fp16:
-        logger.warning("--fp16 ignored: the HIP path computes in float32")
     # ---- one process per GPU (torch.distributed.run): token blocks are data parallel, the code table is range-sharded
     # (the reference has no multi-GPU eval path to mirror beyond --num-shards, fairseq_cli/eval_lm.py:131-132)
     dist = torch.distributed
@@ -536,6 +534,14 @@ def main(args, tables=None, model=None):
         model, margs = GnnLmModel.from_checkpoint(args.path, device, overrides, vocab_size=tabs["vocab"])
     # a sweep over the ratio runs the base branch even when the run's own ratio is 0 (the model leaves both unmixed rows per batch)
     model.keep_branches = bool(sweep and len(sweep) > 3)
+    if args.fp16:
+        # the reference's model.half() (fairseq_cli/eval_lm.py:114-115).  Here: the GEMMs of the graph decoder and of the adaptive
+        # softmax take their operands rounded to float16 and accumulate in f32; attention, LayerNorm, the kNN search and the
+        # interpolation stay f32, as does every tensor in memory -- never narrower than what the flag asks for.  Per rank.
+        model.precision = "fp16"
+        logger.info("--fp16: float16 matrix-core GEMMs with float32 accumulation (graph decoder and adaptive softmax); "
+                    "attention, LayerNorm, kNN search and interpolation stay float32")
+    precision = model.precision if hasattr(model, "precision") else "f32"
     fetcher = None
     if shard is None:
         store = model.make_store(tabs["codes"], tabs["n_store"], device)
@@ -867,7 +873,7 @@ def main(args, tables=None, model=None):
     res = {"score_sum": score_sum, "count": count, "ppl": 2 ** avg_nll_loss, "tokens": ntok, "seconds": gen_time,
             "wall_seconds": wall, "word_stats": word_stats if args.output_word_stats else None,
             "score_sum_f32_order": float(score_sum_f32), "rank": rank, "world": world, "store": store_mode, "rank_score_sum": rank_score_sum, "rank_tokens": rank_tokens,
-            "xgmi_bytes": link_bytes}
+            "xgmi_bytes": link_bytes, "precision": precision}
     if sweep:
         res["sweep"] = sweep_rows
     if getattr(args, "result_json", None):

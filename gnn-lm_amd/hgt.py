@@ -298,7 +298,7 @@ class HGT(nn.Module):
         if hidden_dim != out_dim:
             self.out = nn.Linear(hidden_dim, out_dim)
         self._prepared = self._plist = None
-        self.gemm_precision = 0     # 0 exact f32 MFMA | 1 bf16x3 | 2 bf16x6 (opt-in split-bf16 emulation)
+        self.gemm_precision = 0     # 0 exact f32 MFMA | 1 bf16x3 | 2 bf16x6 (opt-in split-bf16 emulation) | 3 fp16 operands, f32 accumulate (--fp16)
         self.dedup_groups = os.environ.get("GNNLM_DEDUP", "1") != "0"      # merge equal context groups of a batch (multi-layer models)
         self.dedup_rows = os.environ.get("GNNLM_DEDUP_ROWS", "1") != "0"   # ... and project layer 0's K / V once per distinct datastore ROW (ABI 11)
         self._last_groups = None                                             # (groups of the last batch, device counter of the computed ones)

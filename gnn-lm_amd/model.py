@@ -24,7 +24,7 @@ class GnnLmModel(torch.nn.Module):
     orig_prob_ratio, keep_branches, short_cut = 0.0, False, False
 
     def __init__(self, hgt: HGT, asm: AdaptiveSoftmax, quantizer: TorchPQCodec = None, orig_prob_ratio: float = 0.0,
-                 short_cut: bool = False):
+                 short_cut: bool = False, precision=None):
         super().__init__()
         # orig_prob_ratio = alpha > 0 (transformer.py:987-1005,1056-1062,1075-1077): every token is scored with
         #   logsumexp(log(alpha) + log p_asm(target | h), log(1 - alpha) + log p_asm(target | x))
@@ -42,6 +42,23 @@ class GnnLmModel(torch.nn.Module):
         # `eval_lm --graph-capture`: the launches of forward() and of target_log_probs() replayed from HIP graphs, one pair per
         # batch shape (the recipe's literal one-block batches are launch-bound: ~45 launches for 0.2 ms of GPU work)
         self.graph_capture = False
+        if precision is not None:          # a name of ops.PRECISIONS ("fp16": what `eval_lm --fp16` sets); None: as hgt / asm carry
+            self.precision = precision
+
+    @property
+    def precision(self) -> str:
+        """Arithmetic of the GEMMs of the graph decoder and of the adaptive softmax (see ``GnnLmEngine.precision``)."""
+        from . import ops
+        mods = [m for m in (self.hgt_decoder, self.adaptive_softmax) if m is not None]
+        return ops.precision_name(*(m.gemm_precision for m in mods))
+
+    @precision.setter
+    def precision(self, value):
+        from . import ops
+        v = ops.precision_value(value)
+        for m in (self.hgt_decoder, self.adaptive_softmax):
+            if m is not None:
+                m.gemm_precision = v
 
     def eval(self):
         return self
@@ -61,6 +78,7 @@ class GnnLmModel(torch.nn.Module):
         graph's static buffers -- valid until the next call of this shape (the scorer consumes them at once)."""
         import dataclasses
         key = ("fwd", tuple(src_tokens.shape), tuple(graph.ids.shape), graph.tgt_h.dtype, graph.left, graph.right, graph.max_intra_context,
+               self.precision,                                                      # (a captured launch has its arithmetic baked in)
                id(graph.store), graph.store.codes.data_ptr(), _lib_raw_stream())      # (one set of static buffers per stream)
         if self._graphs is None:
             self._graphs, self._static_x = {}, set()

@@ -31,7 +31,23 @@ def _dtype(t, dt, what):
         raise TypeError(f"{what}: expected {dt}, got {t.dtype}")
 
 
-PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x6": 2}
+# "fp16" (`eval_lm --fp16`): both GEMM operands rounded to IEEE float16 (nearest even; beyond +-65504 -> +-inf as Tensor.half()),
+# exact products, f32 accumulation, f32 epilogues and f32 tensors -- never narrower than the reference's model.half()
+PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x6": 2, "fp16": 3}
+
+
+def precision_value(p):
+    """A name of PRECISIONS or its value -> the value of the C ABI's ``precision`` fields."""
+    v = PRECISIONS.get(p, p)
+    if v not in PRECISIONS.values() or isinstance(v, bool):
+        raise ValueError(f"precision: one of {sorted(PRECISIONS)} (or its value), got {p!r}")
+    return int(v)
+
+
+def precision_name(*values):
+    """The name of the precision the given ``gemm_precision`` values share ("mixed" if they differ)."""
+    names = {v: k for k, v in PRECISIONS.items()}
+    return names[values[0]] if len(set(values)) == 1 else "mixed"
 
 
 def gemm_nt(A, W, bias=None, residual=None, alpha=1.0, out=None, bias_mode=1, gate=None,
