@@ -117,6 +117,9 @@ def lib():
         L.gnnlm_enable_peer_access.argtypes = [i32]
         L.gnnlm_adaptive_workspace_bytes.argtypes = [vp, i64]
         L.gnnlm_adaptive_target_logp.argtypes = [vp, vp, i64, vp, i64, vp, vp, ctypes.c_size_t, vp]
+        for nm in ("gnnlm_dense_workspace_bytes", "gnnlm_dense_workspace_bytes_min"):
+            getattr(L, nm).restype, getattr(L, nm).argtypes = ctypes.c_size_t, [vp, i64]
+        L.gnnlm_dense_target_logp.argtypes = [vp, vp, i64, vp, i64, vp, vp, ctypes.c_size_t, vp]
         L.gnnlm_masked_sum_f64.argtypes = [vp, vp, i64, vp, vp]
         L.gnnlm_rows_sum_f64.argtypes = [vp, i64, i64, i64, vp, vp]
         L.gnnlm_knn_interp_grid_lm.argtypes = [vp, i32, i64, vp]

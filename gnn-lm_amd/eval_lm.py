@@ -542,6 +542,11 @@ def main(args, tables=None, model=None):
         logger.info("--fp16: float16 matrix-core GEMMs with float32 accumulation (graph decoder and adaptive softmax); "
                     "attention, LayerNorm, kNN search and interpolation stay float32")
     precision = model.precision if hasattr(model, "precision") else "f32"
+    head_mod = getattr(model, "adaptive_softmax", None)
+    head = "dense" if type(head_mod).__name__ == "DenseSoftmax" else "adaptive"
+    if head == "dense":     # a `--arch transformer_lm` checkpoint (enwik8): output_layer + log_softmax (transformer.py:843-852,1081-1085)
+        logger.info("output layer: dense softmax, V = %d, bias %s, route %s", head_mod.vocab, "yes" if head_mod.bias is not None else "no",
+                    head_mod.route_name())
     fetcher = None
     if shard is None:
         store = model.make_store(tabs["codes"], tabs["n_store"], device)
@@ -873,7 +878,7 @@ def main(args, tables=None, model=None):
     res = {"score_sum": score_sum, "count": count, "ppl": 2 ** avg_nll_loss, "tokens": ntok, "seconds": gen_time,
             "wall_seconds": wall, "word_stats": word_stats if args.output_word_stats else None,
             "score_sum_f32_order": float(score_sum_f32), "rank": rank, "world": world, "store": store_mode, "rank_score_sum": rank_score_sum, "rank_tokens": rank_tokens,
-            "xgmi_bytes": link_bytes, "precision": precision}
+            "xgmi_bytes": link_bytes, "precision": precision, "head": head}
     if sweep:
         res["sweep"] = sweep_rows
     if getattr(args, "result_json", None):

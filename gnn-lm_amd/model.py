@@ -1,19 +1,23 @@
 """``GnnLmModel`` -- the eval-path behaviour of ``TransformerLanguageModel`` with a
 ``TokenGraphTransformerDecoder`` (fairseq/models/transformer.py:910-1085) under
 ``--use-precompute-feat``: the base LM is bypassed (:974-976), the graph decoder (HGT) refines the
-precomputed features, and the tied adaptive softmax scores the targets.
+precomputed features, and the output layer scores the targets: the tied adaptive softmax, or -- for a checkpoint without one
+(``--arch transformer_lm``: enwik8) -- the plain softmax over ``embed_tokens.weight | embed_out [+ xl_bias]`` (``DenseSoftmax``).
 
 State-dict names follow the reference (prefix ``decoder.``): ``hgt_decoder.gcs.*``,
 ``tgt_quantizer.*`` (convert_ckpt.py:40-45), ``embed_tokens.embeddings.{i}.{0,1}.weight``,
-``adaptive_softmax.head.class_proj.weight``.
+``adaptive_softmax.head.class_proj.weight``; dense head: ``embed_tokens.weight`` / ``embed_out``,
+``xl_bias``.
 """
 import os
 from argparse import Namespace
+from typing import Union
 
 import torch
 
 from ._lib import raw_stream as _lib_raw_stream
 from .adaptive_softmax import AdaptiveSoftmax
+from .dense_softmax import DenseSoftmax
 from .hgt import HGT, CodeStore, NeighborGraph
 from .pq_wrapper import TorchPQCodec
 
@@ -23,12 +27,13 @@ class GnnLmModel(torch.nn.Module):
     _graphs, _static_x = None, frozenset()
     orig_prob_ratio, keep_branches, short_cut = 0.0, False, False
 
-    def __init__(self, hgt: HGT, asm: AdaptiveSoftmax, quantizer: TorchPQCodec = None, orig_prob_ratio: float = 0.0,
+    def __init__(self, hgt: HGT, asm: Union[AdaptiveSoftmax, DenseSoftmax], quantizer: TorchPQCodec = None, orig_prob_ratio: float = 0.0,
                  short_cut: bool = False, precision=None):
         super().__init__()
         # orig_prob_ratio = alpha > 0 (transformer.py:987-1005,1056-1062,1075-1077): every token is scored with
         #   logsumexp(log(alpha) + log p_asm(target | h), log(1 - alpha) + log p_asm(target | x))
-        # h the base LM's feature, x the GNN output, both through the same tied adaptive softmax.  Under --use-precompute-feat h is
+        # h the base LM's feature, x the GNN output, both through the same head (`asm`: the tied adaptive softmax, or the dense
+        # softmax, where the reference mixes the two softmaxes in probability space, :990-991,1002 -- the same target column).  Under --use-precompute-feat h is
         # graph.tgt_h, which the step already holds: no base LM is involved.  alpha <= 0 is off (the reference tests `> 0`);
         # alpha >= 1 is where the reference's math.log(1 - p1_coeff) raises ValueError("math domain error")
         if orig_prob_ratio >= 1:
@@ -238,6 +243,13 @@ class GnnLmModel(torch.nn.Module):
             else:
                 raise ValueError("no quantizer: the checkpoint has no decoder.tgt_quantizer.* buffers "
                                  "(fairseq_cli/convert_ckpt.py) and quantizer_path does not name a file")
+        if getattr(args, "adaptive_softmax_cutoff", None) is None or "decoder.adaptive_softmax.head.class_proj.weight" not in sd:
+            # no adaptive softmax (transformer.py:845): the plain output layer of a `--arch transformer_lm` checkpoint
+            asm = DenseSoftmax.from_state_dict(sd, args, device)
+            if vocab_size is not None and int(vocab_size) != asm.vocab:
+                raise ValueError(f"vocabulary mismatch: the dictionary has {int(vocab_size)} entries, the checkpoint's output layer "
+                                 f"has {asm.vocab} rows")
+            return cls(hgt, asm, quantizer, getattr(args, "orig_prob_ratio", 0.0), getattr(args, "short_cut", False)), args
         cut = [int(c) for c in str(args.adaptive_softmax_cutoff).split(",")]
         if vocab_size is None:
             n_bands = sd["decoder.adaptive_softmax.head.class_proj.weight"].shape[0] + 1

@@ -261,6 +261,34 @@ int gnnlm_adaptive_target_logp(const gnnlm_adaptive_softmax_t* w, const float* x
                                const int64_t* target, int64_t n, float* lm_logp,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* Plain (non-adaptive) output layer, target log-probability only.  Additive to ABI 12: a new struct and new entries.
+ * Replaces: TransformerDecoder.output_layer with adaptive_softmax None (fairseq/models/transformer.py:843-852),
+ *           get_normalized_probs' log_softmax (:1081-1085) + gather_target_probs (fairseq/sequence_scorer.py:48-53,89).
+ *   lm_logp[r] = (x[r] . w[t]^T + bias[t]) - log sum_v exp(x[r] . w[v]^T + bias[v]),  t = target[r];  a target outside
+ *   [0, vocab) gives -INFINITY and nothing out of bounds is read.
+ * Routes: 1 = one launch (csrc/dense_logp.hip): a workgroup owns 32 rows and the whole vocabulary, no logit or partial reaches
+ * memory, no workspace; vocab <= 512 and gemm_precision 0 or 3 only (at precision 0 the logits are those of gnnlm_gemm_nt bit for
+ * bit).  2 = the general route, any vocab and precision: without a bias gnnlm_gemm_nt's log-sum-exp epilogue + gnnlm_lse_reduce;
+ * with a bias the logits of a chunk of rows go through the workspace (gnnlm_gemm_nt with bias_mode 1 + gnnlm_row_lse_pick).
+ * 0 = auto: route 1 for vocab <= 384 at gemm_precision 3, where it measured faster on the bias-free problem, else route 2.
+ * gnnlm_dense_workspace_bytes sizes the workspace for chunks of at most 64 MiB of logits (0 on route 1);
+ * gnnlm_dense_workspace_bytes_min is the least the call accepts (128-row chunks) -- in between, a chunk holds the multiple of
+ * 128 rows that fits.  x and w are 16-byte aligned with ldx % 4 == 0, ldw % 4 == 0.  A bad d, vocab, precision or route, a null w
+ * or a workspace that is too small is GNNLM_E_INVALID before anything is launched or any pointer is followed.  The call only
+ * enqueues on `stream`: no allocation, no synchronisation (graph-capturable). */
+typedef struct gnnlm_dense_softmax {
+    int32_t d, vocab;          /* d % 4 == 0, vocab >= 1 */
+    int32_t gemm_precision, route;
+                               /* gemm_precision: as gnnlm_gemm_t.precision (0 f32, 1 / 2 split-bf16, 3 fp16 operands);
+                                  route: 0 auto; 1 the one-launch kernel (vocab <= 512 and precision 0 or 3, else invalid); 2 the general route */
+    const float* w;  int64_t ldw;   /* [vocab, d]: embed_tokens.weight or embed_out */
+    const float* bias;         /* optional [vocab]: xl_bias; added in f32 and never rounded, under every precision */
+} gnnlm_dense_softmax_t;
+size_t gnnlm_dense_workspace_bytes(const gnnlm_dense_softmax_t* w, int64_t n);
+size_t gnnlm_dense_workspace_bytes_min(const gnnlm_dense_softmax_t* w, int64_t n);
+int gnnlm_dense_target_logp(const gnnlm_dense_softmax_t* w, const float* x, int64_t ldx, const int64_t* target,
+                            int64_t n, float* lm_logp, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * kNN-LM distance-softmax + interpolation
  * (KNNModel.get_knn_prob knn/knn_model.py:192-217; SequenceScorer fairseq/sequence_scorer.py:55-68,110,121).
