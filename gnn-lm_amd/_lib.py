@@ -127,6 +127,7 @@ def lib():
         L.gnnlm_ivfpq_pack_codes.argtypes = [vp, i64, i32, vp, vp]
         L.gnnlm_ivfpq_pack_lut.argtypes = [vp, i64, i64, i32, vp, vp]
         L.gnnlm_ivfpq_pack_tiles.argtypes = [vp, i64, i32, vp, vp]
+        L.gnnlm_ivfpq_key_terms.argtypes = [vp, vp, i64, i32, vp, vp, i32, i32, vp, vp]
         L.gnnlm_ivfpq_quantize_lut.argtypes = [vp, i64, i64, i32, vp, vp, vp]
         L.gnnlm_ivfpq_build_groups.argtypes = [vp, i64, i64, i32, i32, i64, vp, vp, vp, vp, vp, vp]
         L.gnnlm_label_tags.argtypes = [vp, i32, i64, vp, vp]

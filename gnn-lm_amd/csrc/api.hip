@@ -789,6 +789,10 @@ int gnnlm_ivfpq_pack_codes(const uint8_t* codes, int64_t N, int32_t M, uint8_t* 
 int gnnlm_ivfpq_pack_lut(const float* lut, int64_t ld_lut, int64_t n, int32_t M, float* out, void* stream) {
     return ivfpq_pack_lut(lut, ld_lut, n, M, out, (hipStream_t)stream);
 }
+int gnnlm_ivfpq_key_terms(const uint8_t* list_codes, const int64_t* list_off, int64_t N, int32_t nlist, const float* coarse, const float* pq,
+                          int32_t M, int32_t dsub, float* key_term, void* stream) {
+    return ivfpq_key_terms(list_codes, list_off, N, nlist, coarse, pq, M, dsub, key_term, (hipStream_t)stream);
+}
 int gnnlm_ivfpq_pack_tiles(const uint8_t* codes, int64_t N, int32_t M, uint8_t* out, void* stream) {
     return ivfpq_pack_tiles(codes, N, M, out, (hipStream_t)stream);
 }

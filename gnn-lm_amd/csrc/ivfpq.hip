@@ -12,6 +12,9 @@
 namespace gnnlm {
 namespace {
 
+// KEY: the L2 metric with one term per KEY (gnnlm_ivfpq_scan_t::key_term): the tables stay the query's own and the score of row r is
+// bias + 2 S - key_term[r], S the table sum below.  A template parameter, so the inner-product kernel is the code it was.
+template <bool KEY>
 __global__ __launch_bounds__(256) void ivfpq_scan_kernel(gnnlm_ivfpq_scan_t p) {
     extern __shared__ __attribute__((aligned(16))) float lut[];            // [M][256]
     const int tid = threadIdx.x;
@@ -35,7 +38,7 @@ __global__ __launch_bounds__(256) void ivfpq_scan_kernel(gnnlm_ivfpq_scan_t p) {
     {   // the query's table -> LDS (coalesced 16-B pieces); L2 metric: 2 <q'_m, p_mc> - (|p_mc|^2 + 2 <c_l,m, p_mc>) per entry
         const float4* src = reinterpret_cast<const float4*>(p.lut + (int64_t)q * p.ld_lut);
         float4* dst = reinterpret_cast<float4*>(lut);
-        if (p.list_term) {
+        if (!KEY && p.list_term) {
             const float4* lt = reinterpret_cast<const float4*>(p.list_term + list * p.ld_list_term);
             for (int e = tid; e < M * 64; e += 256) {
                 const float4 a = src[e], b = lt[e];
@@ -63,7 +66,9 @@ __global__ __launch_bounds__(256) void ivfpq_scan_kernel(gnnlm_ivfpq_scan_t p) {
                 s3 += t[(4 * u + 3) * 256 + (w[u] >> 24)];
             }
         }
-        const float s = bias + ((s0 + s1) + (s2 + s3));
+        float s;
+        if constexpr (KEY) s = fmaf(2.f, (s0 + s1) + (s2 + s3), bias) - p.key_term[lo + j];
+        else s = bias + ((s0 + s1) + (s2 + s3));
         if (!p.tau) {
             if (j < p.seg) { oval[j] = s; if (oid) oid[j] = p.ids[lo + j]; }
         } else if (s > tau) {
@@ -98,7 +103,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int STAGE_CAP = 1024;
 constexpr int STAGE_BYTES = 16 + 2 * STAGE_CAP * 8;
-template <int M, int WHICH>    // 0: query 0 only, 1: query 1 only, 2: both (same list)
+template <int M, int WHICH, bool KEY>    // 0: query 0 only, 1: query 1 only, 2: both (same list); KEY: L2 with a per-key term (see ivfpq_scan_kernel)
 __device__ __forceinline__ void scan_rot(const gnnlm_ivfpq_scan_t& p, const char* lut, int* stage, int64_t lo, int64_t len, int tid,
                                          int q0, int slot0, int q1, int slot1) {
     constexpr int NT = 1024, NW = NT / 64;
@@ -159,6 +164,10 @@ __device__ __forceinline__ void scan_rot(const gnnlm_ivfpq_scan_t& p, const char
     for (int64_t b = b_first; b < b_end; b += NW) {
         const int64_t bn = min(b + NW, b_end - 1);      // the next block of this wave (last: re-read)
         f32x2 acc[2] = {{0.f, 0.f}, {0.f, 0.f}};
+        float kt = 0.f;                                 // KEY: the row's term travels under the look-ups; one load serves both queries
+        if constexpr (KEY) {
+            if (b * 64 + lane >= lo && b * 64 + lane < hi) kt = p.key_term[b * 64 + lane];
+        }
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
             // 32 look-ups, eight reads in flight: v_perm_b32 builds the address in the low register of the pair the read
@@ -305,6 +314,12 @@ __device__ __forceinline__ void scan_rot(const gnnlm_ivfpq_scan_t& p, const char
         }
         const f32x2 sum = acc[0] + acc[1];
         const int64_t r = b * 64 + lane;
+        float sc0, sc1;
+        if constexpr (KEY) {
+            sc0 = fmaf(2.f, sum.x, bias0) - kt; sc1 = fmaf(2.f, sum.y, bias1) - kt;
+        } else {
+            sc0 = bias0 + sum.x; sc1 = bias1 + sum.y;
+        }
 #if GNNLM_IVF_EXP & 4
         if (sum.x != 1234.5f) continue;
 #endif
@@ -312,8 +327,8 @@ __device__ __forceinline__ void scan_rot(const gnnlm_ivfpq_scan_t& p, const char
         const int64_t j = r - lo;
         if (!p.tau) {
             if (j < p.seg) {
-                if (WHICH != 1) ov0[j] = bias0 + sum.x;
-                if (WHICH != 0) ov1[j] = bias1 + sum.y;
+                if (WHICH != 1) ov0[j] = sc0;
+                if (WHICH != 0) ov1[j] = sc1;
                 if (p.out_id) {
                     const int64_t id = p.ids[r];
                     if (WHICH != 1) oi0[j] = id;
@@ -321,20 +336,20 @@ __device__ __forceinline__ void scan_rot(const gnnlm_ivfpq_scan_t& p, const char
                 }
             }
         } else {
-            if (WHICH != 1 && bias0 + sum.x > tau0) {
+            if (WHICH != 1 && sc0 > tau0) {
                 const int pos = atomicAdd(&scnt[0], 1);
-                if (pos < STAGE_CAP) sbuf[pos] = float2{bias0 + sum.x, __int_as_float((int)j)};
+                if (pos < STAGE_CAP) sbuf[pos] = float2{sc0, __int_as_float((int)j)};
                 else {                                              // staging full: straight to the candidate rows
                     const int gp = atomicAdd(&p.cand_cnt[q0], 1);
-                    if (gp < p.cap) { p.cand_val[(int64_t)q0 * p.cap + gp] = bias0 + sum.x; p.cand_id[(int64_t)q0 * p.cap + gp] = p.ids[r]; }
+                    if (gp < p.cap) { p.cand_val[(int64_t)q0 * p.cap + gp] = sc0; p.cand_id[(int64_t)q0 * p.cap + gp] = p.ids[r]; }
                 }
             }
-            if (WHICH != 0 && bias1 + sum.y > tau1) {
+            if (WHICH != 0 && sc1 > tau1) {
                 const int pos = atomicAdd(&scnt[1], 1);
-                if (pos < STAGE_CAP) sbuf[STAGE_CAP + pos] = float2{bias1 + sum.y, __int_as_float((int)j)};
+                if (pos < STAGE_CAP) sbuf[STAGE_CAP + pos] = float2{sc1, __int_as_float((int)j)};
                 else {
                     const int gp = atomicAdd(&p.cand_cnt[q1], 1);
-                    if (gp < p.cap) { p.cand_val[(int64_t)q1 * p.cap + gp] = bias1 + sum.y; p.cand_id[(int64_t)q1 * p.cap + gp] = p.ids[r]; }
+                    if (gp < p.cap) { p.cand_val[(int64_t)q1 * p.cap + gp] = sc1; p.cand_id[(int64_t)q1 * p.cap + gp] = p.ids[r]; }
                 }
             }
         }
@@ -363,7 +378,7 @@ __device__ __forceinline__ void scan_rot(const gnnlm_ivfpq_scan_t& p, const char
     }
 }
 
-template <int M>
+template <int M, bool KEY>
 __global__ __launch_bounds__(1024) void ivfpq_scan_rot_kernel(gnnlm_ivfpq_scan_t p, int64_t n_pairs, int pairs_per_xcd) {
     extern __shared__ __attribute__((aligned(16))) float lut_raw[];
     f32x2* lut = reinterpret_cast<f32x2*>(lut_raw);                       // [M/32][256][32] (query 0, query 1)
@@ -398,10 +413,10 @@ __global__ __launch_bounds__(1024) void ivfpq_scan_rot_kernel(gnnlm_ivfpq_scan_t
     int* stage = reinterpret_cast<int*>(lut_raw + M * 256 * 2);          // behind the tables: 16 B + 2 x STAGE_CAP x 8 B
     if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)lut_raw != 0u) __builtin_trap();   // look-up addresses are absolute
     if (two && la == lb) {
-        scan_rot<M, 2>(p, lc, stage, loa, lena, tid, q0, slot0, q1, slot1);
+        scan_rot<M, 2, KEY>(p, lc, stage, loa, lena, tid, q0, slot0, q1, slot1);
     } else {
-        scan_rot<M, 0>(p, lc, stage, loa, lena, tid, q0, slot0, q1, slot1);
-        if (two) scan_rot<M, 1>(p, lc, stage, lob, lenb, tid, q0, slot0, q1, slot1);
+        scan_rot<M, 0, KEY>(p, lc, stage, loa, lena, tid, q0, slot0, q1, slot1);
+        if (two) scan_rot<M, 1, KEY>(p, lc, stage, lob, lenb, tid, q0, slot0, q1, slot1);
     }
 }
 
@@ -437,7 +452,58 @@ __global__ __launch_bounds__(256) void ivfpq_pack_lut_kernel(const float* __rest
     for (int e = tid; e < 32 * 256; e += 256) dst[e] = tile[e & 31][e >> 5];
 }
 
+// key_term[r] = sum_m (|p_m,c|^2 + 2 <c_l,m, p_m,c>), c = code_m(r), l = the list of row r: what the L2 score of a key with residual
+// codes adds to 2 sum_m <q'_m, p_m,c> - |q' - c_l|^2 whatever the query is (= |x^|^2 - |c_l|^2 of the reconstruction x^, summed term
+// by term: no cancellation).  One thread per row: its list by binary search in list_off (empty lists are stepped over), then M
+// centroid rows of dsub floats (the 256 M of them stay in L2) against the list's coarse centroid, accumulated in float64 in
+// ascending (m, e) order and rounded once.  Runs once per index.
+__global__ __launch_bounds__(256) void ivfpq_key_terms_kernel(const uint8_t* __restrict__ codes, const int64_t* __restrict__ list_off, int nlist,
+                                                               const float* __restrict__ coarse, const float* __restrict__ pq, int64_t N, int M,
+                                                               int dsub, float* __restrict__ out) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= N) return;
+    int a = 0, b = nlist - 1;                           // the smallest l with list_off[l + 1] > r
+    while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (list_off[mid + 1] > r) b = mid; else a = mid + 1;
+    }
+    const float* cen = coarse + (int64_t)a * M * dsub;
+    const uint4* crow = reinterpret_cast<const uint4*>(codes + r * M);
+    double acc = 0.0;
+    for (int c16 = 0; c16 < M / 16; ++c16) {
+        const uint4 v = crow[c16];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int m = c16 * 16 + u;
+            const uint32_t code = (w[u >> 2] >> (8 * (u & 3))) & 255u;
+            const float4* pv = reinterpret_cast<const float4*>(pq + ((int64_t)m * 256 + code) * dsub);
+            const float4* cv = reinterpret_cast<const float4*>(cen + m * dsub);
+            for (int e = 0; e < dsub / 4; ++e) {
+                const float4 x = pv[e], c = cv[e];
+                acc += (double)x.x * x.x + 2.0 * ((double)c.x * x.x);
+                acc += (double)x.y * x.y + 2.0 * ((double)c.y * x.y);
+                acc += (double)x.z * x.z + 2.0 * ((double)c.z * x.z);
+                acc += (double)x.w * x.w + 2.0 * ((double)c.w * x.w);
+            }
+        }
+    }
+    out[r] = (float)acc;
+}
+
 }  // namespace
+
+int ivfpq_key_terms(const uint8_t* codes, const int64_t* list_off, int64_t N, int nlist, const float* coarse, const float* pq, int M, int dsub,
+                    float* out, hipStream_t stream) {
+    GNNLM_REQUIRE(N >= 0 && nlist > 0 && M > 0 && M % 16 == 0 && dsub > 0 && dsub % 4 == 0, "ivfpq_key_terms: need M % 16 == 0 and dsub % 4 == 0");
+    if (N == 0) return OK;
+    GNNLM_REQUIRE(codes && list_off && coarse && pq && out, "ivfpq_key_terms: null operand");
+    GNNLM_REQUIRE((uintptr_t)codes % 16 == 0 && (uintptr_t)coarse % 16 == 0 && (uintptr_t)pq % 16 == 0, "ivfpq_key_terms: 16-byte aligned operands");
+    GNNLM_REQUIRE(cdiv(N, (int64_t)256) < (1ll << 31), "ivfpq_key_terms: too many rows for one launch");
+    hipLaunchKernelGGL(ivfpq_key_terms_kernel, dim3((unsigned)cdiv(N, (int64_t)256)), dim3(256), 0, stream, codes, list_off, nlist, coarse, pq, N, M, dsub, out);
+    GNNLM_LAUNCH_CHECK();
+    return OK;
+}
 
 int ivfpq_pack_codes(const uint8_t* codes, int64_t N, int M, uint8_t* out, hipStream_t stream) {
     GNNLM_REQUIRE(codes && out && N >= 0 && (M == 32 || M == 64), "ivfpq_pack_codes: need M = 32 or 64");
@@ -469,7 +535,9 @@ int ivfpq_scan(const gnnlm_ivfpq_scan_t& d, hipStream_t stream) {
     if (d.tau) GNNLM_REQUIRE(d.cand_val && d.cand_id && d.cand_cnt && d.cap > 0, "ivfpq_scan: filtered mode needs the candidate buffers");
     else GNNLM_REQUIRE(d.out_val && d.seg > 0 && d.ld_out >= d.seg, "ivfpq_scan: dense mode needs the output rows");
     const size_t lds = (size_t)d.M * 256 * sizeof(float);
-    GNNLM_LDS_OPT_IN(&ivfpq_scan_kernel, 128 * 1024);
+    GNNLM_LDS_OPT_IN(&ivfpq_scan_kernel<false>, 128 * 1024);
+    GNNLM_LDS_OPT_IN(&ivfpq_scan_kernel<true>, 128 * 1024);
+    GNNLM_REQUIRE(!(d.list_term && d.key_term), "ivfpq_scan: the L2 metric takes list_term or key_term, not both");
     GNNLM_REQUIRE(!d.list_term || (!d.packed && d.ld_list_term >= (int64_t)d.M * 256 && d.ld_list_term % 4 == 0 && (uintptr_t)d.list_term % 16 == 0),
                   "ivfpq_scan: the L2 metric runs on row-major codes with 16-byte aligned list tables");
     ProfScope prof(K_IVF, stream, 0.0, 0.0);
@@ -477,14 +545,24 @@ int ivfpq_scan(const gnnlm_ivfpq_scan_t& d, hipStream_t stream) {
         GNNLM_REQUIRE(d.M == 32 || d.M == 64, "ivfpq_scan: the packed image exists for M = 32 and 64");
         const int64_t n_pairs = cdiv(d.n_tasks, (int64_t)2);
         const int per_xcd = (int)cdiv(n_pairs, (int64_t)8);
-        GNNLM_LDS_OPT_IN(&ivfpq_scan_rot_kernel<64>, 128 * 1024 + STAGE_BYTES);
-        GNNLM_LDS_OPT_IN(&ivfpq_scan_rot_kernel<32>, 64 * 1024 + STAGE_BYTES);
-        if (d.M == 64) hipLaunchKernelGGL(ivfpq_scan_rot_kernel<64>, dim3((unsigned)(8 * per_xcd)), dim3(1024), 2 * lds + STAGE_BYTES, stream, d, n_pairs, per_xcd);
-        else hipLaunchKernelGGL(ivfpq_scan_rot_kernel<32>, dim3((unsigned)(8 * per_xcd)), dim3(1024), 2 * lds + STAGE_BYTES, stream, d, n_pairs, per_xcd);
+        const dim3 grid((unsigned)(8 * per_xcd));
+        const size_t bytes = 2 * lds + STAGE_BYTES;
+        if (d.key_term) {
+            GNNLM_LDS_OPT_IN((&ivfpq_scan_rot_kernel<64, true>), 128 * 1024 + STAGE_BYTES);
+            GNNLM_LDS_OPT_IN((&ivfpq_scan_rot_kernel<32, true>), 64 * 1024 + STAGE_BYTES);
+            if (d.M == 64) hipLaunchKernelGGL((ivfpq_scan_rot_kernel<64, true>), grid, dim3(1024), bytes, stream, d, n_pairs, per_xcd);
+            else hipLaunchKernelGGL((ivfpq_scan_rot_kernel<32, true>), grid, dim3(1024), bytes, stream, d, n_pairs, per_xcd);
+        } else {
+            GNNLM_LDS_OPT_IN((&ivfpq_scan_rot_kernel<64, false>), 128 * 1024 + STAGE_BYTES);
+            GNNLM_LDS_OPT_IN((&ivfpq_scan_rot_kernel<32, false>), 64 * 1024 + STAGE_BYTES);
+            if (d.M == 64) hipLaunchKernelGGL((ivfpq_scan_rot_kernel<64, false>), grid, dim3(1024), bytes, stream, d, n_pairs, per_xcd);
+            else hipLaunchKernelGGL((ivfpq_scan_rot_kernel<32, false>), grid, dim3(1024), bytes, stream, d, n_pairs, per_xcd);
+        }
         GNNLM_LAUNCH_CHECK();
         return OK;
     }
-    hipLaunchKernelGGL(ivfpq_scan_kernel, dim3((unsigned)d.n_tasks), dim3(256), lds, stream, d);
+    if (d.key_term) hipLaunchKernelGGL(ivfpq_scan_kernel<true>, dim3((unsigned)d.n_tasks), dim3(256), lds, stream, d);
+    else hipLaunchKernelGGL(ivfpq_scan_kernel<false>, dim3((unsigned)d.n_tasks), dim3(256), lds, stream, d);
     GNNLM_LAUNCH_CHECK();
     return OK;
 }

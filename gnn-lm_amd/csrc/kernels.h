@@ -15,6 +15,8 @@ int topk_merge(const gnnlm_topk_t& d, hipStream_t stream);
 int ivfpq_scan(const gnnlm_ivfpq_scan_t& d, hipStream_t stream);
 int ivfpq_pack_codes(const uint8_t* codes, int64_t N, int M, uint8_t* out, hipStream_t stream);
 int ivfpq_pack_lut(const float* lut, int64_t ld_lut, int64_t n, int M, float* out, hipStream_t stream);
+int ivfpq_key_terms(const uint8_t* codes, const int64_t* list_off, int64_t N, int nlist, const float* coarse, const float* pq, int M, int dsub,
+                    float* out, hipStream_t stream);
 
 int ivfpq_pack_tiles(const uint8_t* codes, int64_t N, int M, uint8_t* out, hipStream_t stream);
 int ivfpq_build_groups(const int64_t* pl, int64_t ld, int64_t n, int P, int nlist, int64_t seg, int32_t* grp_list, int32_t* grp_q,

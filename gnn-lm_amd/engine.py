@@ -90,15 +90,16 @@ class GnnLmEngine:
         ``sweep = (ks, temperatures, lmbdas)``: additionally ``sweep_logp`` [G, n], every point of the kNN-LM tuning grid
         (``ops.grid_points`` order) from the step's one forward and one search (which then runs with ``lmbda`` 0 too).
 
-        ``knn_index`` (an ``ivfpq.IVFPQIndex`` with the labels attached): the kNN search of the step's own queries -- the
-        L2-normalised gcn_feat rows, knn_model.py:100,181-184 -- runs on the device inside the step, as it runs inside the
+        ``knn_index`` (an ``ivfpq.IVFPQIndex`` with the labels attached): the kNN search of the step's own queries -- the gcn_feat
+        rows, L2-normalised for a cosine index only (knn_model.py:100,181-184) -- runs on the device inside the step, as it runs inside the
         reference's timer (fairseq_cli/eval_lm.py:214-219 around sequence_scorer.py:115-120); the batch's ``knn_*`` fields are
         then not read.  The softmax is enqueued between the search and the host's one look at its survivor counts.
 
         ``knn_keys`` (the key table in HBM, fp16 / f32 [n_store, d]) with ``knn_sim_func`` "ip" / "l2" (``--knn-sim-func``,
         knn_model.py:161-175): the index's distances are replaced by the similarities recomputed from the full-precision keys
-        (``ops.knn_recompute_sims``; "ip" divides by |key| as the reference does for the cosine index this search stands for) before
-        the interpolation and the sweep, and come back as ``knn_sims``."""
+        (``ops.knn_recompute_sims``; "ip" divides by |key| as the reference does for a cosine index) before
+        the interpolation and the sweep, and come back as ``knn_sims``.  "do_not_recomp_l2" with an L2 index (``metric="l2"``, the
+        reference's default ``faiss_store.l2``): the similarities are the negated squared distances of the search (knn_model.py:153-154)."""
         return self.score_finish(self.score_begin(batch, lmbda, temperature, knn_index, k, sweep, knn_keys, knn_sim_func, orig_prob_ratio))
 
     def score_begin(self, batch: BlockBatch, lmbda: float = 0.0, temperature: float = 1.0, knn_index=None, k: int = 0, sweep=None,
@@ -106,10 +107,14 @@ class GnnLmEngine:
         """Enqueue the step up to the search's host read (features, search, softmax) and return a handle for ``score_finish``:
         several batches can be in flight (one per stream), the host looks at a search's survivor counts only when it comes back
         to that batch."""
-        if knn_sim_func not in ("do_not_recomp_ip", "ip", "l2"):
-            raise ValueError("knn_sim_func: do_not_recomp_ip, ip or l2 (the in-step search is an inner-product one)")
-        if knn_sim_func != "do_not_recomp_ip" and knn_keys is None:
+        if knn_sim_func not in ("do_not_recomp_ip", "do_not_recomp_l2", "ip", "l2"):
+            raise ValueError("knn_sim_func: do_not_recomp_ip, do_not_recomp_l2, ip or l2")
+        if not knn_sim_func.startswith("do_not_recomp") and knn_keys is None:
             raise ValueError(f"knn_sim_func={knn_sim_func!r} needs knn_keys (the key table in HBM)")
+        index_l2 = getattr(knn_index, "metric", "ip") == "l2"
+        if knn_index is not None and knn_sim_func.startswith("do_not_recomp") and (knn_sim_func == "do_not_recomp_l2") != index_l2:
+            raise ValueError(f"knn_sim_func={knn_sim_func!r} on an index of metric {'l2' if index_l2 else 'ip'}: the search's own values are "
+                             "similarities for do_not_recomp_ip on an inner-product index and for do_not_recomp_l2 on an L2 index only")
         if orig_prob_ratio >= 1:
             raise ValueError(f"math domain error: orig_prob_ratio = {orig_prob_ratio} needs log(1 - orig_prob_ratio) (transformer.py:1060)")
         alpha = float(orig_prob_ratio) if orig_prob_ratio > 0 else 0.0
@@ -117,8 +122,11 @@ class GnnLmEngine:
         sweep = tuple(sweep[:3]) if sweep and sweep[0] is not None else None
         x = self.features(batch)
         pending = qn = None
+        # knn_model.py:181-184: the queries (and, for "ip", the recomputed keys, :172-173) are normalised for a cosine index only; an index
+        # object that does not say (no `cosine` attribute: a search stand-in) is a cosine one, as every index was before L2 ones existed
+        cosine = getattr(knn_index, "cosine", True)
         if (lmbda > 0.0 or sweep) and knn_index is not None:
-            qn = x / (x ** 2).sum(-1, keepdim=True).sqrt()
+            qn = x / (x ** 2).sum(-1, keepdim=True).sqrt() if cosine else x
             pending = knn_index.search_begin(qn.contiguous(), k, return_vals=True)
         branches = lm_rows = None
         if alpha > 0 or alphas:
@@ -135,7 +143,9 @@ class GnnLmEngine:
                 lm_logp = ops.logp_mix(*branches, [alpha])[0]
         else:
             lm_logp = self.asm.target_log_prob(x, batch.targets)
-        resim = (qn, knn_keys, knn_sim_func) if pending is not None and knn_sim_func != "do_not_recomp_ip" else None
+        resim = (qn, knn_keys, knn_sim_func, cosine) if pending is not None and not knn_sim_func.startswith("do_not_recomp") else None
+        if pending is not None and resim is None and index_l2:
+            resim = "negate"                                             # knn_model.py:153-154: sims = -dists
         return batch, lmbda, temperature, x, lm_logp, pending, sweep, resim, branches, lm_rows
 
     def score_finish(self, handle):
@@ -148,9 +158,11 @@ class GnnLmEngine:
         grid_lm = lm_rows if lm_rows is not None else lm_logp
         if pending is not None:
             sims, ids, vals = pending.result()
-            if resim is not None:                                # knn_model.py:161-175 on the step's own normalised queries
-                qn, keys, fn = resim
-                sims = ops.knn_recompute_sims(qn.contiguous(), ids.contiguous(), keys, fn, normalize_keys=(fn == "ip"))
+            if resim == "negate":
+                sims = -sims
+            elif resim is not None:                              # knn_model.py:161-175 on the step's own queries
+                qn, keys, fn, cosine = resim
+                sims = ops.knn_recompute_sims(qn.contiguous(), ids.contiguous(), keys, fn, normalize_keys=(fn == "ip" and cosine))
             if lmbda > 0.0:
                 logp, p_knn, recall = ops.knn_interp(lm_logp, sims, ids, batch.targets, temperature, lmbda,
                                                      n_store=self.store.n_store, knn_vals=vals)

@@ -198,19 +198,23 @@ class IVFPQIndex:
         # M = 64: the int8-MFMA search's image of the code rows (tiles of 16 rows, rotated byte order; csrc/ivfpq_mfma.hip)
         # scan="f32": the float32 scan at M = 64 too (tests compare the int8-MFMA search with it)
         self.packed_codes = self.tiles = None
-        self.list_term = None
+        self.list_term = self.key_term = None
         if metric == "l2":
             # squared distances with residual codes: |q' - c_l - r|^2 = |q' - c_l|^2 + sum_m (T[l][m][code] - 2 <q'_m, p_mc>) with the
-            # per-list table T[l][m][c] = |p_mc|^2 + 2 <c_l,m, p_mc> (faiss IndexIVFPQ's precomputed table); the scan adds it to the
-            # query's table while it fills LDS (gnnlm_ivfpq_scan, list_term).  nlist * M KiB of HBM: built when that is affordable
-            need = self.nlist * self.M * 1024
-            if need > list_term_bytes:
-                raise ValueError(f"IVFPQIndex: the L2 metric keeps a [nlist, M, 256] float32 table ({need / 2**30:.1f} GiB here, "
-                                 f"list_term_bytes = {list_term_bytes / 2**30:.1f} GiB)")
+            # per-list table T[l][m][c] = |p_mc|^2 + 2 <c_l,m, p_mc> (faiss IndexIVFPQ's precomputed table).  A key's M entries of T add up
+            # to a constant of the key, key_term = |c_l + r|^2 - |c_l|^2 (gnnlm_ivfpq_key_terms): with that one float per key the tables
+            # are the query's own, as for the inner product.
+            #   M = 64 (the kNN-LM shape): key_term + the packed float32 scan, two rounds (scan="rowmajor": the per-list table below)
+            #   T beyond list_term_bytes (nlist * M KiB: many lists): key_term + the row-major scan
+            #   otherwise: T itself; the row-major scan adds it to the query's table while it fills LDS (gnnlm_ivfpq_scan, list_term)
             self.coarse_n2 = (coarse ** 2).sum(1).contiguous()
-            cross = torch.einsum("lmd,mcd->lmc", coarse.reshape(self.nlist, self.M, self.dsub), pq)
-            self.list_term = ((pq ** 2).sum(2)[None] + 2.0 * cross).reshape(self.nlist, self.M * 256).contiguous()
-            scan = "rowmajor"
+            fits = self.nlist * self.M * 1024 <= list_term_bytes
+            if fits and (self.M != 64 or scan == "rowmajor"):
+                cross = torch.einsum("lmd,mcd->lmc", coarse.reshape(self.nlist, self.M, self.dsub), pq)
+                self.list_term = ((pq ** 2).sum(2)[None] + 2.0 * cross).reshape(self.nlist, self.M * 256).contiguous()
+            elif self.ntotal:
+                self.key_term = ops.ivfpq_key_terms(list_codes, list_off, coarse, pq)
+            scan = "f32" if self.M == 64 and scan != "rowmajor" else "rowmajor"
         if scan == "rowmajor":
             pass                                                             # the row-major kernels (one table per (query, list) task)
         elif self.M == 64 and self.ntotal and self.ntotal < (1 << 32) and scan != "f32" and self.max_list < (1 << 19) and self.nlist <= (1 << 18):
@@ -345,6 +349,8 @@ class IVFPQIndex:
         s.task_q, s.task_p, s.n_tasks = task_q.data_ptr(), task_p.data_ptr(), order.numel()
         if self.list_term is not None:
             s.list_term, s.ld_list_term = self.list_term.data_ptr(), self.list_term.stride(0)
+        if self.key_term is not None:
+            s.key_term = self.key_term.data_ptr()
         if tau is None:
             s.out_val, s.ld_out, s.p0, s.seg = out.data_ptr(), out.stride(0), p_lo, self.max_list       # scores only (out_id NULL)
         else:

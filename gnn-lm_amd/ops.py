@@ -572,6 +572,25 @@ def ivfpq_pack_tiles(codes):
     return out
 
 
+def ivfpq_key_terms(list_codes, list_off, coarse, pq):
+    """The L2 scan's term of every key (gnnlm_ivfpq_key_terms): list_codes [N, M] u8 in list order, list_off [nlist + 1] i64,
+    coarse [nlist, M * dsub] f32, pq [M, 256, dsub] f32 -> key_term [N] f32 = sum_m (|p_m,c|^2 + 2 <c_l,m, p_m,c>) of the row's
+    codes c and list l, accumulated in float64."""
+    for t in (list_codes, list_off, coarse, pq):
+        _dev(t)
+    _dtype(list_codes, torch.uint8, "list_codes")
+    _dtype(list_off, torch.int64, "list_off")
+    _dtype(coarse, torch.float32, "coarse")
+    _dtype(pq, torch.float32, "pq")
+    N, M = list_codes.shape
+    nlist, dsub = coarse.shape[0], pq.shape[2]
+    if list_off.numel() != nlist + 1 or pq.shape[0] != M or pq.shape[1] != 256 or coarse.shape[1] != M * dsub:
+        raise ValueError("ivfpq_key_terms: list_off [nlist + 1], coarse [nlist, M * dsub], pq [M, 256, dsub]")
+    out = torch.empty(N, dtype=torch.float32, device=list_codes.device)
+    call("gnnlm_ivfpq_key_terms", ptr(list_codes), ptr(list_off), N, nlist, ptr(coarse), ptr(pq), M, dsub, ptr(out), stream())
+    return out
+
+
 def ivfpq_quantize_lut(lut, M=64):
     """lut [n, M * 256] f32 -> (qlut [n, 2, 256, 32] u8, qmeta [n, 4] f32 = {delta, sum_m lo_m, max |lut|, 0}) with
     lut[m][c] < lo_m + (u + 1) * delta for every entry, u = qlut[m // 32][c][m % 32] ^ 0x80 (the table stores the signed

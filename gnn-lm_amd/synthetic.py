@@ -48,7 +48,7 @@ def synthetic_ivfpq_index(N, d, nlist, M, dev, nprobe=32, seed=7, skew=0.0, **kw
     """Shape-true, content-free IVF-PQ index of the reference's kNN index family (OPQ64_1024,IVF4096,PQ64 over the
     103 M WikiText-103 keys: 6.6 GB of codes): random codes and centroids, a random rotation; lists of equal length, or
     (``skew`` > 0) log-normally distributed lengths with that sigma -- k-means lists of real keys are skewed (the 8.4 M-key
-    clustered test index: 1 .. 32,659 keys, median 1,349).  For search-throughput measurements only (bench.py,
+    clustered test index: 1 .. 32,659 keys, median 1,349).  ``metric="l2"``: the same arrays as an L2 index (not a cosine one).  For search-throughput measurements only (bench.py,
     tools/ivfpq_bench.py); a real index comes from run_index_build."""
     from .ivfpq import IVFPQIndex
     g = torch.Generator(device=dev)
@@ -66,7 +66,7 @@ def synthetic_ivfpq_index(N, d, nlist, M, dev, nprobe=32, seed=7, skew=0.0, **kw
         per = -(-N // nlist)
         off = torch.clamp(torch.arange(nlist + 1, device=dev, dtype=torch.int64) * per, max=N)
     return IVFPQIndex(R, coarse, pq, off, torch.arange(N, device=dev, dtype=torch.int64), device_codes(N, M, dev, seed),
-                      nprobe=nprobe, cosine=True, **kw)
+                      nprobe=nprobe, cosine=kw.get("metric", "ip") != "l2", **kw)
 
 
 def make_codec(rs, M, dsub, d, opq=True):

@@ -441,8 +441,22 @@ typedef struct gnnlm_ivfpq_scan {
      * list_term[l][m][c] = |p_mc|^2 + 2 <c_l,m , p_mc>  ([nlist, M * 256], row stride ld_list_term; faiss's "precomputed table")
      * and probe_bias = -|q' - c_l|^2.  list_term != NULL selects it (row-major codes, packed = 0); larger score = nearer */
     const float* list_term;  int64_t ld_list_term;
+    /* Appended within ABI 12 (additive: one member at the end, no existing member moved).  The same L2 score with one term per KEY in
+     * place of the per-list table: the 64 list_term entries of a key add up to a constant of the key,
+     *     key_term[r] = sum_m list_term[l][m][code_m(r)] = |c_l + r(x)|^2 - |c_l|^2        (gnnlm_ivfpq_key_terms; [N], list order like `ids`)
+     * so  -|q' - c_l - r(x)|^2 = probe_bias + 2 sum_m lut[q][m][code_m] - key_term[r]  with the tables of the QUERY alone, as for the
+     * inner product: row-major or packed codes, dense and filtered mode, nothing of size nlist.  key_term != NULL selects it;
+     * list_term and key_term together are refused */
+    const float* key_term;
 } gnnlm_ivfpq_scan_t;
 int gnnlm_ivfpq_scan(const gnnlm_ivfpq_scan_t* desc, void* stream);
+/* Added within ABI 12 (additive: a new entry).  The per-key term of the L2 scan above, once per index (faiss keeps the per-list
+ * "precomputed table" instead: IndexIVFPQ::precompute_table behind `IndexBuilder`'s METRIC_L2, knn/index_builder.py:26,118):
+ * key_term[r] = sum_m (|p_m,c|^2 + 2 <c_l,m, p_m,c>), c = list_codes[r][m], l the list of row r by list_off (empty lists allowed),
+ * coarse [nlist, M * dsub], pq [M, 256, dsub]; accumulated in float64 in ascending (m, element) order and rounded to float32 once.
+ * M % 16 == 0, dsub % 4 == 0, 16-byte aligned operands; rows are addressed with 64 bits. */
+int gnnlm_ivfpq_key_terms(const uint8_t* list_codes, const int64_t* list_off, int64_t N, int32_t nlist, const float* coarse, const float* pq,
+                          int32_t M, int32_t dsub, float* key_term, void* stream);
 
 /* The scan's own device layouts (M = 32 or 64).  Codes: blocks of 64 rows stored [M/16 pieces][64 rows][16 B], and inside a
  * row byte s of half h holds sub-quantizer 32 h + (row + s) mod 32 -- `out` has ceil(N / 64) * 64 * M bytes, rows beyond N
