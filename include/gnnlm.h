@@ -430,9 +430,11 @@ typedef struct gnnlm_ivfpq_scan {
     const float* lut;  int64_t ld_lut;    /* [n, M*256] */
     const int64_t* probe_list;  const float* probe_bias;  int32_t ld_probe;   /* [n, ld_probe]: probed lists (-1: none) and <q', centroid> */
     const int32_t* task_q;  const int32_t* task_p;  int64_t n_tasks;
-    float* out_val;  int64_t* out_id;  int64_t ld_out;  int32_t p0, seg;      /* dense: column (p - p0) * seg + j, ids -1 beyond the list;
+    float* out_val;  int64_t* out_id;  int64_t ld_out;  int32_t p0, seg;      /* dense: column (p - p0) * seg + j, ids -1 beyond the list
+                                                                               * (out_val is NOT written there: the -1 marks the column);
                                                                                * out_id NULL (ABI 5): scores only, -inf beyond the list -- the
-                                                                               * caller maps the columns it keeps to ids[list_off[list] + j] */
+                                                                               * caller maps the columns it keeps to ids[list_off[list] + j].
+                                                                               * Rows of a list beyond seg are dropped */
     const float* tau;  float* cand_val;  int64_t* cand_id;  int32_t* cand_cnt;  int32_t cap;   /* filtered: rows of `cap` slots, cand_cnt[q] counts ALL survivors */
     int32_t packed;                       /* ABI 5: nonzero = `codes` is the image of gnnlm_ivfpq_pack_codes and `lut` the tables of
                                            * gnnlm_ivfpq_pack_lut (M = 32 or 64): the bank-conflict-free scan */
