@@ -826,7 +826,7 @@ int chain_attn(const ChainAttnParams& p, hipStream_t stream) {
 }
 
 int causal_softmax(float* S, int64_t n_mats, int T, int64_t ld, int max_ctx, hipStream_t stream) {
-    GNNLM_REQUIRE(S && T > 0 && ld >= T, "causal_softmax: bad arguments");
+    GNNLM_REQUIRE(S && T > 0 && ld >= T && n_mats >= 0, "causal_softmax: bad arguments");
     const int64_t rows = n_mats * T;
     if (rows == 0) return OK;
     ProfScope prof(K_CAUSAL, stream, 0.0, 8.0 * rows * ld);
@@ -841,6 +841,8 @@ int causal_attn_fused(const float* Q, const float* K, const float* V, int64_t ld
                       int n_blocks, int T, int H, int dk, int max_ctx, hipStream_t stream, bool accumulate) {
     GNNLM_REQUIRE(Q && K && V && out, "causal_attn: null operand");
     GNNLM_REQUIRE(causal_attn_fused_ok(T, dk), "causal_attn: the fused kernel is built for T = 256, d_k = 128");
+    GNNLM_REQUIRE(H > 0 && n_blocks >= 0 && (int64_t)n_blocks * H < (1ll << 31), "causal_attn: bad shape");
+    GNNLM_REQUIRE(ld >= (int64_t)H * dk && ldo >= (int64_t)H * dk, "causal_attn: row strides must be >= H * d_k");
     GNNLM_REQUIRE(ld % 4 == 0 && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)K % 16 == 0) && ((uintptr_t)V % 16 == 0),
                   "causal_attn: operands must be 16-byte aligned with ld % 4 == 0");
     if (n_blocks == 0) return OK;
