@@ -346,7 +346,7 @@ int gather_decode(const GatherParams& p, hipStream_t stream) {
     GNNLM_REQUIRE(p.M > 0 && p.dsub > 0 && p.dsub % 4 == 0, "gather_decode: dsub must be a multiple of 4");
     GNNLM_REQUIRE(!p.out_x || (p.centroids && p.ld_x % 4 == 0 && (uintptr_t)p.out_x % 16 == 0),
                   "gather_decode: out_x needs centroids, 16-byte alignment and ld % 4 == 0");
-    GNNLM_REQUIRE(p.vals_itemsize == 2 || p.vals_itemsize == 4, "gather_decode: vals must be int16 or int32");
+    GNNLM_REQUIRE(!p.vals || p.vals_itemsize == 2 || p.vals_itemsize == 4, "gather_decode: vals must be int16 or int32");
     const int64_t n_slots = p.n_groups * (1 + p.left + p.right);
     if (n_slots == 0) return OK;
     if (!mapped && !p.direct && !p.out_x && p.out_codes && p.left == 0 && p.right == 0 && p.M % 16 == 0 &&

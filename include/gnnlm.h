@@ -109,7 +109,7 @@ typedef struct gnnlm_shards {
 typedef struct gnnlm_gather {
     const uint8_t* codes;      /* [n_local, M] */
     const void* vals;          /* [n_local] int16 / int32 (optional) */
-    int32_t vals_itemsize;     /* 2 or 4 */
+    int32_t vals_itemsize;     /* 2 or 4 with vals; ignored (0 is fine) when vals is NULL */
     int64_t n_store, row0, n_local;
     int32_t M, dsub;           /* dsub % 4 == 0; ksub is fixed to 256 (8-bit codes, pq_wrapper.py:33) */
     const float* centroids;    /* [M, 256, dsub] */
