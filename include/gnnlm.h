@@ -397,11 +397,27 @@ int gnnlm_label_tags(const void* vals, int32_t vals_itemsize, int64_t n, uint8_t
  *   (cosine index: col_scale = 1/|key|;  L2: alpha = -2, col_bias = |key|^2, largest = 0, add |q|^2 afterwards)
  * State: best_val / best_id [n, k], best first, ties by ascending id (== a stable argsort of the whole row, so the
  * result is independent of the chunking); unfilled slots hold id -1 like faiss.  No [n, N] matrix is ever built.
+ * The rules in full (tests/topk_ref.py restates them, tests/test_topk_abi_gpu.py holds both kernels to them bit for bit):
+ *   - the value is float32, rounded after each step in this order: scores[r, c] * alpha (alpha 0 is read as 1), then * col_scale[c],
+ *     then + col_bias[c]; no fused multiply-add.  Denormals are kept and ordered as numbers;
+ *   - the id of column c of row r is ids[r * ld_ids + c] if ids is given, else col_ids[c] if col_ids is given, else col0 + c:
+ *     ids overrides col_ids, which overrides col0; the overridden fields are not read;
+ *   - a column is absent if its id is < 0 (from any of the three sources; col0 + c < 0 included), if its value is NaN, or if its
+ *     value is the worst infinity of the direction (-inf for largest, +inf otherwise: the padding value).  The other infinity is a
+ *     value like any other;
+ *   - row r has min(ncols, row_ncols[r]) columns: row_ncols[r] <= 0 is an empty row, row_ncols[r] > ncols is clamped; the columns
+ *     beyond, and the pad columns of ld / ld_ids, are not read;
+ *   - a call folds the state's real entries (id >= 0; slots with id < 0 are unfilled whatever their value) and the chunk's columns:
+ *     the k best by (value, ascending id), then id -1 with -inf (largest) / +inf.  Ids are expected to be unique within a row and
+ *     across its chunks; a zero is returned with either sign (-0 and +0 compare equal and tie);
+ *   - n = 0 is accepted and touches nothing.  ncols = 0 is accepted with scores = NULL: init = 1 writes the padding to all n * k
+ *     slots, init = 0 leaves the state's content as it is.  k outside [1, 2048], n < 0, ncols < 0, a NULL state buffer and NULL
+ *     scores with ncols > 0 are refused with nothing written.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct gnnlm_topk {
     const float* scores;  int64_t ld;     /* [n, ncols] chunk, row stride ld elements */
     int64_t n;  int32_t ncols;
-    int64_t col0;                         /* id of column c = col_ids ? col_ids[c] : col0 + c (col_ids < 0: skipped) */
+    int64_t col0;                         /* id of column c = ids ? ids[r, c] : col_ids ? col_ids[c] : col0 + c (an id < 0: skipped) */
     const int64_t* col_ids;
     const float* col_scale;  const float* col_bias;  float alpha;   /* alpha 0 is read as 1 */
     int32_t k;                            /* <= 2048 */

@@ -440,7 +440,8 @@ def test_knn_model_reads_faiss_flat_file(dev, tmp_path, metric):
 def test_topk_select_from_ragged_candidate_lists(dev, k, largest):
     """init + per-row ids + row_ncols (what the exact re-score of an IVF-PQ search hands over: one ragged candidate list per
     query, a few times k long -- the counting pre-pass applies from 2 KP columns on): exact ids with ties by ascending id,
-    empty and short rows, negative (skipped) ids."""
+    empty and short rows, negative (skipped) ids.  With ncols = 20000 > 16384 the dispatcher takes the merge kernel with its counting
+    pre-pass, not the select kernel; tests/test_topk_abi_gpu.py reaches the select kernel with these fields."""
     from gnnlm_amd import ops
     rs = np.random.RandomState(3 * k + largest)
     n, W = 11, 20000
