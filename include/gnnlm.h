@@ -47,6 +47,21 @@ size_t gnnlm_sizeof(const char* struct_name);
  *           fn.v_dot_u / u_mul_e+sum on the dense tgt-tgt edges (:354,383-385),
  *           `x @ A` of TorchPQCodec.decode (knn/pq_wrapper.py:202),
  *           the head/tail matmuls of AdaptiveSoftmax (fairseq/modules/adaptive_softmax.py:184-203).
+ *
+ * Store flavour, for every logical row r < m = min(M, *m_dev) (m = M without m_dev; *m_dev >= 0) and every batch (b1, b2):
+ *   C[b][c_rows[r], n] = alpha * <A[b][a_rows[r], :], W[b][n, :]> + gate[r] * bias + R[b][c_rows[r], n],   n < N
+ *   with X[b] = X + b1 * sX1 + b2 * sX2; bias is bias[b][n] (bias_mode 1) or bias[b][r] (bias_mode 2).  a_rows, c_rows, gate and
+ *   m_dev are shared by all batches.  a_rows[r] < 0 makes the product term of the row zero (bias and R still apply).  Nothing else
+ *   of C is written: not the pad columns of ldc > N, not the rows from m on, not a row no c_rows entry names.  c_rows entries
+ *   below m must be distinct.  R may be C itself with ldr = ldc (in place).
+ * Alignment: A and W 16 bytes, lda, ldw, K and the A / W batch strides multiples of 4 elements; C, R, bias, gate and lse_picked need
+ *   their natural 4 bytes only and ldc, ldr, the C / R / bias strides may be any number; lse_part needs 8 bytes.
+ * tile_order, m_dev's presence and a_rows_bound choose among kernels and the order tiles are visited in.  tile_order never changes a
+ *   bit of the result.  Kernels differ in the order they sum k in, so "the same bits" holds per kernel: the same problem with and
+ *   without m_dev (or with and without a_rows_bound) may differ in the last bits.  Two identical calls give identical bits.
+ * Refused with GNNLM_E_INVALID before anything is launched or written: a NULL A or W, C and lse_part both NULL, M < 0, N or K <= 0,
+ *   K, lda, ldw or an A / W batch stride not a multiple of 4, A or W not 16-byte aligned, precision outside 0..3, tile_order outside
+ *   0..66, and what the log-sum-exp flavour does not take (below).  M = 0 is accepted and touches nothing (m_out included).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct gnnlm_gemm {
     const float* A;  int64_t lda;
@@ -60,8 +75,9 @@ typedef struct gnnlm_gemm {
     const float* R;  int64_t ldr;
     float alpha;               /* 0 is read as 1 */
     int32_t M, N, K;           /* K % 4 == 0 */
-    const int32_t* m_dev;      /* optional device-side row count (<= M): tiles beyond it exit */
-    int32_t* m_out;            /* optional: receives min(M, *m_dev) (device or host-mapped memory; used by the profiler) */
+    const int32_t* m_dev;      /* optional device-side row count >= 0, read as min(M, *m_dev): rows from it on are neither read nor written */
+    int32_t* m_out;            /* optional: receives that row count (M without m_dev) (device or host-mapped memory; while the library's
+                                  profiler runs it records there instead) */
     int32_t batch1, batch2;    /* 0 is read as 1; batch index (b1, b2) */
     int64_t sA1, sA2, sW1, sW2, sC1, sC2, sB1, sB2, sR1, sR2;   /* batch strides in elements */
     int32_t precision;         /* 0: f32 MFMA (exact fmaf chain; or the enclosing orchestrator's setting);
@@ -69,10 +85,16 @@ typedef struct gnnlm_gemm {
                                   3: fp16 -- both operands rounded to IEEE float16 (round-to-nearest-even; beyond +-65504
                                      -> +-inf, as torch.Tensor.half(), not clamped), exact products, f32 accumulation;
                                      every epilogue and every tensor in memory stays f32 */
-    int32_t tile_order;        /* 0: auto (consecutive tiles share the larger operand's panel), 1: n fastest, 2: m fastest */
-    /* log-sum-exp epilogue (C may be NULL): instead of storing C, every (row, 64-column slab) writes a
-     * (max, sum exp(x - max)) pair to lse_part[row][slab], slab count = 2*ceil(N/128); lse_picked[row] =
-     * alpha * (A.W^T)[row, lse_pick[row]].  Finish with gnnlm_lse_reduce.  batch must be 1. */
+    int32_t tile_order;        /* 0: auto (consecutive tiles share the larger operand's panel), 1: n fastest, 2: m fastest, 2 + GM (GM in
+                                  1..64): bands of GM m-tiles, n slow inside a band.  Speed only: no bit of the result depends on it */
+    /* log-sum-exp epilogue, taken when lse_part is given: instead of storing C (ignored, may be NULL), every row r < m and every
+     * part p < 2*ceil(N/128) writes lse_part[r][p] = (alpha * max, sum exp(alpha * x - alpha * max)) over the logits x = (A.W^T)[r, n]
+     * of the columns 64 p <= n < min(N, 64 p + 64); a part without a column (the last one when N mod 128 is in 1..64) holds
+     * (-inf, 0).  With lse_pick, lse_picked[r] = alpha * x[r, lse_pick[r]] for r < m where 0 <= lse_pick[r] < N; any other entry of
+     * lse_picked is left untouched, as are the rows of lse_part from m on.  Finish with gnnlm_lse_reduce.
+     * a_rows, a_rows_bound, m_dev, m_out, precision and tile_order act as in the store flavour, except that every a_rows[r], r < m,
+     * must be >= 0: a negative entry reads nothing out of bounds, but the row's result is unspecified.  Refused (GNNLM_E_INVALID):
+     * batch1 * batch2 != 1, alpha < 0 or NaN (0 is read as 1), and bias, gate, R or c_rows -- the epilogue would drop them. */
     float* lse_part;           /* [M, 2*ceil(N/128), 2] */
     const int32_t* lse_pick;   /* optional [M] */
     float* lse_picked;         /* [M] (with lse_pick) */
@@ -80,7 +102,9 @@ typedef struct gnnlm_gemm {
                                   32-bit row offsets take a gathered problem */
 } gnnlm_gemm_t;
 int gnnlm_gemm_nt(const gnnlm_gemm_t* desc, void* stream);
-/* lse[row] = log sum exp over the row, from the partial pairs of the LSE epilogue */
+/* lse[row] = log sum exp over the row, from the n_parts (max, sum) pairs of the LSE epilogue: max_p + log sum_p s_p exp(m_p - max_p) for
+ * row < min(rows, *m_dev); later rows are untouched.  A (-inf, 0) pair adds nothing; a row of such pairs only gives -inf.  rows = 0 is
+ * accepted. */
 int gnnlm_lse_reduce(const float* part, int32_t n_parts, int64_t rows, const int32_t* m_dev, float* lse, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
