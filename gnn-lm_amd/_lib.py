@@ -131,6 +131,7 @@ def lib():
         L.gnnlm_ivfpq_quantize_lut.argtypes = [vp, i64, i64, i32, vp, vp, vp]
         L.gnnlm_ivfpq_build_groups.argtypes = [vp, i64, i64, i32, i32, i64, vp, vp, vp, vp, vp, vp]
         L.gnnlm_label_tags.argtypes = [vp, i32, i64, vp, vp]
+        L.gnnlm_neighbor_labels.argtypes = [vp, i64, i64, vp, i32, i32, vp, vp]
         L.gnnlm_knn_interp_scratch_bytes.argtypes = [i64, i32, i64]
         L.gnnlm_knn_interp_scratch_bytes.restype = ctypes.c_size_t
         L.gnnlm_ivfpq_split_payload.argtypes = [vp, i64, i32, i32, vp, vp]
@@ -140,7 +141,7 @@ def lib():
         L.gnnlm_hgt_forward_ragged.argtypes = [vp, vp, vp, vp, ctypes.c_size_t, vp]
         L.gnnlm_ragged_tiles.argtypes = [vp, i32, vp]
         L.gnnlm_causal_attn_varlen.argtypes = [vp, vp, vp, i64, vp, i64, vp, i32, i32, i32, vp]
-        for nm in ("gnnlm_gemm_nt", "gnnlm_pq_gather_decode", "gnnlm_star_attn", "gnnlm_chain_attn",
+        for nm in ("gnnlm_gemm_nt", "gnnlm_pq_gather_decode", "gnnlm_token_gather", "gnnlm_star_attn", "gnnlm_chain_attn",
                    "gnnlm_knn_interp", "gnnlm_knn_interp_grid", "gnnlm_knn_recompute_sims", "gnnlm_topk_merge", "gnnlm_ivfpq_scan", "gnnlm_gather_rows_peer",
                    "gnnlm_ivfpq_scan8", "gnnlm_ivfpq_rescore", "gnnlm_ivfpq_tau", "gnnlm_group_assign",
                    "gnnlm_ivfpq_tables"):

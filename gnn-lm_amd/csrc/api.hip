@@ -122,6 +122,7 @@ struct HgtBufs {
     int32_t *rows_out, *rows_kv;     // slot subsets of the elided ntgt updates
     int32_t *win_counts;             // device-side group count (ABI 9): rows per GEMM window x multiplier
     int32_t *nb_row;                 // merged groups on fetched codes: code row of every neighbour's centre
+    int32_t *nb_label;               // token store: label of every neighbour (-1: none), layer 0's index into the embedding table
     // ABI 11, layer 0's K / V keyed by datastore row: the slots' rows, the distinct ones, slot -> position, their count, validity, decoded rows
     int64_t *slot_row, *urows;
     int32_t *slot_u, *row_cnt, *win_counts_u;
@@ -132,10 +133,13 @@ struct HgtBufs {
 constexpr int MAX_WINDOWS = 128;
 
 bool needs_ntgt(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io) { return m.n_layers > 1 || io.out_ntgt != nullptr; }
+// `--reinit-nfeat`: the ntgt features are rows of the token-embedding table (gnnlm_hgt_t.token_embed); explicit layer-0 states win
+bool token_store(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io) { return m.token_embed != nullptr && io.ntgt_feats == nullptr; }
 // layer 0's K / V projections once per distinct datastore ROW of the batch's slots (ABI 11): merged groups on a local or mapped
 // store, rotation-folded layer-0 weights, and a model whose layer 0 computes a subset of the slots (the un-elided forward with
 // out_ntgt keeps the slot-keyed path)
 bool row_keyed_kv(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io) {
+    if (m.token_embed) return false;               // tied to the OPQ fold: a token store has none
     if (!io.row_table || !io.group_ids || io.fetched_codes || io.ntgt_feats || io.out_ntgt || m.n_layers < 2 || !m.opq_at) return false;
     const gnnlm_hgt_layer_t& w0 = m.layers[0];
     return w0.wq_n0 && w0.bq_n0 && w0.wk_n0 && w0.bk_n0 && w0.wv_n0 && w0.bv_n0 && m.n_layers - 2 < std::max(m.left, m.right);
@@ -143,7 +147,8 @@ bool row_keyed_kv(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io) {
 
 void carve_hgt(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, Carver& c, HgtBufs& b, bool ragged = false) {
     const int64_t Tt = (int64_t)io.n_blocks * io.T, d = m.d, H = m.n_heads;
-    const int64_t dpq = (int64_t)m.M * m.dsub, dmax = std::max<int64_t>(dpq, d);
+    const bool token = token_store(m, io);          // the codec fields are then not read
+    const int64_t dpq = token ? d : (int64_t)m.M * m.dsub, dmax = std::max<int64_t>(dpq, d);
     b.Tp = (io.T + 3) & ~3;
     b.slot_row = b.urows = nullptr; b.slot_u = b.row_cnt = b.win_counts_u = nullptr; b.uvalid = nullptr; b.xu = nullptr;
     b.ht[0] = c.take<float>(Tt * d);
@@ -169,6 +174,10 @@ void carve_hgt(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, Carver& c, HgtBuf
     b.has_nb = c.take<float>(Tt);
     b.win_counts = io.n_unique_dev ? c.take<int32_t>(MAX_WINDOWS * 8) : nullptr;
     b.nb_row = (io.group_ids && io.fetched_codes && !io.state_cache) ? c.take<int32_t>(Tt * io.kg) : nullptr;
+    // token store: the neighbours' labels are read by layer 0's star edges only, before that layer's a_linear writes b.aout --
+    // they live there when they fit (k_g <= d: every recipe), so that a one-layer step then needs no more workspace than on a
+    // code store; with k_g > d they get n_tok * k_g * 4 bytes of their own
+    b.nb_label = !token ? nullptr : (io.kg <= d ? reinterpret_cast<int32_t*>(b.aout) : c.take<int32_t>(Tt * io.kg));
     if (needs_ntgt(m, io)) {
         const int64_t S = (io.group_ids ? io.n_unique : Tt * io.kg) * (1 + m.left + m.right);
         b.hn[0] = c.take<float>(S * dmax);
@@ -274,8 +283,14 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
     if ((int64_t)io.n_blocks * io.T == 0) return OK;                 // empty batch: nothing to do
     GNNLM_REQUIRE(io.tgt_feats && io.ids && io.out_tgt, "hgt: null io");
     const bool dense0 = io.ntgt_feats != nullptr;        // layer-0 ntgt states given (input adapters): no code store
-    GNNLM_REQUIRE(dense0 || (m.centroids && m.M > 0 && m.dsub > 0), "hgt: codec missing");
-    GNNLM_REQUIRE(dense0 || io.fetched_codes || m.codes || m.shards, "hgt: no code store");
+    const bool token = token_store(m, io);               // ntgt features = rows of the token-embedding table (transformer.py:1046-1048)
+    GNNLM_REQUIRE(dense0 || token || (m.centroids && m.M > 0 && m.dsub > 0), "hgt: codec missing");
+    GNNLM_REQUIRE(dense0 || token || io.fetched_codes || m.codes || m.shards, "hgt: no code store");
+    GNNLM_REQUIRE(!token || (m.vals && (m.vals_itemsize == 2 || m.vals_itemsize == 4) && m.n_vocab > 0 && m.n_store > 0),
+                  "hgt: token_embed needs vals (int16 / int32, the whole label table), n_vocab and n_store");
+    GNNLM_REQUIRE(!token || (m.ld_token_embed >= m.d && m.ld_token_embed % 4 == 0 && (uintptr_t)m.token_embed % 16 == 0),
+                  "hgt: token_embed needs ld_token_embed >= d (a multiple of 4) and 16-byte alignment");
+    GNNLM_REQUIRE(!token || (!io.fetched_codes && !io.code_cache), "hgt: token_embed excludes fetched codes");
     GNNLM_REQUIRE(!dense0 || (io.ntgt_valid && io.ld_ntgt >= m.d && io.ld_ntgt % 4 == 0 && !io.fetched_codes),
                   "hgt: ntgt_feats needs ntgt_valid, ld_ntgt >= d (a multiple of 4) and no fetched_codes");
     const bool ntgt = needs_ntgt(m, io);
@@ -290,7 +305,7 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
     if (Tt == 0) return OK;
     const int d = m.d, H = m.n_heads, dk = d / H, T = io.T, kg = io.kg, nb = io.n_blocks;
     const int n_g = 1 + m.left + m.right;
-    const int dpq = dense0 ? d : m.M * m.dsub;
+    const int dpq = (dense0 || token) ? d : m.M * m.dsub;
     // ABI 6: the ntgt pipeline over the DISTINCT centre rows of the batch (io.group_ids); the star edges reach a group through
     // io.group_index
     const bool dedup = io.group_ids != nullptr;
@@ -308,7 +323,7 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
     GNNLM_REQUIRE(!(cached && io.fetched_codes) || (io.code_cache && m.M % 16 == 0), "hgt: state_cache on fetched codes needs code_cache and M % 16 == 0");
     const int64_t G = dedup ? io.n_unique : Tt * kg, S = G * n_g;
     GNNLM_REQUIRE(dk % 4 == 0 && d % 4 == 0 && dpq % 4 == 0, "hgt: d_k and the PQ dimension must be multiples of 4");
-    GNNLM_REQUIRE(dense0 || m.opq_at || dpq == d, "hgt: without OPQ the PQ dimension must equal d");
+    GNNLM_REQUIRE(dense0 || token || m.opq_at || dpq == d, "hgt: without OPQ the PQ dimension must equal d");
 
     // a ragged batch (gnnlm_hgt_forward_ragged): the packed tokens are one run of io.T rows, cut into blocks by rg
     GNNLM_REQUIRE(!rg || (nb == 1 && rg->n_tok == Tt && rg->n_blocks >= 1 && rg->block_off && rg->tiles),
@@ -335,6 +350,18 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
     } else if (ntgt && S == 0) {                         // a de-duplicated batch without a single valid neighbour
         hn_cur = b.hn[0];
         valid = b.valid;
+    } else if (ntgt && token) {
+        // layer-0 ntgt states: the embedding row of every slot's label (the no-OPQ shape of the branch below)
+        gnnlm_token_gather_t g{};
+        g.ids = dedup ? io.group_ids : io.ids; g.n_groups = G; g.left = m.left; g.right = m.right;
+        g.n_store = m.n_store; g.vals = m.vals; g.vals_itemsize = m.vals_itemsize;
+        g.n_vocab = m.n_vocab; g.d = d; g.embed = m.token_embed; g.ld_embed = m.ld_token_embed;
+        g.out_x = b.hn[0]; g.ld_x = d; g.out_valid = b.valid;
+        g.n_groups_dev = gdev;
+        TRY(token_gather(g, s));
+        hn_cur = b.hn[0];
+        valid = b.valid;
+        if (io.out_valid) GNNLM_HIP(hipMemcpyAsync(io.out_valid, b.valid, (size_t)S, hipMemcpyDeviceToDevice, s));
     } else if (ntgt) {
         // layer-0 ntgt states: PQ lookup of every slot, then the OPQ rotation (pq_wrapper.py:189-202)
         GatherParams g{};
@@ -382,6 +409,9 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
             TRY(gather_decode(gu, s));
         }
     }
+    // token store: layer 0's star edges read the embedding table itself through the neighbours' labels, whatever the depth
+    // (cached groups have no slot rows in this call, a one-layer model has none at all)
+    if (token) TRY(neighbor_labels(io.ids, Tt * kg, m.n_store, m.vals, m.vals_itemsize, m.n_vocab, b.nb_label, s));
     // V^T buffer of the GEMM path: its padding columns (t >= T) are read by the P.V GEMM against zero probabilities
     if (!fusedc) GNNLM_HIP(hipMemsetAsync(b.vt, 0, sizeof(float) * (size_t)nb * d * Tp, s));
 
@@ -459,7 +489,11 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
             else if (ntgt || dense0) { a.nb_valid = valid; a.nb_valid_stride = n_g; }        // centre slot of each group
             else if (io.fetched_valid) { a.nb_valid = io.fetched_valid; a.nb_valid_stride = io.fetched_centres_only ? 1 : n_g; }
             if (dedup) a.x_index = io.group_index;
-            if (cached && l > 0) {
+            if (token && l == 0) {
+                // X = E, one row per vocabulary entry; (i, j) is a neighbour iff its id is a row of the store and its label an entry
+                a.nb_valid = nullptr; a.x_index = b.nb_label;
+                a.X = m.token_embed; a.ldx = m.ld_token_embed; a.x_group_stride = 1;
+            } else if (cached && l > 0) {
                 a.X = io.state_cache + (int64_t)(l - 1) * io.cache_cap * d; a.ldx = d; a.x_group_stride = 1;
             } else if (l == 0 && !dense0 && dedup && io.fetched_codes) {
                 // merged groups on a sharded store: neighbour e's code row is the centre slot of its group
@@ -498,6 +532,8 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
             else if (fused) TRY(causal_attn_fused(qp, kp, vp, ldq, b.ms, d, nb, T, H, dk, m.max_intra_context, s, true));
         }
         // a_linear on the cross-type mean (0.5 folded into alpha) + residual, then LayerNorm (hgt.py:397-405)
+        // (token store with k_g <= d: b.aout held the neighbours' labels, b.nb_label, until here -- layer 0's star_attn above is their
+        // only reader and this GEMM is b.aout's first writer; see carve_hgt before moving either)
         TRY(linear(b.ms, d, w.wa_t, w.ba_t, b.aout, Tt, d, d, nullptr, 0.5f, s));
         float* ht_out = last ? io.out_tgt : b.ht[l & 1];
         TRY(layernorm(b.aout, d, w.ln_g_t, w.ln_b_t, ht_out, d, Tt, d, m.ln_eps, nullptr, s, ht_in, d));    // + h (hgt.py:403)
@@ -688,7 +724,7 @@ const char* gnnlm_target_arch(void) { return "gfx950"; }
 size_t gnnlm_sizeof(const char* name) {
     if (!name) return 0;
 #define GNNLM_SZ(t) if (!strcmp(name, #t)) return sizeof(t);
-    GNNLM_SZ(gnnlm_group_assign_t) GNNLM_SZ(gnnlm_gemm_t) GNNLM_SZ(gnnlm_gather_t) GNNLM_SZ(gnnlm_star_attn_t) GNNLM_SZ(gnnlm_chain_attn_t)
+    GNNLM_SZ(gnnlm_group_assign_t) GNNLM_SZ(gnnlm_gemm_t) GNNLM_SZ(gnnlm_gather_t) GNNLM_SZ(gnnlm_token_gather_t) GNNLM_SZ(gnnlm_star_attn_t) GNNLM_SZ(gnnlm_chain_attn_t)
     GNNLM_SZ(gnnlm_adaptive_softmax_t) GNNLM_SZ(gnnlm_dense_softmax_t) GNNLM_SZ(gnnlm_knn_interp_t) GNNLM_SZ(gnnlm_knn_interp_grid_t) GNNLM_SZ(gnnlm_knn_resim_t) GNNLM_SZ(gnnlm_hgt_layer_t)
     GNNLM_SZ(gnnlm_hgt_t) GNNLM_SZ(gnnlm_hgt_io_t) GNNLM_SZ(gnnlm_profile_entry_t) GNNLM_SZ(gnnlm_topk_t) GNNLM_SZ(gnnlm_ivfpq_scan_t) GNNLM_SZ(gnnlm_ivfpq_scan8_t) GNNLM_SZ(gnnlm_ivfpq_rescore_t) GNNLM_SZ(gnnlm_ivfpq_tau_t) GNNLM_SZ(gnnlm_ivfpq_tables_t) GNNLM_SZ(gnnlm_peer_gather_t) GNNLM_SZ(gnnlm_shards_t) GNNLM_SZ(gnnlm_ragged_t)
 #undef GNNLM_SZ
@@ -726,6 +762,11 @@ int gnnlm_bucket_rows_padded(const int64_t* rows, int64_t n, int64_t n_store, in
     return bucket_rows_padded(rows, n, n_store, rows_per_rank, world, cap, cursor, send_rows, inv, overflow, (hipStream_t)stream);
 }
 int gnnlm_pq_gather_decode(const gnnlm_gather_t* d, void* stream) { GNNLM_DESC(d); return gather_decode(*d, (hipStream_t)stream); }
+int gnnlm_token_gather(const gnnlm_token_gather_t* d, void* stream) { GNNLM_DESC(d); return token_gather(*d, (hipStream_t)stream); }
+int gnnlm_neighbor_labels(const int64_t* ids, int64_t n, int64_t n_store, const void* vals, int32_t vals_itemsize, int32_t n_vocab, int32_t* out,
+                          void* stream) {
+    return neighbor_labels(ids, n, n_store, vals, vals_itemsize, n_vocab, out, (hipStream_t)stream);
+}
 int gnnlm_star_attn(const gnnlm_star_attn_t* d, void* stream) { GNNLM_DESC(d); return star_attn(*d, (hipStream_t)stream); }
 int gnnlm_chain_attn(const gnnlm_chain_attn_t* d, void* stream) { GNNLM_DESC(d); return chain_attn(*d, (hipStream_t)stream); }
 int gnnlm_causal_softmax(float* S, int64_t n_mats, int32_t T, int64_t ld, int32_t max_ctx, void* stream) {

@@ -50,6 +50,10 @@ int lse_reduce(const float* part, int n_parts, int64_t rows, const int32_t* m_de
 int gather_decode(const GatherParams& p, hipStream_t stream);
 int pq_encode(const float* x, int64_t ldx, const float* cen, const float* norm2, int M, int dsub, int64_t n, uint8_t* codes,
               hipStream_t stream);
+// token-embedding rows of the slots' labels / labels of a neighbour-id matrix (token_gather.hip, `--reinit-nfeat`)
+int token_gather(const gnnlm_token_gather_t& p, hipStream_t stream);
+int neighbor_labels(const int64_t* ids, int64_t n, int64_t n_store, const void* vals, int itemsize, int n_vocab, int32_t* out,
+                    hipStream_t stream);
 int bucket_rows(const int64_t* rows, int64_t n, int64_t n_store, int64_t per, int world, int self, int64_t* counts,
                 int64_t* cursor, int64_t* send_rows, int32_t* inv, hipStream_t stream);
 int gather_rows_peer(const gnnlm_peer_gather_t& d, hipStream_t stream);

@@ -20,7 +20,7 @@ import torch
 from . import ops
 from .adaptive_softmax import AdaptiveSoftmax
 from .dense_softmax import DenseSoftmax
-from .hgt import HGT, CodeStore, NeighborGraph
+from .hgt import HGT, CodeStore, NeighborGraph, TokenStore
 
 
 @dataclass
@@ -43,7 +43,7 @@ class BlockBatch:
 
 
 class GnnLmEngine:
-    def __init__(self, hgt: HGT, asm: "AdaptiveSoftmax | DenseSoftmax", store: CodeStore, left: int, right: int,
+    def __init__(self, hgt: HGT, asm: "AdaptiveSoftmax | DenseSoftmax", store: "CodeStore | TokenStore", left: int, right: int,
                  max_intra_context: int = 0, fetcher=None, fetch_vals: bool = False, precision=None):
         self.hgt, self.asm, self.store = hgt, asm, store
         if precision is not None:                    # None: whatever hgt / asm already carry

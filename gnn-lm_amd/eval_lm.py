@@ -58,6 +58,11 @@ def get_parser():
     p.add_argument("--graph", action="store_true", default=False)
     p.add_argument("--neighbor-context", default="(2, 2)")
     p.add_argument("--use-precompute-feat", action="store_true", default=False)
+    p.add_argument("--reinit-nfeat", action="store_true", default=False,
+                   help="use word embedding as neighbor node feature instead of cached representation (the task flag of "
+                        "fairseq/tasks/language_modeling.py:151-153): no train_dstore/quantized-keys.npy and no quantizer are read; the "
+                        "store is train_dstore/vals.npy plus the checkpoint's embed_tokens as one [V, d] table.  Not with --store sharded | peer "
+                        "(there is nothing to shard)")
     p.add_argument("--invalid-neighbor-context", default=1536, type=int)
     p.add_argument("--gcn-k", default=1024, type=int)
     p.add_argument("--gcn-context-window", default=0, type=int)
@@ -439,8 +444,30 @@ def check_tables(args, info, n_store):
         logger.info("targets of %s_dstore/vals.npy == token stream of %s.bin (%d tokens)", split, split, n_tok)
 
 
+def check_store_mode(args):
+    """``--reinit-nfeat`` has one label table and one embedding table, whole on every rank: the code-table layouts are refused."""
+    if getattr(args, "reinit_nfeat", False) and getattr(args, "store", "auto") in ("sharded", "peer"):
+        raise ValueError(f"--store {args.store} with --reinit-nfeat: there is no code table to shard (the store is the 4-byte label table and "
+                         "one [V, d] embedding table, whole on every rank); use --store auto or replicated")
+
+
+def check_labels(vals, vocab, what="train_dstore/vals.npy"):
+    """One pass on the device: every label must be an entry of the vocabulary (it indexes the embedding table).  ValueError names
+    the first bad row."""
+    if vals.numel() == 0:
+        return
+    lo, hi = torch.aminmax(vals)                                 # the one pass; the first bad row is looked for only when there is one
+    if int(lo) < 0 or int(hi) >= int(vocab):
+        bad = (vals < 0) | (vals >= int(vocab))
+        at = int(bad.to(torch.uint8).argmax())
+        raise ValueError(f"{what} row {at} = {int(vals[at])}: not a label of the {int(vocab)}-entry vocabulary (--reinit-nfeat reads "
+                         "embed_tokens at every label)")
+
+
 def load_tables(args, device, shard=None):
-    """``shard`` (dist.Shard): upload only the rows of the code table this rank holds (its key range plus the halo)."""
+    """``shard`` (dist.Shard): upload only the rows of the code table this rank holds (its key range plus the halo).
+    With ``--reinit-nfeat`` the code table is neither opened nor required (language_modeling.py:273-278): the train split's labels
+    (``neighbor_tokens``, :291-293) are uploaded instead, as ``train_vals``."""
     split, data = args.gen_subset, args.data
     info = json.load(open(os.path.join(dstore_path(data, split), "info.json")))
     tinfo = json.load(open(os.path.join(dstore_path(data, "train"), "info.json")))        # language_modeling.py:266-272
@@ -453,6 +480,23 @@ def load_tables(args, device, shard=None):
     targets = np.memmap(value_path(data, split), mode="r", shape=(n_tok,),
                         dtype=vals_dtype(info["dstore_fp16"], info.get("vocab_size")))
     nbrs = np.memmap(neighbor_path(data, split, args.gcn_k), mode="r", dtype=np.int64, shape=(n_tok, args.gcn_k))
+    if getattr(args, "reinit_nfeat", False):
+        if shard is not None:
+            raise ValueError("--reinit-nfeat: the label table is never sharded")
+        tpath, n_store = value_path(data, "train"), tinfo["dstore_size"]
+        vdt = np.dtype(vals_dtype(tinfo["dstore_fp16"], tinfo.get("vocab_size")))
+        if not os.path.exists(tpath) or os.path.getsize(tpath) != n_store * vdt.itemsize:
+            raise ValueError(f"{tpath}: expected {n_store} labels of {vdt} ({n_store * vdt.itemsize} bytes) as train_dstore/info.json says")
+        up = lambda a: torch.from_numpy(np.array(a)).to(device)
+        train_vals = up(np.memmap(tpath, mode="r", shape=(n_store,), dtype=vdt))
+        vocab = info.get("vocab_size") or tinfo.get("vocab_size")
+        if vocab:
+            check_labels(train_vals, vocab, tpath)
+        tg = up(targets).long()
+        return {"n_tok": n_tok, "d": d, "vocab": info.get("vocab_size"), "n_store": n_store,
+                "feats": up(feats), "targets": tg, "nbrs": up(nbrs), "codes": None, "train_vals": train_vals, "codes_row0": 0,
+                "labels_checked": int(vocab) if vocab else None,        # (main() checks only what was not checked here)
+                "no_pad": not bool(tg.eq(_Dict().pad()).any())}
     codes = np.load(quantized_feature_path(data, "train"), mmap_mode="r")                  # language_modeling.py:274-276
     if codes.ndim != 2 or codes.dtype != np.uint8 or codes.shape[0] != tinfo["dstore_size"]:
         raise ValueError(f"{quantized_feature_path(data, 'train')}: {codes.dtype} {codes.shape}, expected uint8 "
@@ -481,6 +525,8 @@ def main(args, tables=None, model=None):
         raise ValueError("--save-knnlm-dstore needs --dstore-mmap")
     if args.knnlm and args.save_knnlm_dstore:
         raise ValueError("Cannot use knnlm while trying to build the datastore!")
+    check_store_mode(args)
+    reinit = bool(getattr(args, "reinit_nfeat", False))
     sweep = parse_sweep(args)
     args.sweep = sweep                                                                     # (read by the scorer)
     break_mode = getattr(args, "sample_break_mode", None) or "none"
@@ -517,7 +563,8 @@ def main(args, tables=None, model=None):
     else:
         device = torch.device(args.device)
         torch.cuda.set_device(device)
-    store_mode = args.store if args.store != "auto" else ("sharded" if world > 1 else "replicated")
+    # (--reinit-nfeat: `auto` is the one table in any world size -- labels and embeddings are whole on every rank)
+    store_mode = args.store if args.store != "auto" else ("sharded" if world > 1 and not reinit else "replicated")
     if world == 1 and store_mode != "replicated" and not os.environ.get("GNNLM_EVAL_FORCE_EXCHANGE"):
         store_mode = "replicated"                                                           # one rank owns every row
     nc = ast.literal_eval(str(args.neighbor_context))                                      # language_modeling.py:295
@@ -531,7 +578,8 @@ def main(args, tables=None, model=None):
     tabs = tables if tables is not None else load_tables(args, device, shard)
     overrides = ast.literal_eval(args.model_overrides)
     if model is None:
-        model, margs = GnnLmModel.from_checkpoint(args.path, device, overrides, vocab_size=tabs["vocab"])
+        model, margs = GnnLmModel.from_checkpoint(args.path, device, overrides, vocab_size=tabs["vocab"], reinit_nfeat=reinit,
+                                                  precision="fp16" if args.fp16 else None)
     # a sweep over the ratio runs the base branch even when the run's own ratio is 0 (the model leaves both unmixed rows per batch)
     model.keep_branches = bool(sweep and len(sweep) > 3)
     if args.fp16:
@@ -548,7 +596,15 @@ def main(args, tables=None, model=None):
         logger.info("output layer: dense softmax, V = %d, bias %s, route %s", head_mod.vocab, "yes" if head_mod.bias is not None else "no",
                     head_mod.route_name())
     fetcher = None
-    if shard is None:
+    if reinit:
+        if getattr(model, "token_embed", None) is None:
+            raise ValueError("--reinit-nfeat: the model handed in was not built with reinit_nfeat=True (no token-embedding table)")
+        if tabs.get("train_vals") is None:
+            raise ValueError("--reinit-nfeat: the tables handed in carry no train_vals (the train split's labels)")
+        if tabs.get("labels_checked") != model.token_embed.vocab:                          # tables handed in, or an info.json without a vocabulary
+            check_labels(tabs["train_vals"], model.token_embed.vocab)
+        store = model.make_store(None, tabs["n_store"], device, vals=tabs["train_vals"])
+    elif shard is None:
         store = model.make_store(tabs["codes"], tabs["n_store"], device)
     else:
         from .dist import PeerMappedFetcher, ShardedFetcher

@@ -46,6 +46,34 @@ class CodeStore:
     rows_per_rank: int = 0
 
 
+@dataclass
+class TokenStore:
+    """The store of ``--reinit-nfeat`` (fairseq/tasks/language_modeling.py:151-153: "use word embedding as neighbor node feature
+    instead of cached representation"): the label table and the token-embedding table, both whole in HBM -- no codes are loaded
+    (:273-278) and a node's feature is ``embed[vals[row]]`` (fairseq/models/transformer.py:1046-1048).  Accepted wherever
+    ``NeighborGraph.store`` takes a :class:`CodeStore`; there is nothing to shard (413 MB of labels + one [V, d] table)."""
+    embed: torch.Tensor                  # f32 [V, d]  (token_embed.TokenEmbedding.table)
+    vals: torch.Tensor                   # int16/int32 [n_store]  (train_dstore/vals.npy, language_modeling.py:291-293)
+    n_store: int
+    # what the code-store consumers ask a store for: one whole table, no codec
+    row0 = 0
+    codes = centroids = A = b = shards = None
+    rows_per_rank = 0
+
+    @property
+    def n_vocab(self):
+        return self.embed.shape[0]
+
+
+def is_token_store(store):
+    return getattr(store, "embed", None) is not None
+
+
+def store_table(store):
+    """The tensor whose identity and in-place version name the store's content: the code table, or the embedding table."""
+    return store.embed if is_token_store(store) else store.codes
+
+
 def shards_device_ptr(store):
     """Device address of the store's gnnlm_shards_t (built once, kept alive on the store); None for a one-table store."""
     if store is None or not getattr(store, "shards", None):
@@ -75,7 +103,7 @@ class NeighborGraph:
     T: int
     left: int
     right: int
-    store: CodeStore
+    store: "CodeStore | TokenStore"
     tgt_h: Optional[torch.Tensor] = None            # f32 [n_blocks*T, d]  (graph.nodes['tgt'].data['h'])
     fetched_codes: Optional[torch.Tensor] = None    # sharded store: codes of every slot, already fetched
     fetched_valid: Optional[torch.Tensor] = None
@@ -187,7 +215,7 @@ def prepare_hgt_weights(sd: Dict[str, torch.Tensor], n_layers: int, n_heads: int
         for j, nm in enumerate("qkv"):
             lay[f"w{nm}_t"], lay[f"b{nm}_t"] = qkv_w[j * d:(j + 1) * d], qkv_b[j * d:(j + 1) * d]
         layers.append((lay, din))
-    codec = {"centroids": store.centroids.to(device, torch.float32).contiguous()}
+    codec = {} if store.centroids is None else {"centroids": store.centroids.to(device, torch.float32).contiguous()}   # (a token store has no codec)
     if A is not None:
         codec["opq_at"] = dev32(A.t())
         if bq is not None:
@@ -329,7 +357,7 @@ class HGT(nn.Module):
         ver = lambda t: None if t is None else (t.data_ptr(), t._version, tuple(t.shape))
         if self._plist is None:                                   # (walking the module tree costs ~50 us per call: kept, dropped by load_state_dict)
             self._plist = list(self.parameters())
-        key = (str(device), ver(store.centroids), ver(store.A), ver(store.b),
+        key = (str(device), ver(store.centroids), ver(store.A), ver(store.b), is_token_store(store),
                tuple(ver(p) for p in self._plist))
         if self._prepared is not None and self._prepared["key"] == key:
             self._bind_store(self._prepared["model"], store)
@@ -345,9 +373,10 @@ class HGT(nn.Module):
         m = _lib.gnnlm_hgt_t()
         m.d, m.n_heads, m.n_layers = self.hidden_dim, self.n_heads, self.n_layers
         m.ln_eps = self.gcs[0].norms[0].eps
-        M, _, dsub = store.centroids.shape
-        m.M, m.dsub = M, dsub
-        m.centroids = codec["centroids"].data_ptr()
+        if not is_token_store(store):                            # (a token store folds nothing of a codec: layer 0's din is d)
+            M, _, dsub = store.centroids.shape
+            m.M, m.dsub = M, dsub
+            m.centroids = codec["centroids"].data_ptr()
         if "opq_at" in codec:
             m.opq_at = codec["opq_at"].data_ptr()
         if "opq_nba" in codec:
@@ -366,13 +395,16 @@ class HGT(nn.Module):
         # every cached group is taken for a VALID neighbour (the cached path carries no per-group validity): cache only when every
         # in-range row can be read -- the whole table resident, its shards mapped, or a fetcher that brings what is not local.  A
         # partial local table without any of these runs un-cached, where rows that are not local are excluded from the star softmax.
-        if G.fetcher is None and shards_device_ptr(store) is None and not (store.row0 == 0 and store.codes.shape[0] >= store.n_store):
+        if not is_token_store(store) and G.fetcher is None and shards_device_ptr(store) is None and \
+                not (store.row0 == 0 and store.codes.shape[0] >= store.n_store):
             return None
         c = self.state_cache
         # everything the cached states are a function of: the folded weights (prep key: parameters + codec), the GEMM arithmetic,
         # the context shape, and the code table itself (identity AND in-place version)
-        key = (prep["key"], id(store), store.codes.data_ptr(), store.codes._version, store.n_store, self.gemm_precision,
-               G.left, G.right, G.max_intra_context, G.fetcher is not None)
+        # (a token store: the embedding table AND the label table)
+        tab, lab = store_table(store), (store.vals if is_token_store(store) else None)
+        key = (prep["key"], id(store), tab.data_ptr(), tab._version, store.n_store, self.gemm_precision,
+               G.left, G.right, G.max_intra_context, G.fetcher is not None, None if lab is None else (lab.data_ptr(), lab._version))
         if c is not None and (getattr(c, "key", None) != key):
             c = self.state_cache = None                                       # other weights / store / arithmetic: the states are stale
         if c is None:
@@ -427,6 +459,12 @@ class HGT(nn.Module):
     @staticmethod
     def _bind_store(m, store):
         """(Re)point the descriptor at the store's tables: cheap, done on every forward."""
+        if is_token_store(store):
+            m.codes, m.shards, m.row0, m.n_local = None, None, 0, store.n_store
+            m.vals, m.vals_itemsize, m.n_store = store.vals.data_ptr(), store.vals.element_size(), store.n_store
+            m.token_embed, m.ld_token_embed, m.n_vocab = store.embed.data_ptr(), store.embed.stride(0), store.embed.shape[0]
+            return
+        m.token_embed, m.ld_token_embed, m.n_vocab = None, 0, 0
         m.codes = store.codes.data_ptr()
         m.vals, m.vals_itemsize = (store.vals.data_ptr(), store.vals.element_size()) if store.vals is not None else (None, 4)
         m.n_store, m.row0, m.n_local = store.n_store, store.row0, store.codes.shape[0]
@@ -470,8 +508,11 @@ class HGT(nn.Module):
             st = G.store
             lin = lambda x, mod: ops.gemm_nt(x, mod.weight.detach().to(tgt.device).contiguous(),
                                              bias=mod.bias.detach().to(tgt.device).contiguous())
-            dec = ops.pq_gather_decode(st.codes, st.centroids, G.ids.reshape(-1).contiguous(), G.left, G.right,
-                                       n_store=st.n_store, row0=st.row0)
+            if is_token_store(st):                                      # embed_tokens(labels) of every slot (transformer.py:1046-1048)
+                dec = ops.token_gather(st.embed, st.vals, G.ids.reshape(-1).contiguous(), G.left, G.right, n_store=st.n_store)
+            else:
+                dec = ops.pq_gather_decode(st.codes, st.centroids, G.ids.reshape(-1).contiguous(), G.left, G.right,
+                                           n_store=st.n_store, row0=st.row0)
             x0 = dec["x"]
             if st.A is not None:                                        # (x - b) @ A  (pq_wrapper.py:198-202)
                 At = st.A.t().contiguous()
@@ -502,6 +543,12 @@ class HGT(nn.Module):
         io.tgt_feats, io.ids = tgt.data_ptr(), ids.data_ptr()
         fetched = (G.fetched_codes, G.fetched_valid, G.fetched_index, G.fetched_centres_only)
         st, fetcher = G.store, G.fetcher
+        if is_token_store(st):
+            if fetcher is not None or G.fetched_codes is not None:
+                raise ValueError("a token store (--reinit-nfeat) is one whole table: there are no code rows to fetch")
+            if st.vals.shape[0] < st.n_store or st.embed.shape[1] != self.in_dim:
+                raise ValueError(f"token store: {st.vals.shape[0]} labels for n_store = {st.n_store}, embedding dimension "
+                                 f"{st.embed.shape[1]} for in_dim = {self.in_dim}")
         if fetcher is not None and adapted:
             raise NotImplementedError("input adapters with a sharded store are not built")
         if adapted:
@@ -537,7 +584,7 @@ class HGT(nn.Module):
             if merged:
                 io.group_ids, io.n_unique, io.group_index = group_ids.data_ptr(), flat.numel(), group_index.data_ptr()
                 io.n_unique_dev = counters.data_ptr()
-                if self.dedup_rows and fetcher is None and (G.left or G.right):
+                if self.dedup_rows and fetcher is None and (G.left or G.right) and not is_token_store(st):   # (tied to the OPQ fold)
                     # layer 0's K / V once per distinct datastore ROW among the groups' slots (neighbouring groups share rows)
                     rt = self._row_table(st.n_store, tgt.device)
                     if rt is not None:

@@ -18,7 +18,7 @@ import torch
 from ._lib import raw_stream as _lib_raw_stream
 from .adaptive_softmax import AdaptiveSoftmax
 from .dense_softmax import DenseSoftmax
-from .hgt import HGT, CodeStore, NeighborGraph
+from .hgt import HGT, CodeStore, NeighborGraph, TokenStore, store_table
 from .pq_wrapper import TorchPQCodec
 
 
@@ -28,8 +28,11 @@ class GnnLmModel(torch.nn.Module):
     orig_prob_ratio, keep_branches, short_cut = 0.0, False, False
 
     def __init__(self, hgt: HGT, asm: Union[AdaptiveSoftmax, DenseSoftmax], quantizer: TorchPQCodec = None, orig_prob_ratio: float = 0.0,
-                 short_cut: bool = False, precision=None):
+                 short_cut: bool = False, precision=None, token_embed=None):
         super().__init__()
+        # `--reinit-nfeat` (language_modeling.py:151-153): the neighbour features are rows of this token_embed.TokenEmbedding
+        # instead of decoded PQ codes; no quantizer is involved
+        self.token_embed = token_embed
         # orig_prob_ratio = alpha > 0 (transformer.py:987-1005,1056-1062,1075-1077): every token is scored with
         #   logsumexp(log(alpha) + log p_asm(target | h), log(1 - alpha) + log p_asm(target | x))
         # h the base LM's feature, x the GNN output, both through the same head (`asm`: the tied adaptive softmax, or the dense
@@ -84,7 +87,7 @@ class GnnLmModel(torch.nn.Module):
         import dataclasses
         key = ("fwd", tuple(src_tokens.shape), tuple(graph.ids.shape), graph.tgt_h.dtype, graph.left, graph.right, graph.max_intra_context,
                self.precision,                                                      # (a captured launch has its arithmetic baked in)
-               id(graph.store), graph.store.codes.data_ptr(), _lib_raw_stream())      # (one set of static buffers per stream)
+               id(graph.store), store_table(graph.store).data_ptr(), _lib_raw_stream())      # (one set of static buffers per stream)
         if self._graphs is None:
             self._graphs, self._static_x = {}, set()
         e = self._graphs.get(key)
@@ -222,8 +225,11 @@ class GnnLmModel(torch.nn.Module):
         raise NotImplementedError("the dense [B, T, V] tensor is never materialised; use target_log_probs()")
 
     @classmethod
-    def from_checkpoint(cls, path, device, overrides=None, vocab_size=None, quantizer=None):
-        """Load a reference ``.pt`` ({'args': Namespace, 'model': state_dict}, checkpoint_utils.py:161-176)."""
+    def from_checkpoint(cls, path, device, overrides=None, vocab_size=None, quantizer=None, reinit_nfeat=False, precision=None):
+        """Load a reference ``.pt`` ({'args': Namespace, 'model': state_dict}, checkpoint_utils.py:161-176).
+        ``reinit_nfeat`` (the task flag ``--reinit-nfeat``): no quantizer is needed; the token-embedding table is built instead.
+        ``precision`` (a name of ``ops.PRECISIONS``, e.g. "fp16" for ``--fp16``) is set on the model AND is what the table's GEMMs run
+        under: the table is built once, so a model whose precision is changed afterwards refuses to make a store (``make_store``)."""
         ckpt = torch.load(path, map_location="cpu", weights_only=False)
         args = ckpt["args"] if isinstance(ckpt["args"], Namespace) else Namespace(**ckpt["args"])
         for k_, v in (overrides or {}).items():
@@ -233,7 +239,16 @@ class GnnLmModel(torch.nn.Module):
         hgt = HGT(in_dim=d, hidden_dim=getattr(args, "decoder_gcn_dim", d), out_dim=d, n_layers=L, n_heads=H)
         hgt.load_state_dict({k_[len("decoder.hgt_decoder."):]: v for k_, v in sd.items()
                              if k_.startswith("decoder.hgt_decoder.")})
-        if quantizer is None:
+        token_embed = None
+        if reinit_nfeat:
+            from . import ops
+            from .token_embed import TokenEmbedding
+            token_embed = TokenEmbedding.from_state_dict(sd, args, device, ops.precision_value(precision or "f32"))
+            if token_embed.d != hgt.in_dim:
+                raise ValueError(f"--reinit-nfeat: the embedding table has {token_embed.d} columns, the graph decoder reads {hgt.in_dim}")
+            if vocab_size is not None and int(vocab_size) != token_embed.vocab:
+                raise ValueError(f"vocabulary mismatch: the dictionary has {int(vocab_size)} entries, embed_tokens has {token_embed.vocab} rows")
+        elif quantizer is None:
             if "decoder.tgt_quantizer.centroids_torch" in sd:
                 quantizer = TorchPQCodec.from_arrays(sd["decoder.tgt_quantizer.centroids_torch"].numpy(),
                                                      sd["decoder.tgt_quantizer.A"].numpy() if "decoder.tgt_quantizer.A" in sd else None,
@@ -242,22 +257,34 @@ class GnnLmModel(torch.nn.Module):
                 quantizer = TorchPQCodec.from_file(args.quantizer_path)      # .npz or the recipe's faiss `quantizer` file
             else:
                 raise ValueError("no quantizer: the checkpoint has no decoder.tgt_quantizer.* buffers "
-                                 "(fairseq_cli/convert_ckpt.py) and quantizer_path does not name a file")
+                                 "(fairseq_cli/convert_ckpt.py) and quantizer_path does not name a file; a checkpoint trained with "
+                                 "--reinit-nfeat has none and is scored with --reinit-nfeat (reinit_nfeat=True)")
         if getattr(args, "adaptive_softmax_cutoff", None) is None or "decoder.adaptive_softmax.head.class_proj.weight" not in sd:
             # no adaptive softmax (transformer.py:845): the plain output layer of a `--arch transformer_lm` checkpoint
             asm = DenseSoftmax.from_state_dict(sd, args, device)
             if vocab_size is not None and int(vocab_size) != asm.vocab:
                 raise ValueError(f"vocabulary mismatch: the dictionary has {int(vocab_size)} entries, the checkpoint's output layer "
                                  f"has {asm.vocab} rows")
-            return cls(hgt, asm, quantizer, getattr(args, "orig_prob_ratio", 0.0), getattr(args, "short_cut", False)), args
+            return cls(hgt, asm, quantizer, getattr(args, "orig_prob_ratio", 0.0), getattr(args, "short_cut", False), precision=precision,
+                       token_embed=token_embed), args
         cut = [int(c) for c in str(args.adaptive_softmax_cutoff).split(",")]
         if vocab_size is None:
             n_bands = sd["decoder.adaptive_softmax.head.class_proj.weight"].shape[0] + 1
             vocab_size = cut[0] + sum(sd[f"decoder.embed_tokens.embeddings.{i}.0.weight"].shape[0] for i in range(1, n_bands))
         asm = AdaptiveSoftmax.from_state_dict(sd, cut, vocab_size, device)
-        return cls(hgt, asm, quantizer, getattr(args, "orig_prob_ratio", 0.0), getattr(args, "short_cut", False)), args
+        return cls(hgt, asm, quantizer, getattr(args, "orig_prob_ratio", 0.0), getattr(args, "short_cut", False), precision=precision,
+                   token_embed=token_embed), args
 
-    def make_store(self, codes, n_store, device, vals=None, row0=0) -> CodeStore:
+    def make_store(self, codes, n_store, device, vals=None, row0=0) -> "CodeStore | TokenStore":
+        if getattr(self, "token_embed", None) is not None:            # --reinit-nfeat: labels + embedding table, no codes
+            if vals is None or row0 != 0:
+                raise ValueError("--reinit-nfeat: the store is the whole label table (vals) of the train split; there is nothing to shard")
+            from . import ops
+            built = self.token_embed.precision
+            if built is not None and ops.precision_name(built) != self.precision:
+                raise ValueError(f"--reinit-nfeat: the token-embedding table was built under precision {ops.precision_name(built)!r}, the model "
+                                 f"now runs {self.precision!r}; pass precision= to from_checkpoint so that one arithmetic serves both")
+            return TokenStore(embed=self.token_embed.table, vals=vals.to(device).contiguous(), n_store=n_store)
         q = self.tgt_quantizer
         t = lambda a: a.to(device).contiguous()
         return CodeStore(codes=codes, centroids=t(q.centroids_torch), n_store=n_store, row0=row0, vals=vals,

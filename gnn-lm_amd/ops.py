@@ -156,6 +156,66 @@ def pq_gather_decode(codes, centroids, ids, left=0, right=0, n_store=None, row0=
     return out
 
 
+def token_gather(embed, vals, ids, left=0, right=0, n_store=None, n_vocab=None, want_x=True, want_labels=False, want_valid=True,
+                 n_groups_dev=None, out_x=None):
+    """``--reinit-nfeat``: the token-embedding rows of the slots of each centre row in ``ids`` (flattened) -- the counterpart of
+    :func:`pq_gather_decode` for a label-only store (transformer.py:1046-1048).  embed [V, d] f32 (row stride may exceed d), vals
+    [n_store] int16 / int32 (the whole label table).  Returns a dict (x [n_slots, d] with zero rows for invalid slots, labels
+    int32 with -1, valid uint8).  ``out_x``: write the rows into this [n_slots, >= d] buffer instead (its row stride is used)."""
+    _dev(embed, vals, ids, n_groups_dev, out_x)
+    _f32(embed, out_x)
+    _dtype(ids, torch.int64, "ids"), _dtype(n_groups_dev, torch.int32, "n_groups_dev")
+    if vals.dtype not in (torch.int16, torch.int32):
+        raise TypeError(f"vals: expected int16 or int32, got {vals.dtype}")
+    n_g = 1 + left + right
+    G = ids.numel()
+    S = G * n_g
+    dev = embed.device
+    t = _lib.gnnlm_token_gather_t()
+    t.ids, t.n_groups, t.left, t.right = ids.data_ptr(), G, left, right
+    t.n_store = n_store if n_store is not None else vals.shape[0]
+    if t.n_store > vals.shape[0]:
+        raise ValueError(f"token_gather: n_store = {t.n_store} but the label table has {vals.shape[0]} rows (it is never sharded)")
+    t.vals, t.vals_itemsize = vals.data_ptr(), vals.element_size()
+    t.n_vocab, t.d = (n_vocab if n_vocab is not None else embed.shape[0]), embed.shape[1]
+    if t.n_vocab > embed.shape[0]:
+        raise ValueError(f"token_gather: n_vocab = {t.n_vocab} but the table has {embed.shape[0]} rows")
+    t.embed, t.ld_embed = embed.data_ptr(), embed.stride(0)
+    out = {}
+    if want_x or out_x is not None:
+        if out_x is None:
+            out_x = torch.empty(S, embed.shape[1], device=dev, dtype=torch.float32)
+        assert out_x.shape[0] >= S and out_x.shape[1] >= embed.shape[1]
+        out["x"] = out_x
+        t.out_x, t.ld_x = out_x.data_ptr(), out_x.stride(0)
+    if want_labels:
+        out["labels"] = torch.empty(S, device=dev, dtype=torch.int32)
+        t.out_labels = out["labels"].data_ptr()
+    if want_valid:
+        out["valid"] = torch.empty(S, device=dev, dtype=torch.uint8)
+        t.out_valid = out["valid"].data_ptr()
+    if n_groups_dev is not None:
+        t.n_groups_dev = n_groups_dev.data_ptr()
+    call_desc("gnnlm_token_gather", t)
+    return out
+
+
+def neighbor_labels(ids, vals, n_store=None, n_vocab=None):
+    """int32, shaped like ``ids``: the label of every neighbour, -1 where ``ids`` names no row of the store (or the label lies
+    outside [0, n_vocab)) -- the index through which layer 0's star edges read the embedding table (``gnnlm_star_attn_t.x_index``)."""
+    _dev(ids, vals)
+    _dtype(ids, torch.int64, "ids")
+    if vals.dtype not in (torch.int16, torch.int32):
+        raise TypeError(f"vals: expected int16 or int32, got {vals.dtype}")
+    n_store = n_store if n_store is not None else vals.shape[0]
+    if n_store > vals.shape[0]:
+        raise ValueError(f"neighbor_labels: n_store = {n_store} but the label table has {vals.shape[0]} rows")
+    out = torch.empty(ids.shape, device=ids.device, dtype=torch.int32)
+    call("gnnlm_neighbor_labels", ptr(ids), ids.numel(), n_store, ptr(vals), vals.element_size(),
+         n_vocab if n_vocab is not None else 2 ** 31 - 1, ptr(out), stream())
+    return out
+
+
 def pq_lookup_direct(codes, centroids):
     """x[n, m*dsub:(m+1)*dsub] = centroids[m, codes[n, m]] for an explicit code matrix (no store)."""
     _dev(codes, centroids)
@@ -173,7 +233,7 @@ def pq_lookup_direct(codes, centroids):
 
 
 def star_attn(U, ids, codes=None, centroids=None, row0=0, X=None, x_group_stride=1, codes_direct=0, n_store=None,
-              nb_valid=None, nb_valid_stride=1, shards=None, rows_per_rank=0):
+              nb_valid=None, nb_valid_stride=1, shards=None, rows_per_rank=0, x_index=None):
     """n_store: rows of the whole store (ids >= n_store are not neighbours; default: the rows of ``codes``);
     nb_valid (uint8): validity byte of neighbour (i, j) at [(i*kg + j) * nb_valid_stride];
     shards = [(codes_g [rows_g, M], first global row), ...] + rows_per_rank: a range-sharded table whose shards are all
@@ -181,6 +241,7 @@ def star_attn(U, ids, codes=None, centroids=None, row0=0, X=None, x_group_stride
     _dev(U, ids, codes, centroids, X, nb_valid)
     _f32(U, centroids, X)
     _dtype(ids, torch.int64, "ids"), _dtype(codes, torch.uint8, "codes"), _dtype(nb_valid, torch.uint8, "nb_valid")
+    _dtype(x_index, torch.int32, "x_index"), _dev(x_index)
     T, H, D = U.shape
     kg = ids.shape[1]
     Z = torch.empty_like(U)
@@ -207,6 +268,8 @@ def star_attn(U, ids, codes=None, centroids=None, row0=0, X=None, x_group_stride
     a.n_store = n_store or 0
     if nb_valid is not None:
         a.nb_valid, a.nb_valid_stride = nb_valid.data_ptr(), nb_valid_stride
+    if x_index is not None:                                     # [T, kg] int32: dense row / validity byte of (i, j) (-1: not a neighbour)
+        a.x_index = x_index.data_ptr()
     call_desc("gnnlm_star_attn", a)
     if shards:
         Z._gnnlm_keep = keep                                    # the device copy of the shard table outlives the queued launch

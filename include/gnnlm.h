@@ -160,6 +160,44 @@ int gnnlm_pq_encode(const float* x, int64_t ldx, const float* centroids, const f
                     int64_t n, uint8_t* codes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * `--reinit-nfeat` ("use word embedding as neighbor node feature instead of cached representation",
+ * fairseq/tasks/language_modeling.py:151-153): the datastore is the label table alone (no quantized-keys.npy is loaded,
+ * :273-278; the graph builder attaches only `labels` to the ntgt nodes, fairseq/data/token_block_dataset.py:369-371,392-394,
+ * 407-410) and a node's feature is the token embedding of its label,
+ *     ntgt_feat = self.embed_tokens(graph.nodes["ntgt"].data["labels"])         fairseq/models/transformer.py:1046-1048
+ * (embed_tokens called directly: no embed_scale, no positions, no project_in_dim).  `embed` is that table materialised once,
+ * [n_vocab, d] f32 with row stride ld_embed (gnn-lm_amd/token_embed.py, imported as gnnlm_amd.token_embed: per band emb_i . proj_i^T of AdaptiveInput,
+ * fairseq/modules/adaptive_input.py:63-74, or embed_tokens.weight itself).  Additive to ABI 12: a new struct and new entries.
+ *
+ * gnnlm_token_gather is the counterpart of gnnlm_pq_gather_decode: the same slot order (centre o, then o-left..o-1, then
+ * o+1..o+right) and the same validity rule (ids[g] >= 0 and 0 <= row < n_store); in addition a slot whose label lies outside
+ * [0, n_vocab) is invalid (memory safety only: the loader refuses such a table).  out_x [n_slots, d] (row stride ld_x) gets
+ * embed[vals[row]] -- a copy, bit for bit -- and zero rows for invalid slots; out_labels the label (-1: invalid); out_valid
+ * 1 / 0.  Each output is optional.  Only the first min(n_groups, *n_groups_dev) groups are processed; nothing else is written.
+ * d % 4 == 0, ld_embed % 4 == 0, ld_x % 4 == 0, embed and out_x 16-byte aligned; vals is the WHOLE table [n_store].
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct gnnlm_token_gather {
+    const int64_t* ids;        /* [n_groups] centre rows */
+    int64_t n_groups;
+    int32_t left, right;
+    int64_t n_store;
+    const void* vals;          /* [n_store] int16 / int32 labels (neighbor_tokens, language_modeling.py:291-293) */
+    int32_t vals_itemsize;     /* 2 or 4 */
+    int32_t n_vocab, d;
+    const float* embed;  int64_t ld_embed;   /* [n_vocab, d] */
+    float* out_x;  int64_t ld_x;   /* optional [n_groups*(1+left+right), d], zero rows for invalid slots */
+    int32_t* out_labels;       /* optional [n_slots], -1 for invalid */
+    uint8_t* out_valid;        /* optional [n_slots] */
+    const int32_t* n_groups_dev;   /* optional (DEVICE int32): only the first min(n_groups, *n_groups_dev) groups are processed */
+} gnnlm_token_gather_t;
+int gnnlm_token_gather(const gnnlm_token_gather_t* desc, void* stream);
+/* out[e] = vals[ids[e]] for the n entries of a neighbour-id matrix, or -1 where ids[e] is not a neighbour (ids[e] < 0,
+ * ids[e] >= n_store, or a label outside [0, n_vocab)): the index through which the star edges of layer 0 read the embedding
+ * table directly (gnnlm_star_attn_t: X = embed, x_group_stride = 1, x_index = out) -- no [n_slots, d] buffer. */
+int gnnlm_neighbor_labels(const int64_t* ids, int64_t n, int64_t n_store, const void* vals, int32_t vals_itemsize,
+                          int32_t n_vocab, int32_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * ('ntgt','inter','tgt') attention with the neighbour-side projections absorbed into the query:
  *   s[i,h,j] = x_j . U[i,h,:]  (valid j only),  alpha = softmax_j,  Z[i,h,:] = sum_j alpha x_j
  * x_j is decoded on the fly from PQ codes (codes != NULL) or read from dense rows (X != NULL).
@@ -649,6 +687,15 @@ typedef struct gnnlm_hgt {
     int32_t gemm_precision;    /* precision of the GEMMs (see gnnlm_gemm_t.precision); 0 = exact f32, 3 = fp16 operands
                                   (`eval_lm --fp16`; attention, LayerNorm and everything that is not a GEMM stay f32) */
     const gnnlm_shards_t* shards;  /* ABI 4 (DEVICE pointer): the code table is this set of mapped shards instead of `codes` */
+    /* Appended within ABI 12 (additive: members at the end, zero = off).  `--reinit-nfeat` (language_modeling.py:151-153,
+     * transformer.py:1046-1048): the ntgt features are rows of the token-embedding table, x(r) = token_embed[vals[r]], instead of
+     * decoded PQ codes.  With token_embed set the codec fields (M, dsub, centroids, opq_*, codes, shards, row0, n_local) are not
+     * read, layer 0's `din` is d, `vals` (the whole label table, [n_store]) is required, and fetched codes / the row-keyed K / V
+     * of ABI 11 are not available.  Layer 0's star edges read the table through gnnlm_neighbor_labels (no [n_slots, d] buffer
+     * for a one-layer model, whose workspace is then no larger than on a code store when k_g <= d, and n_tok * k_g * 4 bytes
+     * larger otherwise); the ntgt pipeline starts from gnnlm_token_gather.  Group merge, the centre-state cache and the
+     * ragged entry work as for a code store. */
+    const float* token_embed;  int64_t ld_token_embed;  int32_t n_vocab;
 } gnnlm_hgt_t;
 
 typedef struct gnnlm_hgt_io {
