@@ -648,16 +648,26 @@ void carve_asm(const gnnlm_adaptive_softmax_t& w, int64_t n, Carver& c, AsmBufs&
 
 int adaptive_impl(const gnnlm_adaptive_softmax_t& w, const float* x, int64_t ldx, const int64_t* target, int64_t n,
                   float* lm_logp, void* ws, size_t ws_bytes, hipStream_t s) {
+    // everything is checked here, in front of the first launch: what gemm_nt() would refuse half-way through the call included
     GNNLM_REQUIRE(w.n_bands >= 1 && w.n_bands <= 8 && w.head_w && w.d > 0 && w.d % 4 == 0, "adaptive: bad weights");
     GNNLM_REQUIRE(w.gemm_precision >= 0 && w.gemm_precision <= 3, "adaptive: gemm_precision must be 0, 1, 2 or 3");
-    GemmPrecisionScope prec_scope(w.gemm_precision);
+    GNNLM_REQUIRE(w.cutoff[0] >= 1, "adaptive: cutoffs must be positive and strictly ascending");
+    GNNLM_REQUIRE((uintptr_t)w.head_w % 16 == 0, "adaptive: weights must be 16-byte aligned");
+    for (int i = 1; i < w.n_bands; ++i) {
+        GNNLM_REQUIRE(w.cutoff[i] > w.cutoff[i - 1], "adaptive: cutoffs must be positive and strictly ascending");
+        GNNLM_REQUIRE(w.proj_t[i] && w.emb[i] && w.dim[i] > 0 && w.dim[i] % 4 == 0, "adaptive: bad tail band");
+        GNNLM_REQUIRE((uintptr_t)w.proj_t[i] % 16 == 0 && (uintptr_t)w.emb[i] % 16 == 0, "adaptive: weights must be 16-byte aligned");
+    }
+    GNNLM_REQUIRE(n >= 0 && n < (1ll << 31), "adaptive: bad row count");
     GNNLM_REQUIRE(x && target && lm_logp, "adaptive: null io");
+    GNNLM_REQUIRE(ldx >= w.d && ldx % 4 == 0 && (uintptr_t)x % 16 == 0, "adaptive: x must be 16-byte aligned with ldx >= d, ldx % 4 == 0");
     if (n == 0) return OK;
-    GNNLM_REQUIRE(n < (1ll << 31), "adaptive: too many rows");
     Carver c(ws, ws_bytes);
     AsmBufs b;
     carve_asm(w, n, c, b);
     GNNLM_REQUIRE(ws && c.fits(), "adaptive: workspace too small (see gnnlm_adaptive_workspace_bytes)");
+    GNNLM_REQUIRE((uintptr_t)ws % 16 == 0, "adaptive: the workspace must be 16-byte aligned");
+    GemmPrecisionScope prec_scope(w.gemm_precision);
     const int nt = w.n_bands - 1;
     const int head_n = w.cutoff[0] + nt;
 
@@ -681,10 +691,9 @@ int adaptive_impl(const gnnlm_adaptive_softmax_t& w, const float* x, int64_t ldx
         TRY(gemm_nt(g, s));     // logits are reduced in the epilogue, never written
     }
     TRY(lse_reduce(b.head_part, 2 * (int)cdiv(head_n, 128), n, nullptr, b.head_lse, s));
-    TRY(head_logp(b.head_picked, b.head_lse, lm_logp, n, s));
+    TRY(head_logp(b.head_picked, b.head_lse, b.head_pick, lm_logp, n, s));
 
     for (int i = 1; i < w.n_bands; ++i) {   // tails (adaptive_softmax.py:91-115,199-203), target rows only
-        GNNLM_REQUIRE(w.proj_t[i] && w.emb[i] && w.dim[i] > 0 && w.dim[i] % 4 == 0, "adaptive: bad tail band");
         const int size = w.cutoff[i] - w.cutoff[i - 1];
         const int32_t* rows = b.band_rows + (int64_t)(i - 1) * n;
         const int32_t* pick = b.band_pick + (int64_t)(i - 1) * n;

@@ -160,22 +160,24 @@ int half_to_float(const void* src, float* dst, int64_t n, hipStream_t stream);
 // ---------------------------------------------------------------------------------------------
 // adaptive softmax / kNN interpolation
 // ---------------------------------------------------------------------------------------------
-// lse[r] = logsumexp(logits[r, :n]); picked[r] = logits[r, pick[r]] (pick may be null)
+// lse[r] = logsumexp(logits[r, :n]); picked[r] = logits[r, pick[r]] (pick may be null; include/gnnlm.h: gnnlm_row_lse_pick)
 int row_lse_pick(const float* logits, int64_t ld, int64_t rows, const int32_t* m_dev, int n,
                  const int32_t* pick, float* lse, float* picked, hipStream_t stream);
 
 struct BandSplitParams {
     const int64_t* target = nullptr; int64_t n = 0;
     int n_bands = 0; int32_t cutoff[8] = {0};      // cutoff[0..n_bands-1], band b = [cutoff[b-1], cutoff[b])
-    int32_t* head_pick = nullptr;          // [n] index into the head logits (target or cutoff0+band-1)
+    int32_t* head_pick = nullptr;          // [n] index into the head logits (target or cutoff0+band-1); -1 for a target outside
+                                           // [0, cutoff[n_bands-1]), which joins no band either
     int32_t* band_rows = nullptr;          // [n_bands-1, n] compacted row lists of the tail bands
     int32_t* band_pick = nullptr;          // [n_bands-1, n] target - cutoff[band-1] for the compacted rows
     int32_t* band_count = nullptr;         // [n_bands-1]
 };
 int band_split(const BandSplitParams& p, hipStream_t stream);
 
-// lm_logp[rows[r]] = head_lsm[rows[r]] + (tail_picked[r] - tail_lse[r])   (rows null: identity)
-int head_logp(const float* picked, const float* lse, float* out, int64_t n, hipStream_t stream);
+// out[r] = picked[r] - lse[r], -inf where pick[r] < 0 (a target outside the vocabulary: BandSplitParams.head_pick)
+int head_logp(const float* picked, const float* lse, const int32_t* pick, float* out, int64_t n, hipStream_t stream);
+// lm_logp[rows[r]] += tail_picked[r] - tail_lse[r] for r < min(n_max, *count_dev)   (rows null: identity)
 int tail_combine(const float* tail_picked, const float* tail_lse, const int32_t* rows,
                  const int32_t* count_dev, int64_t n_max, float* lm_logp, hipStream_t stream);
 

@@ -98,22 +98,28 @@ __global__ void filter_neighbors_kernel(const int64_t* ids, const int64_t* pos, 
     out[e] = (id != -1 && (dlt < 0 ? -dlt : dlt) < ctx) ? (int64_t)-1 : id;
 }
 
-// one workgroup per row: lse = logsumexp(row[:n]), picked = row[pick]
+// one workgroup per row: lse = logsumexp(row[:n]), picked = row[pick] (include/gnnlm.h: gnnlm_row_lse_pick).  Every thread
+// keeps a running (max, sum); an element of -inf adds nothing (exp(-inf - -inf) would be NaN), and a +inf is held back from the
+// pair -- inf - inf again -- and counted: any +inf makes the row +inf unless a NaN is there too
 __global__ __launch_bounds__(256) void row_lse_pick_kernel(const float* logits, int64_t ld, int64_t rows,
                                                            const int32_t* m_dev, int n, const int32_t* pick,
                                                            float* lse, float* picked) {
     __shared__ float red_m[4], red_s[4];
+    __shared__ int red_inf[4];
     const int64_t row = blockIdx.x;
     if (m_dev && row >= *m_dev) return;
     const float* r = logits + row * ld;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float m = -INFINITY, s = 0.f;
+    int pinf = 0;
     for (int e = tid; e < n; e += 256) {
         const float v = r[e];
-        if (v > m) {
-            s = s * expf(m - v) + 1.f;
+        if (v == INFINITY) {
+            pinf = 1;
+        } else if (v > m) {
+            s = s * expf(m - v) + 1.f;      // m = -inf: s is 0 and expf(-inf) is 0
             m = v;
-        } else {
+        } else if (v != -INFINITY) {        // a NaN comes here: expf(NaN) stays in s
             s += expf(v - m);
         }
     }
@@ -122,22 +128,30 @@ __global__ __launch_bounds__(256) void row_lse_pick_kernel(const float* logits, 
     for (int o = 32; o > 0; o >>= 1) {
         const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
         const float mm = fmaxf(m, m2);
-        s = (m == -INFINITY ? 0.f : s * expf(m - mm)) + (m2 == -INFINITY ? 0.f : s2 * expf(m2 - mm));
+        s = (m == -INFINITY ? s : s * expf(m - mm)) + (m2 == -INFINITY ? s2 : s2 * expf(m2 - mm));
         m = mm;
     }
-    if (lane == 0) { red_m[wave] = m; red_s[wave] = s; }
+    const int any_inf = __any(pinf);
+    if (lane == 0) { red_m[wave] = m; red_s[wave] = s; red_inf[wave] = any_inf; }
     __syncthreads();
     if (tid == 0) {
         float mm = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
         float ss = 0.f;
-        for (int w = 0; w < 4; ++w) ss += red_m[w] == -INFINITY ? 0.f : red_s[w] * expf(red_m[w] - mm);
-        lse[row] = mm + logf(ss);
-        if (picked) picked[row] = pick ? r[pick[row]] : 0.f;
+        for (int w = 0; w < 4; ++w) ss += red_m[w] == -INFINITY ? red_s[w] : red_s[w] * expf(red_m[w] - mm);
+        const bool inf = red_inf[0] | red_inf[1] | red_inf[2] | red_inf[3];
+        // ss != ss: a NaN element.  ss == 0: no finite element (mm is -inf, and so is the row unless it holds a +inf)
+        lse[row] = ss != ss ? ss : inf ? INFINITY : ss == 0.f ? -INFINITY : mm + logf(ss);
+        if (picked) {
+            if (!pick) picked[row] = 0.f;
+            else if (pick[row] >= 0 && pick[row] < n) picked[row] = r[pick[row]];
+        }
     }
 }
 
 // one workgroup of 16 waves: stable compaction of the rows whose target falls into each tail band.  Rows are
-// taken in chunks of 1024; per band a ballot per wave + a 16-entry LDS prefix gives every row its slot.
+// taken in chunks of 1024; per band a ballot per wave + a 16-entry LDS prefix gives every row its slot.  A target outside
+// [0, vocab) joins no band and gets head_pick = -1 (the 64-bit value is compared, before any cast): the GEMM epilogue leaves its
+// lse_picked alone and head_logp_kernel writes -inf.
 constexpr int BS_WAVES = 16;
 __global__ __launch_bounds__(64 * BS_WAVES) void band_split_kernel(BandSplitParams p) {
     __shared__ int wcnt[8][BS_WAVES];
@@ -147,17 +161,18 @@ __global__ __launch_bounds__(64 * BS_WAVES) void band_split_kernel(BandSplitPara
         const int64_t r = base + tid;
         const bool in = r < p.n;
         const int64_t t = in ? p.target[r] : 0;
+        const bool ok = in && t >= 0 && t < p.cutoff[p.n_bands - 1];
         int band = 0;
 #pragma unroll
         for (int b = 1; b < 8; ++b)
             if (b < p.n_bands && t >= p.cutoff[b - 1]) band = b;
-        if (in) p.head_pick[r] = band == 0 ? (int32_t)t : p.cutoff[0] + band - 1;
+        if (in) p.head_pick[r] = !ok ? -1 : band == 0 ? (int32_t)t : p.cutoff[0] + band - 1;
         unsigned long long mask[8];
 #pragma unroll
         for (int b = 1; b < 8; ++b) {
             mask[b] = 0;
             if (b < p.n_bands) {
-                mask[b] = __ballot(in && band == b);
+                mask[b] = __ballot(ok && band == b);
                 if (lane == 0) wcnt[b][wave] = __popcll(mask[b]);
             }
         }
@@ -171,7 +186,7 @@ __global__ __launch_bounds__(64 * BS_WAVES) void band_split_kernel(BandSplitPara
                 before += w < wave ? wcnt[b][w] : 0;
                 total += wcnt[b][w];
             }
-            if (in && band == b) {
+            if (ok && band == b) {
                 const int64_t dst = (int64_t)(b - 1) * p.n + count[b] + before + __popcll(mask[b] & ((1ull << lane) - 1ull));
                 p.band_rows[dst] = (int32_t)r;
                 p.band_pick[dst] = (int32_t)(t - p.cutoff[b - 1]);
@@ -184,9 +199,10 @@ __global__ __launch_bounds__(64 * BS_WAVES) void band_split_kernel(BandSplitPara
         for (int b = 1; b < p.n_bands; ++b) p.band_count[b - 1] = count[b];
 }
 
-__global__ void head_logp_kernel(const float* picked, const float* lse, float* out, int64_t n) {
+// pick[i] < 0: the target lies outside the vocabulary (band_split_kernel) and picked[i] was never written
+__global__ void head_logp_kernel(const float* picked, const float* lse, const int32_t* pick, float* out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = picked[i] - lse[i];
+    if (i < n) out[i] = pick[i] < 0 ? -INFINITY : picked[i] - lse[i];
 }
 
 __global__ void tail_combine_kernel(const float* tail_picked, const float* tail_lse, const int32_t* rows,
@@ -471,9 +487,9 @@ int band_split(const BandSplitParams& p, hipStream_t stream) {
     return OK;
 }
 
-int head_logp(const float* picked, const float* lse, float* out, int64_t n, hipStream_t stream) {
+int head_logp(const float* picked, const float* lse, const int32_t* pick, float* out, int64_t n, hipStream_t stream) {
     if (n == 0) return OK;
-    hipLaunchKernelGGL(head_logp_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream, picked, lse, out, n);
+    hipLaunchKernelGGL(head_logp_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream, picked, lse, pick, out, n);
     GNNLM_LAUNCH_CHECK();
     return OK;
 }

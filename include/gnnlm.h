@@ -304,6 +304,10 @@ int gnnlm_half_to_float(const void* src, float* dst, int64_t n, void* stream);
  * (AdaptiveSoftmax.get_log_prob with target, fairseq/modules/adaptive_softmax.py:170-206, +
  *  gather_target_probs fairseq/sequence_scorer.py:48-53,89).
  * ---------------------------------------------------------------------------------------------- */
+/* lse[row] = log sum exp of logits[row * ld + e], e < n, for row < min(rows, *m_dev) (m_dev optional, a device-side count); later
+ * rows of lse and picked are untouched.  An element of -inf adds nothing and a row of -inf only gives -inf; a row with a +inf gives
+ * +inf; a NaN gives NaN (as torch.logsumexp).  With picked: picked[row] = logits[row * ld + pick[row]] where 0 <= pick[row] < n, and
+ * untouched for any other pick (nothing out of bounds is read); without pick, picked[row] = 0.  n >= 1; rows = 0 is accepted. */
 int gnnlm_row_lse_pick(const float* logits, int64_t ld, int64_t rows, const int32_t* m_dev, int32_t n,
                        const int32_t* pick, float* lse, float* picked, void* stream);
 
@@ -318,7 +322,18 @@ typedef struct gnnlm_adaptive_softmax {
     int32_t dim[8];
 } gnnlm_adaptive_softmax_t;
 size_t gnnlm_adaptive_workspace_bytes(const gnnlm_adaptive_softmax_t* w, int64_t n);
-/* lm_logp[r] = log p(target[r] | x[r]) */
+/* lm_logp[r] = log p(target[r] | x[r]) for r < n: with b the band of t = target[r] (cutoff[b-1] <= t < cutoff[b], cutoff[-1] = 0),
+ *   band 0:  head[t] - lse(head),                 head = x[r] . head_w^T   (cutoff[0] + n_bands - 1 logits)
+ *   band b:  head[cutoff[0] + b - 1] - lse(head) + tail[t - cutoff[b-1]] - lse(tail),   tail = (x[r] . proj_t[b]^T) . emb[b]^T;
+ *   the projection is a float32 tensor in the workspace, so at gemm_precision 1..3 it is rounded again as an operand of the band GEMM.
+ * A target outside [0, cutoff[n_bands-1]) gives -INFINITY and nothing out of bounds is read; the 64-bit value is compared, so
+ * 2^31 or 2^32 + 3 are outside too.  Nothing but lm_logp[0..n) and the workspace is written, and no bit of the result depends on
+ * what the workspace held.  x, head_w, proj_t[b], emb[b] and the workspace are 16-byte aligned, ldx >= d, ldx % 4 == 0.
+ * GNNLM_E_INVALID before anything is launched or any pointer is followed: n_bands outside 1..8, d or a tail dim not a positive
+ * multiple of 4, gemm_precision outside 0..3, a NULL or misaligned head_w / proj_t[b] / emb[b] (b >= 1), cutoffs that are not
+ * positive and strictly ascending, n < 0 or >= 2^31, a NULL x, target or lm_logp, ldx < d or ldx % 4 != 0, a misaligned x, and
+ * (n > 0) a NULL, misaligned or too small workspace (gnnlm_adaptive_workspace_bytes).  n = 0 is accepted and touches nothing.
+ * The call only enqueues on `stream`: no allocation, no synchronisation (graph-capturable). */
 int gnnlm_adaptive_target_logp(const gnnlm_adaptive_softmax_t* w, const float* x, int64_t ldx,
                                const int64_t* target, int64_t n, float* lm_logp,
                                void* workspace, size_t workspace_bytes, void* stream);
