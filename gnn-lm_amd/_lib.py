@@ -120,6 +120,12 @@ def lib():
         for nm in ("gnnlm_dense_workspace_bytes", "gnnlm_dense_workspace_bytes_min"):
             getattr(L, nm).restype, getattr(L, nm).argtypes = ctypes.c_size_t, [vp, i64]
         L.gnnlm_dense_target_logp.argtypes = [vp, vp, i64, vp, i64, vp, vp, ctypes.c_size_t, vp]
+        for nm in ("gnnlm_adaptive_log_probs_workspace_bytes", "gnnlm_adaptive_log_probs_workspace_bytes_min",
+                   "gnnlm_dense_log_probs_workspace_bytes", "gnnlm_dense_log_probs_workspace_bytes_min"):
+            getattr(L, nm).restype, getattr(L, nm).argtypes = ctypes.c_size_t, [vp, i64]
+        L.gnnlm_adaptive_log_probs.argtypes = [vp, vp, i64, i64, vp, i64, vp, ctypes.c_size_t, vp]
+        L.gnnlm_dense_log_probs.argtypes = [vp, vp, i64, i64, vp, i64, vp, ctypes.c_size_t, vp]
+        L.gnnlm_row_rank.argtypes = [vp, i64, i64, i32, vp, vp, vp]
         L.gnnlm_masked_sum_f64.argtypes = [vp, vp, i64, vp, vp]
         L.gnnlm_rows_sum_f64.argtypes = [vp, i64, i64, i64, vp, vp]
         L.gnnlm_knn_interp_grid_lm.argtypes = [vp, i32, i64, vp]
@@ -142,7 +148,7 @@ def lib():
         L.gnnlm_ragged_tiles.argtypes = [vp, i32, vp]
         L.gnnlm_causal_attn_varlen.argtypes = [vp, vp, vp, i64, vp, i64, vp, i32, i32, i32, vp]
         for nm in ("gnnlm_gemm_nt", "gnnlm_pq_gather_decode", "gnnlm_token_gather", "gnnlm_star_attn", "gnnlm_chain_attn",
-                   "gnnlm_knn_interp", "gnnlm_knn_interp_grid", "gnnlm_knn_recompute_sims", "gnnlm_topk_merge", "gnnlm_ivfpq_scan", "gnnlm_gather_rows_peer",
+                   "gnnlm_knn_interp", "gnnlm_knn_interp_grid", "gnnlm_knn_mix_dense", "gnnlm_knn_recompute_sims", "gnnlm_topk_merge", "gnnlm_ivfpq_scan", "gnnlm_gather_rows_peer",
                    "gnnlm_ivfpq_scan8", "gnnlm_ivfpq_rescore", "gnnlm_ivfpq_tau", "gnnlm_group_assign",
                    "gnnlm_ivfpq_tables"):
             getattr(L, nm).argtypes = [vp, vp]

@@ -56,6 +56,20 @@ class AdaptiveSoftmax:
             for k_ in [k_ for k_ in self._ws if k_ not in set(keep)]:
                 del self._ws[k_]
 
+    def log_probs(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [n, d] f32 -> log p(v | x) for every v, [n, V] f32: ``get_log_prob(input, None)`` (adaptive_softmax.py:170-206).  4 V bytes
+        per row: callers that do not need the whole batch at once work in row chunks (``predict.predict_rows``)."""
+        from . import ops
+        self._w.gemm_precision = self.gemm_precision
+        key = (_lib.raw_stream(), "dense")                      # one arena per stream, beside target_log_prob's
+        if self._ws is None:
+            self._ws = {}
+        need = _lib.lib().gnnlm_adaptive_log_probs_workspace_bytes(ctypes.byref(self._w), x.shape[0])
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[key] = torch.empty(need, device=x.device, dtype=torch.uint8)
+        return ops.adaptive_log_probs(self._w, x, out=out, workspace=ws)
+
     def target_log_prob(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         """x [n, d] f32, target [n] int64 -> log p(target | x) [n]."""
         n = x.shape[0]

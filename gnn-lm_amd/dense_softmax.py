@@ -71,6 +71,20 @@ class DenseSoftmax:
             for k_ in [k_ for k_ in self._ws if k_ not in set(keep)]:
                 del self._ws[k_]
 
+    def log_probs(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [n, d] f32 -> log_softmax(x . w^T + bias) [n, V] f32 (transformer.py:843-852,1081-1085): the logits are written into
+        the result by the GEMM and finished in place (csrc/dense_dist.hip); ``route`` plays no part."""
+        from . import ops
+        self._w.gemm_precision = self.gemm_precision
+        key = (_lib.raw_stream(), "dense")                      # one arena per stream, beside target_log_prob's
+        if self._ws is None:
+            self._ws = {}
+        need = _lib.lib().gnnlm_dense_log_probs_workspace_bytes(ctypes.byref(self._w), x.shape[0])
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[key] = torch.empty(need, device=x.device, dtype=torch.uint8)
+        return ops.dense_log_probs(self._w, x, out=out, workspace=ws)
+
     def target_log_prob(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         """x [n, d] f32 (row stride % 4 == 0), target [n] int64 -> log p(target | x) [n]; -inf for a target outside [0, V)."""
         n = x.shape[0]

@@ -102,6 +102,39 @@ class GnnLmEngine:
         reference's default ``faiss_store.l2``): the similarities are the negated squared distances of the search (knn_model.py:153-154)."""
         return self.score_finish(self.score_begin(batch, lmbda, temperature, knn_index, k, sweep, knn_keys, knn_sim_func, orig_prob_ratio))
 
+    def predict(self, batch: BlockBatch, lmbda: float = 0.0, temperature: float = 1.0, knn_index=None, k: int = 0, sweep=None,
+                knn_keys=None, knn_sim_func: str = "do_not_recomp_ip", orig_prob_ratio: float = 0.0, topk: int = 1):
+        """The arguments of ``score`` plus ``topk`` = N <= 2048 -> ``(ids [n, N] int64, logp [n, N], target_rank [n] int32,
+        target_logp [n])``: the N most probable next tokens of every position under the distribution ``score`` takes the target's
+        column of (GNN head, ``orig_prob_ratio`` mixture, kNN mix), best first with ties by ascending id; the number of tokens in
+        front of the target; and the target's own log-probability (``score``'s ``logp`` up to the summation order of p_knn).
+        Worked in row chunks of at most 256 MiB of dense log-probs (``predict.predict_rows``): the [n, V] tensor of the batch never
+        exists.  A sweep has no single distribution: refused."""
+        from .predict import check_topk, head_vocab, lm_dense_rows, predict_rows
+        if sweep:
+            raise ValueError("predict: a sweep has no single distribution to rank; call it once per setting")
+        V = head_vocab(self.asm)
+        check_topk(topk, V)
+        out = self.score_finish(self.score_begin(batch, lmbda, temperature, knn_index, k, None, knn_keys, knn_sim_func, orig_prob_ratio))
+        x = out["gcn_feat"]
+        h = None
+        if orig_prob_ratio > 0:
+            h = batch.tgt_feats
+            h = ops.half_to_float(h.contiguous()) if h.dtype == torch.float16 else h.float()
+        knn = None
+        if lmbda > 0.0:
+            if "knn_sims" in out:                                # searched inside the step
+                knn = dict(sims=out["knn_sims"], ids=out["knn_ids"], knn_vals=out["knn_vals"], n_store=self.store.n_store)
+            else:
+                knn_vals = batch.knn_vals
+                if knn_vals is None and self.fetcher is not None and self.fetch_vals:
+                    knn_vals = self.fetcher.fetch_knn_vals(batch.knn_ids)
+                knn = dict(sims=batch.knn_sims.contiguous(), ids=batch.knn_ids.contiguous(), knn_vals=knn_vals, vals=self.store.vals,
+                           n_store=self.store.n_store, row0=getattr(self.store, "vals_row0", self.store.row0))
+            knn.update(temperature=temperature, lmbda=lmbda)
+        dense_fn = lambda r0, r1: lm_dense_rows(self.asm, x[r0:r1], None if h is None else h[r0:r1], orig_prob_ratio)
+        return predict_rows(dense_fn, x.shape[0], V, batch.targets, topk, knn)
+
     def score_begin(self, batch: BlockBatch, lmbda: float = 0.0, temperature: float = 1.0, knn_index=None, k: int = 0, sweep=None,
                     knn_keys=None, knn_sim_func: str = "do_not_recomp_ip", orig_prob_ratio: float = 0.0):
         """Enqueue the step up to the search's host read (features, search, softmax) and return a handle for ``score_finish``:

@@ -23,6 +23,10 @@ gnnlm_scripts/wiki103/hgt_lm_wiki103_reproduce.sh:137) and prints one ``sweep k=
 line per point after the two result lines.  ``--sweep-orig-prob-ratio 0,0.3,1`` adds the base-LM / GNN mixture ratio
 (``--model-overrides "{'orig_prob_ratio': a}"``, transformer.py:987-1005,1056-1077) as the grid's outer axis -- or, without
 ``--knnlm``, sweeps it alone (``sweep orig_prob_ratio=.. loss=.. ppl=..``): the base branch is one more softmax pass for every ratio.
+
+What the run predicts (this build): ``--output-topk N [--topk-out PATH]`` also ranks the whole vocabulary at every scored position under
+the distribution the run scores -- the N most probable next tokens, the target's rank, one ``top-1 acc | top-N acc | MRR`` line -- from
+dense rows worked in chunks on the device; the two result lines do not change.
 """
 import argparse
 import ast
@@ -146,6 +150,14 @@ def get_parser():
     p.add_argument("--result-json", default=None,
                    help="(this build) write the run's figures (score_sum, count, ppl, tokens, seconds, per-rank sums, xGMI bytes) to this "
                         "file as JSON; in a multi-process run rank r writes PATH.rank<r> and rank 0 also PATH")
+    p.add_argument("--output-topk", default=0, type=int,
+                   help="(this build) N > 0: besides the target's log-probability, every scored position gets the N most probable next tokens "
+                        "of the distribution the run scores (head, orig_prob_ratio mixture, kNN mix) and the target's rank in it, from dense rows "
+                        "worked in chunks on the device; one more line `top-1 acc | top-N acc | MRR` is logged.  The perplexity is unchanged.  "
+                        "N <= 2048; not with --sweep-*, --save-knnlm-dstore, --graph-capture or more than one process")
+    p.add_argument("--topk-out", default=None,
+                   help="(this build) with --output-topk: write an .npz with ids [n_tok, N] int32, logp [n_tok, N] float32 and target_rank "
+                        "[n_tok] int32 (-1: the target is no vocabulary entry), scored tokens in corpus order")
     p.add_argument("--exchange", choices=["exact", "padded"], default="exact",
                    help="(this build) --store sharded: variable-split exchange that never drops a row (default), or the fixed-capacity "
                         "sync-free one (checked at the end of the run)")
@@ -315,6 +327,32 @@ def _parse_knn_sweep(args, raw):
     if any(not 0.0 <= v <= 1.0 for v in out["lmbda"]):
         raise ValueError("--sweep-lmbda: every lmbda must lie in 0 .. 1")
     return out["k"], out["temperature"], out["lmbda"]
+
+
+OUTPUT_TOPK_MAX = 2048     # the k of gnnlm_topk_merge
+
+
+def check_output_topk(args, world=None):
+    """-> N of ``--output-topk`` (0: off), or ValueError for what it cannot be combined with.  ``world``: the number of processes
+    (None: WORLD_SIZE)."""
+    n = int(getattr(args, "output_topk", 0) or 0)
+    if n == 0:
+        if getattr(args, "topk_out", None):
+            raise ValueError("--topk-out needs --output-topk N (there is nothing to write otherwise)")
+        return 0
+    if n < 0 or n > OUTPUT_TOPK_MAX:
+        raise ValueError(f"--output-topk: N must lie in 1 .. {OUTPUT_TOPK_MAX} (the k-selection kernel's k), got {n}")
+    if any(getattr(args, a, None) is not None for a in ("sweep_lmbda", "sweep_temperature", "sweep_k", "sweep_orig_prob_ratio")):
+        raise ValueError("--output-topk cannot be combined with --sweep-*: a grid has no single distribution to rank (run the chosen point)")
+    if getattr(args, "save_knnlm_dstore", False):
+        raise ValueError("--output-topk cannot be combined with --save-knnlm-dstore: that run writes keys, it scores no distribution")
+    if getattr(args, "graph_capture", False):
+        raise ValueError("--output-topk cannot be combined with --graph-capture: the dense rows are worked in chunks whose buffers are "
+                         "allocated per batch, outside the captured graphs")
+    world = int(os.environ.get("WORLD_SIZE", "1")) if world is None else int(world)
+    if world > 1:
+        raise ValueError(f"--output-topk writes ONE table in corpus order: run it with one process (WORLD_SIZE = {world})")
+    return n
 
 
 def sweep_table(sweep, sums, count):
@@ -526,6 +564,8 @@ def main(args, tables=None, model=None):
     if args.knnlm and args.save_knnlm_dstore:
         raise ValueError("Cannot use knnlm while trying to build the datastore!")
     check_store_mode(args)
+    topk = check_output_topk(args)
+    top_parts = []                                                                         # (first sample id, ids, logp, rank) per batch
     reinit = bool(getattr(args, "reinit_nfeat", False))
     sweep = parse_sweep(args)
     args.sweep = sweep                                                                     # (read by the scorer)
@@ -795,6 +835,9 @@ def main(args, tables=None, model=None):
             lens = [h[0]["positional_scores"].numel() for h in hypos]
             hyp_sums.append(pos.view(len(hypos), -1).sum(dim=1) if len(set(lens)) == 1 and lens[0] > 0 else
                             torch.stack([h[0]["positional_scores"].float().sum() for h in hypos]))
+        if topk:                                                 # the scored positions' rows, hypothesis by hypothesis (device tensors)
+            top_parts.append((int(sample["id"][0]), torch.cat([h[0]["topk_ids"] for h in hypos]).to(torch.int32),
+                              torch.cat([h[0]["topk_scores"] for h in hypos]), torch.cat([h[0]["target_rank"] for h in hypos])))
         state["count"] += pos.numel()                                                                # :274
         if want_words or bpe_toks is not None:
             state["count"] -= word_outputs(args, hypos, sample["id"], symbols, bpe_toks, bpe_len, word_stats)     # skipped_toks (:274)
@@ -925,6 +968,17 @@ def main(args, tables=None, model=None):
     if count_rank:
         nll32 = -float(score_sum_f32) / count_rank / math.log(2)
         logger.info("float32 accumulation order (as the reference, rank {}): Loss (base 2): {:.4f}, Perplexity: {:.2f}".format(rank, nll32, 2 ** nll32))
+    if topk:
+        from .predict import topk_stats
+        top_parts.sort(key=lambda p_: p_[0])                                                # corpus order (lanes finish in turn)
+        cat = lambda j, shape, dt: (torch.cat([p_[j] for p_ in top_parts]).cpu().numpy() if top_parts else np.zeros(shape, dt))
+        top_ids, top_logp, top_rank = cat(1, (0, topk), np.int32), cat(2, (0, topk), np.float32), cat(3, (0,), np.int32)
+        acc1, accn, mrr = topk_stats(top_rank, topk)
+        top_line = "top-1 acc {:.4f} | top-{} acc {:.4f} | MRR {:.4f}".format(acc1, topk, accn, mrr)
+        logger.info(top_line)
+        if getattr(args, "topk_out", None):
+            with open(args.topk_out, "wb") as fh:                                           # (a file object: np.savez appends no suffix)
+                np.savez(fh, ids=top_ids.astype(np.int32), logp=top_logp.astype(np.float32), target_rank=top_rank.astype(np.int32))
     if args.output_word_stats:                                                              # :333-336
         for ws in sorted(word_stats.values(), key=lambda x: x.count, reverse=True):
             logger.info(ws)

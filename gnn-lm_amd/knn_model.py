@@ -336,6 +336,18 @@ class KNNModel(object):
         return ops.knn_interp_grid(lm_logp.contiguous(), sims, knns, targets.long().contiguous(), ks, temperatures, lmbdas,
                                    vals=self.vals_device() if kvals is None else None, n_store=self.dstore_size, knn_vals=kvals)
 
+    def mix_labels(self, handle):
+        """The search result of a handle (``interpolate_begin`` / ``search_finish``) as the ``knn`` dict of ``predict.predict_rows``."""
+        sims, knns, kvals = self.search_finish(handle)[2]
+        return dict(sims=sims, ids=knns, knn_vals=kvals, vals=self.vals_device() if kvals is None else None, n_store=self.dstore_size)
+
+    def interpolate_dense(self, queries, lm_logp_dense, t, lmbda, k=0, out=None):
+        """The dense form of ``interpolate``: one search, then ``gnnlm_knn_mix_dense`` -> [n, V] log-probs of the mixture of the
+        rows' kNN distribution and ``lm_logp_dense`` [n, V]; column t of row r is what ``interpolate`` returns for target t."""
+        kn = self.mix_labels(self.interpolate_begin(queries, k))
+        return ops.knn_mix_dense(lm_logp_dense, kn["sims"], kn["ids"], t, lmbda, vals=kn["vals"], n_store=kn["n_store"],
+                                 knn_vals=kn["knn_vals"], out=out)
+
     def interpolate(self, queries, targets, lm_logp, t, lmbda, k=0):
         """Fused hot-path form: search -> (interpolated log-prob [n], p_knn [n], recall [n])."""
         sims, knns, kvals = self.search_sims(queries, k, with_vals=True)

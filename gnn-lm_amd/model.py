@@ -221,8 +221,24 @@ class GnnLmModel(torch.nn.Module):
         extra["branch_logp"] = (gnn, base)
         return mixed
 
-    def get_normalized_probs(self, net_output, log_probs, sample):
-        raise NotImplementedError("the dense [B, T, V] tensor is never materialised; use target_log_probs()")
+    def dense_log_probs_rows(self, x2, h2=None):
+        """Dense log-probs [rows, V] of flattened rows: the head over the GNN output ``x2`` [rows, d], mixed with the head over the
+        base LM's features ``h2`` at the model's ``orig_prob_ratio`` when that is > 0 and ``h2`` is given (transformer.py:1075-1077)."""
+        from .predict import lm_dense_rows
+        if h2 is None or self.orig_prob_ratio <= 0 or self.short_cut:     # short_cut: both branches are the same rows (mixing x with x)
+            return self.adaptive_softmax.log_probs(x2)
+        return lm_dense_rows(self.adaptive_softmax, x2, h2, self.orig_prob_ratio)
+
+    def get_normalized_probs(self, net_output, log_probs, sample=None):
+        """The dense [B, T, V] (log-)probabilities (transformer.py:1064-1085), on the device: 4 V bytes per token -- the eval path
+        never asks for it (``target_log_probs``), and ``predict.predict_rows`` consumes it in row chunks instead."""
+        x = net_output[0]
+        bsz, T, d = x.shape
+        extra = net_output[1] if len(net_output) > 1 and isinstance(net_output[1], dict) else {}
+        h = extra.get("orig_x") if self.orig_prob_ratio > 0 else None         # :1075-1077 (a ratio of 0 is the GNN branch itself)
+        lp = self.dense_log_probs_rows(x.reshape(-1, d).contiguous(), None if h is None else h.reshape(-1, h.shape[-1]).contiguous())
+        lp = lp.view(bsz, T, -1)
+        return lp if log_probs else lp.exp_()
 
     @classmethod
     def from_checkpoint(cls, path, device, overrides=None, vocab_size=None, quantizer=None, reinit_nfeat=False, precision=None):

@@ -540,6 +540,114 @@ def knn_interp_grid(lm_logp, sims, ids, targets, ks, temperatures, lmbdas, vals=
     return out, pk, rec
 
 
+def _rows_out(out, n, V, dev, what):
+    """The [n, V] float32 result of a dense call: ``out`` as given (rows may be wider than V: its pad columns are left alone) or new."""
+    if out is None:
+        return torch.empty(n, V, device=dev, dtype=torch.float32)
+    _f32(out)
+    if not out.is_cuda or out.dim() != 2 or out.shape != (n, V) or (out.stride(1) != 1 and V > 1) or (n > 1 and out.stride(0) < V):
+        raise ValueError(f"{what}: out must be a device tensor [n, V] with unit column stride and row stride >= V")
+    return out
+
+
+def _row_stride(t):
+    """Row stride in elements of a [n, V] tensor with contiguous rows (a single row may carry any stride: V then)."""
+    if t.dim() != 2 or (t.stride(1) != 1 and t.shape[1] > 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError("expected a 2-D tensor with contiguous rows and row stride >= its width")
+    return max(t.stride(0), t.shape[1])
+
+
+def _head_log_probs(entry, w, V, x, out, workspace, least_workspace):
+    _f32(x)
+    if not x.is_cuda:
+        raise _lib.GnnlmError("gnnlm_amd kernels need device (HIP) tensors; there is no CPU fallback")
+    if x.dim() != 2 or x.shape[1] != w.d:
+        raise ValueError(f"{entry}: x [n, {w.d}]")
+    if x.stride(-1) != 1 or x.stride(0) % 4 or x.stride(0) < w.d or x.data_ptr() % 16:
+        x = x.contiguous()
+    n = x.shape[0]
+    out = _rows_out(out, n, V, x.device, entry)
+    if n == 0:
+        return out
+    L = _lib.lib()
+    need = getattr(L, f"gnnlm_{entry}_workspace_bytes" + ("_min" if least_workspace else ""))(ctypes.byref(w), n)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=x.device, dtype=torch.uint8)
+    _lib.check(getattr(L, "gnnlm_" + entry)(ctypes.byref(w), ctypes.c_void_p(x.data_ptr()), x.stride(0), n, ctypes.c_void_p(out.data_ptr()),
+                                            _row_stride(out), ptr(workspace), need if least_workspace else workspace.numel(), stream()),
+               "gnnlm_" + entry)
+    return out
+
+
+def adaptive_log_probs(w, x, out=None, workspace=None, least_workspace=False):
+    """Full log-probabilities of the tied adaptive softmax (``gnnlm_adaptive_log_probs``; AdaptiveSoftmax.get_log_prob without a
+    target, adaptive_softmax.py:170-206): ``w`` a filled ``gnnlm_adaptive_softmax_t``, ``x`` [n, d] f32 -> [n, V] f32.  ``out`` may be
+    a view with a wider row stride (its pad columns stay untouched); ``workspace`` a uint8 device buffer that is used if it is
+    large enough; ``least_workspace`` hands the library the least it accepts (128-row chunks: tests)."""
+    return _head_log_probs("adaptive_log_probs", w, w.cutoff[w.n_bands - 1], x, out, workspace, least_workspace)
+
+
+def dense_log_probs(w, x, out=None, workspace=None, least_workspace=False):
+    """The same for the plain head (``gnnlm_dense_log_probs``): ``w`` a filled ``gnnlm_dense_softmax_t`` -> [n, vocab] f32."""
+    return _head_log_probs("dense_log_probs", w, w.vocab, x, out, workspace, least_workspace)
+
+
+def knn_mix_dense(lm_logp, sims, ids, temperature, lmbda, vals=None, n_store=None, row0=0, knn_vals=None, out=None, want_pknn=False):
+    """The kNN distribution of every row interpolated with a whole row of language-model log-probabilities
+    (``gnnlm_knn_mix_dense``): ``lm_logp`` [n, V] f32 (row stride >= V), ``sims`` [n, k] f32, ``ids`` [n, k] i64, labels as in
+    :func:`knn_interp` -> ``out`` [n, V] f32, or ``(out, p_knn [n, V])`` with ``want_pknn``.  ``out[r, t]`` is what ``knn_interp`` gives
+    for target ``t``.  Deterministic (no atomics); k <= 1024; ``out`` must not overlap ``lm_logp``."""
+    _dev(lm_logp, sims, ids, vals, knn_vals)
+    _f32(lm_logp, sims)
+    _dtype(ids, torch.int64, "ids"), _dtype(knn_vals, torch.int32, "knn_vals")
+    if vals is not None and vals.dtype not in (torch.int16, torch.int32):
+        raise TypeError(f"vals: expected int16 / int32, got {vals.dtype}")
+    for t in (sims, ids, vals, knn_vals):
+        if t is not None and not t.is_contiguous():
+            raise _lib.GnnlmError("knn_mix_dense needs contiguous sims / ids / labels")
+    if lm_logp.dim() != 2 or sims.dim() != 2 or sims.shape != ids.shape or sims.shape[0] != lm_logp.shape[0]:
+        raise ValueError("knn_mix_dense: lm_logp [n, V], sims / ids [n, k]")
+    n, V = lm_logp.shape
+    k = sims.shape[1]
+    out = _rows_out(out, n, V, lm_logp.device, "knn_mix_dense")
+    pk = torch.empty(n, V, device=lm_logp.device, dtype=torch.float32) if want_pknn else None
+    d = _lib.gnnlm_knn_mix_dense_t()
+    d.lm_logp, d.ld_lm = lm_logp.data_ptr(), _row_stride(lm_logp)
+    d.sims, d.ids = sims.data_ptr(), ids.data_ptr()
+    d.vals_itemsize = 4
+    if vals is not None:
+        d.vals, d.vals_itemsize = vals.data_ptr(), vals.element_size()
+        d.n_local = vals.shape[0]
+        d.n_store = n_store if n_store is not None else vals.shape[0]
+        d.row0 = row0
+    if knn_vals is not None:
+        d.knn_vals = knn_vals.data_ptr()
+    d.n, d.k, d.V = n, k, V
+    d.temperature, d.lmbda = temperature, lmbda
+    d.out, d.ldo = out.data_ptr(), _row_stride(out)
+    if pk is not None:
+        d.out_pknn, d.ld_pknn = pk.data_ptr(), V
+    call_desc("gnnlm_knn_mix_dense", d)
+    return (out, pk) if want_pknn else out
+
+
+def row_rank(logp, target, out=None):
+    """``rank[r]`` = the number of columns of ``logp[r]`` in front of column ``target[r]`` in ``topk_merge``'s order (larger value
+    first, then smaller id); -1 for a target outside [0, V) (``gnnlm_row_rank``).  logp [n, V] f32, target [n] i64 -> int32 [n]."""
+    _dev(logp, target, out)
+    _f32(logp)
+    _dtype(target, torch.int64, "target"), _dtype(out, torch.int32, "out")
+    if logp.dim() != 2 or target.shape != (logp.shape[0],) or not target.is_contiguous():
+        raise ValueError("row_rank: logp [n, V], target [n] contiguous")
+    n, V = logp.shape
+    if out is None:
+        out = torch.empty(n, device=logp.device, dtype=torch.int32)
+    elif out.shape != (n,) or not out.is_contiguous():
+        raise ValueError("row_rank: out [n] contiguous")
+    call("gnnlm_row_rank", ptr_strided(logp), _row_stride(logp), n, V, ptr(target), ptr(out), stream())
+    return out
+
+
 def knn_recompute_sims(queries, ids, keys, metric, normalize_keys=False, out=None):
     """Similarities recomputed from the stored keys (``gnnlm_knn_recompute_sims``; knn_model.py:161-175) -> ``out`` [n, k] f32.
 

@@ -5,6 +5,7 @@ hypothesis dicts (``tokens, score, attention, alignment, positional_scores, dsto
 :185-193).  (This build) with ``args.sweep = (ks, temperatures, lmbdas[, alphas])`` ``generate_finish`` also leaves
 ``handle["sweep_logp"]`` [G, scored tokens]: every point of the kNN-LM tuning grid, from the batch's one search (``alphas``: the
 ``orig_prob_ratio`` axis, slowest, from the model's two softmax branches; ``(None, None, None, alphas)`` sweeps the ratio alone).
+(This build) with ``args.output_topk = N > 0`` every hypothesis also carries ``topk_ids`` / ``topk_scores`` [len, N] and ``target_rank`` [len].
 What differs is only where the arithmetic runs: the dense ``[B, T, V]`` log-prob tensor and
 the host-side kNN gathers are replaced by the HIP kernels behind ``model.target_log_probs`` and
 ``KNNModel.interpolate``.
@@ -74,7 +75,7 @@ class SequenceScorer(object):
             if hasattr(knn_model, "interpolate_begin"):
                 pending = knn_model.interpolate_begin(queries.contiguous().view(-1, hidden))
         probs = model.target_log_probs(decoder_out, orig_target.clamp(min=0))
-        return dict(sample=sample, decoder_out=decoder_out, probs=probs, use_knn=use_knn, pending=pending, lmbda=lmbda, temperature=temperature,
+        return dict(sample=sample, decoder_out=decoder_out, probs=probs, use_knn=use_knn, pending=pending, lmbda=lmbda, temperature=temperature, model=model,
                     knn_model=kwargs.get("knn_dstore"), queries=(queries if use_knn or sweep else None), sweep=sweep, alphas=alphas)
 
     @torch.no_grad()
@@ -85,6 +86,11 @@ class SequenceScorer(object):
         bsz, tsz = orig_target.shape
         recall = None
         sweep, grid, alphas = h.get("sweep"), None, h.get("alphas")
+        # (this build) args.output_topk = N > 0: every hypothesis also carries the N most probable next tokens of each scored position
+        # (`topk_ids` / `topk_scores` [len, N], best first) and the number of tokens in front of the target (`target_rank` [len])
+        topk, found = int(getattr(self.args, "output_topk", 0) or 0), None
+        if topk and (sweep or alphas):
+            raise ValueError("output_topk with a sweep: a grid has no single distribution to rank")
         if alphas:
             from . import ops
             if "branch_logp" not in decoder_out[1]:
@@ -114,7 +120,10 @@ class SequenceScorer(object):
             # one-block batches have: targets in the queries' order.
             tq = (orig_target.transpose(0, 1) if sample.get("blockwise_knn") else orig_target.permute(0, 1)).reshape(seq_len * b2)
             lm_flat = probs.transpose(0, 1).reshape(-1)                                 # [T*B] like the queries
-            if pending is not None:
+            if topk:                                            # one search result, two consumers: the target column and the dense rows
+                found = knn_model.search_finish(pending if pending is not None else knn_model.interpolate_begin(queries.contiguous().view(-1, hidden)))
+                mixed, _, rec = knn_model.interpolate_finish(found, tq.clamp(min=0), lm_flat, temperature, lmbda)
+            elif pending is not None:
                 mixed, _, rec = knn_model.interpolate_finish(pending, tq.clamp(min=0), lm_flat, temperature, lmbda)
             else:
                 mixed, _, rec = knn_model.interpolate(queries.contiguous().view(-1, hidden), tq.clamp(min=0),
@@ -123,8 +132,9 @@ class SequenceScorer(object):
             recall = rec.view(seq_len, b2).transpose(0, 1)
         kt = getattr(self.args, "knn_keytype", None)
         feat = decoder_out[1][kt] if kt in decoder_out[1] else decoder_out[1]["inner_states"][-1]
+        top = self._dense_topk(h, found, topk) if topk else None
         if sample.get("ragged") is not None:
-            return self._finish_ragged(h, probs, recall, grid, feat)
+            return self._finish_ragged(h, probs, recall, grid, feat, top)
         start_idxs = sample["start_indices"] if "start_indices" in sample else [0] * bsz
         # strip_pad / the [mask] selections of the reference (:156-191) are boolean indexings: each one synchronises the
         # stream (nonzero).  LM eval targets carry no padding (--sample-break-mode none), so ask ONCE per batch -- or not
@@ -156,6 +166,7 @@ class SequenceScorer(object):
                 p_i = probs[i][s:]
                 keys_i = feat[s:, i, :]
                 rec_i = recall[i, s:] if recall is not None else None
+                top_i = [t[i, s:] for t in top] if top is not None else None
             else:
                 ref = strip_pad(sample["target"][i, s:], self.pad)
                 tgt_len = ref.numel()
@@ -163,6 +174,7 @@ class SequenceScorer(object):
                 mask = sample["target"][i, s:].ne(self.pad)
                 keys_i = feat[s:, i, :][mask]
                 rec_i = recall[i, s:][mask] if recall is not None else None
+                top_i = [t[i, s:][mask] for t in top] if top is not None else None
             hypos.append([{
                 "tokens": ref,
                 "score": score_all[i] if score_all is not None else p_i.sum() / tgt_len,
@@ -172,9 +184,38 @@ class SequenceScorer(object):
                 "dstore_keys": keys_i,
                 "knn_recall": rec_i,
             }])
+            if top_i is not None:
+                hypos[-1][0].update(topk_ids=top_i[0], topk_scores=top_i[1], target_rank=top_i[2])
         return hypos
 
-    def _finish_ragged(self, h, probs, recall, grid, feat):
+    def _dense_topk(self, h, found, topk):
+        """-> (ids [B, T, N] int64, scores [B, T, N], target_rank [B, T] int32) of the batch: the distribution behind ``probs`` (the
+        model's head, its ``orig_prob_ratio`` mixture, and the kNN mix when ``found`` holds the batch's search result), consumed in
+        row chunks (``predict.predict_rows``).  Rows run in the queries' [T, B] order, and the kNN branch ranks the target it scores:
+        the pairing of ``generate_finish`` as written."""
+        from .predict import head_vocab, predict_rows
+        model, decoder_out, sample = h["model"], h["decoder_out"], h["sample"]
+        if not hasattr(model, "dense_log_probs_rows"):
+            raise ValueError("output_topk needs a model with dense_log_probs_rows (GnnLmModel)")
+        x, extra = decoder_out[0], decoder_out[1]
+        bsz, tsz, d = x.shape
+        x2 = x.transpose(0, 1).reshape(tsz * bsz, d).contiguous()
+        h2 = None
+        if getattr(model, "orig_prob_ratio", 0) > 0 and "orig_x" in extra:
+            h2 = extra["orig_x"].transpose(0, 1).reshape(tsz * bsz, -1).contiguous()
+        tgt = sample["target"]
+        tq = (tgt.transpose(0, 1) if found is None or sample.get("blockwise_knn") else tgt.permute(0, 1)).reshape(-1).clamp(min=0).contiguous()
+        knn = None
+        if found is not None:
+            if not hasattr(h["knn_model"], "mix_labels"):
+                raise ValueError("output_topk with a kNN store needs KNNModel.mix_labels (the search result with its labels)")
+            knn = dict(h["knn_model"].mix_labels(found), temperature=h["temperature"], lmbda=h["lmbda"])
+        ids, scores, rank, _ = predict_rows(lambda r0, r1: model.dense_log_probs_rows(x2[r0:r1], None if h2 is None else h2[r0:r1]),
+                                            x2.shape[0], head_vocab(model.adaptive_softmax), tq, topk, knn)
+        back = lambda t: t.view(tsz, bsz, *t.shape[1:]).transpose(0, 1)
+        return back(ids), back(scores), back(rank)
+
+    def _finish_ragged(self, h, probs, recall, grid, feat, top=None):
         """(this build) The hypotheses of a RAGGED batch: ``sample["ragged"]`` (a ragged.RaggedBatch) cuts the batch's one row of
         packed tokens into blocks; one hypothesis per block, ``tokens`` / ``positional_scores`` of the block's own scored length
         (``start_indices`` tokens of context in front are not scored) -- what ``strip_pad`` leaves of the reference's padded rows
@@ -222,4 +263,6 @@ class SequenceScorer(object):
                 "dstore_keys": feat[a:e, 0, :],
                 "knn_recall": recall[0, a:e] if recall is not None else None,
             }])
+            if top is not None:
+                hypos[-1][0].update(topk_ids=top[0][0, a:e], topk_scores=top[1][0, a:e], target_rank=top[2][0, a:e])
         return hypos

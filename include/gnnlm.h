@@ -467,6 +467,79 @@ int gnnlm_knn_recompute_sims(const gnnlm_knn_resim_t* desc, void* stream);
 int gnnlm_label_tags(const void* vals, int32_t vals_itemsize, int64_t n, uint8_t* tag, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Next-token DISTRIBUTIONS: the dense [n, V] outputs of the scoring chain (csrc/dense_dist.hip).  Additive to ABI 12: one new
+ * struct and new entries, no existing member moved.
+ * Replaces: AdaptiveSoftmax.get_log_prob(input, target=None) (fairseq/modules/adaptive_softmax.py:170-206) as called by
+ *           TokenGraphTransformerDecoder.get_normalized_probs (fairseq/models/transformer.py:1064-1085), the log_softmax of the
+ *           plain head (:1081-1085), KNNModel.get_knn_prob(targets=None) (knn/knn_model.py:192-205) and
+ *           combine_knn_and_vocab_probs over the whole row (fairseq/sequence_scorer.py:55-68,121).
+ * ---------------------------------------------------------------------------------------------- */
+/* out[r, v] = log p(v | x[r]) for r < n and EVERY v < V = cutoff[n_bands-1]; out is [n, V] with row stride ldo >= V:
+ *   v < cutoff[0]:                   head[v] - lse(head)                                  head = x[r] . head_w^T
+ *   cutoff[b-1] <= v < cutoff[b]:    tail_b[v - cutoff[b-1]] - lse(tail_b) + head[cutoff[0] + b - 1] - lse(head)
+ * built from gnnlm_gemm_nt (the head's logits go to the workspace, a band's straight into its columns of out with ldc = ldo),
+ * gnnlm_row_lse_pick without a pick, and one kernel that finishes the rows in place.  The columns ldo > V leaves behind a row
+ * are not written.  Rows are worked in chunks -- at most 1024 rows, as many multiples of 128 as the workspace holds, and
+ * chunk * max(ldo, ldx) < 2^31: the base pointers advance per chunk, so no kernel sees an element offset of 2^31 or more and
+ * n * ldo may be any size.  gnnlm_adaptive_log_probs_workspace_bytes sizes the workspace for the largest chunk,
+ * ..._workspace_bytes_min is the least the call accepts (chunks of min(n, 128) rows).  Two identical calls give identical bits.
+ * x, the weights and the workspace are 16-byte aligned, ldx >= d, ldx % 4 == 0; out needs its natural 4 bytes only.
+ * GNNLM_E_INVALID before anything is launched or written: what gnnlm_adaptive_target_logp refuses of w, x, ldx and n, a NULL
+ * or misaligned out, ldo < V or >= 2^31, and (n > 0) a NULL, misaligned or too small workspace.  n = 0 is accepted and touches
+ * nothing.  The call only enqueues on `stream`: no allocation, no synchronisation. */
+size_t gnnlm_adaptive_log_probs_workspace_bytes(const gnnlm_adaptive_softmax_t* w, int64_t n);
+size_t gnnlm_adaptive_log_probs_workspace_bytes_min(const gnnlm_adaptive_softmax_t* w, int64_t n);
+int gnnlm_adaptive_log_probs(const gnnlm_adaptive_softmax_t* w, const float* x, int64_t ldx, int64_t n, float* out, int64_t ldo,
+                             void* workspace, size_t workspace_bytes, void* stream);
+/* The same for the plain head: out[r, v] = (x[r] . w[v]^T + bias[v]) - log sum_u exp(x[r] . w[u]^T + bias[u]), v < vocab.  The
+ * logits of a chunk are written into out by gnnlm_gemm_nt (bias_mode 1 with a bias) and finished in place by the same kernel;
+ * `route` is not read.  Chunks, alignment, refusals and the two workspace sizes as above. */
+size_t gnnlm_dense_log_probs_workspace_bytes(const gnnlm_dense_softmax_t* w, int64_t n);
+size_t gnnlm_dense_log_probs_workspace_bytes_min(const gnnlm_dense_softmax_t* w, int64_t n);
+int gnnlm_dense_log_probs(const gnnlm_dense_softmax_t* w, const float* x, int64_t ldx, int64_t n, float* out, int64_t ldo,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* kNN distance-softmax aggregated by label and interpolated with a WHOLE row of language-model log-probabilities:
+ *   p_j = softmax_j((ids[r, j] == -1 ? -1e10 : sims[r, j]) / temperature)                 (knn/knn_model.py:192-196)
+ *   p_knn[r, v] = sum of p_j over the neighbours j whose label is v                       (:203-205, `weighted_probs`)
+ *   out[r, v] = logaddexp(lm_logp[r, v] + log(1 - lmbda), logf(p_knn[r, v] + 1e-10f) + log(lmbda))   for EVERY v < V
+ * -- the 1e-10 applies to labels without a neighbour too, so out[r, t] is what gnnlm_knn_interp gives for target t, whatever
+ * t is (fairseq/sequence_scorer.py:55-68,121; up to the summation order of p_knn).  Labels as in gnnlm_knn_interp_t: knn_vals,
+ * or vals with n_store / row0 / n_local (an id < 0 wraps to id + n_store; a row outside the shard has no label).  A neighbour
+ * whose label lies outside [0, V) or is missing takes part in the softmax and contributes to no column; nothing is read or
+ * written out of bounds.  The aggregation is deterministic: the k (label, p) pairs of a row are sorted by label in LDS and every
+ * run is summed in sorted order (float64, rounded once); no floating-point atomics; two identical calls give identical bits.
+ * Two launches ordered by the stream: an elementwise pass over [n, V] that writes the no-neighbour value (16-byte loads and
+ * stores when lm_logp, out, out_pknn are 16-byte aligned and their row strides multiples of 4; any 4-byte alignment works),
+ * then one workgroup per row that overwrites its at most k label columns from lm_logp.  The pad columns of ldo / ld_pknn > V
+ * are not written.  out, out_pknn and lm_logp must not overlap.
+ * GNNLM_E_INVALID before anything is launched or written: a NULL lm_logp / sims / ids / out, neither vals nor knn_vals, vals
+ * without n_store / n_local or with an itemsize other than 2 / 4, k outside 1 .. 1024, temperature <= 0, lmbda outside (0, 1),
+ * V < 1, n < 0, a row stride below V, a misaligned pointer (natural alignment), out == lm_logp.  n = 0 is accepted and touches
+ * nothing.  The call only enqueues: no allocation, no synchronisation, no scratch. */
+typedef struct gnnlm_knn_mix_dense {
+    const float* lm_logp;  int64_t ld_lm;     /* [n, V], row stride ld_lm >= V */
+    const float* sims;         /* [n, k] similarities after sim_func */
+    const int64_t* ids;        /* [n, k], -1 = padding */
+    const void* vals;  int32_t vals_itemsize;  int64_t n_store, row0, n_local;
+    const int32_t* knn_vals;   /* optional [n, k]: vals[ids] already fetched */
+    int64_t n;  int32_t k, V;  /* k <= 1024 */
+    float temperature;
+    double lmbda;
+    float* out;  int64_t ldo;          /* [n, V] */
+    float* out_pknn;  int64_t ld_pknn; /* optional [n, V]: p_knn itself, zero where no neighbour has the label */
+} gnnlm_knn_mix_dense_t;
+int gnnlm_knn_mix_dense(const gnnlm_knn_mix_dense_t* desc, void* stream);
+
+/* rank[r] = the number of columns of logp[r, 0..V) that come before column target[r] in the order of gnnlm_topk_merge (largest
+ * = 1): larger value first, then smaller id -- so target[r] is at position rank[r] of the row's full top-V list, and inside the
+ * top-N that gnnlm_topk_merge (ncols = V, k = N) returns iff rank[r] < N.  As there, a NaN or -inf column is absent: it comes
+ * before nothing, and a target whose own value is absent comes behind every present column.  A target outside [0, V) gives -1
+ * and reads nothing.  logp [n, V] with row stride ld >= V; target int64 [n]; rank int32 [n].  NULL operands, ld < V, V < 1 and
+ * n < 0 are GNNLM_E_INVALID; n = 0 is accepted and touches nothing. */
+int gnnlm_row_rank(const float* logp, int64_t ld, int64_t n, int32_t V, const int64_t* target, int32_t* rank, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * On-device kNN search, selection half: fold one chunk of scores into a running top-k per query.
  * Replaces the k-selection of faiss `index.search` (knn/knn_model.py:87-101, knn/find_knn.py:55-70); the
  * scores of a chunk come from gnnlm_gemm_nt over a chunk of keys (exact search) or from gnnlm_ivfpq_scan.
