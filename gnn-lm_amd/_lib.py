@@ -109,6 +109,11 @@ def lib():
         L.gnnlm_half_to_float.argtypes = [vp, vp, i64, vp]
         L.gnnlm_filter_neighbors.argtypes = [vp, vp, i64, i32, i64, vp, vp]
         L.gnnlm_gelu.argtypes = [vp, i64, vp]
+        L.gnnlm_relu.argtypes = [vp, i64, vp]
+        L.gnnlm_lm_embed.argtypes = [vp, vp, vp]
+        L.gnnlm_transformer_lm_workspace_bytes.restype = ctypes.c_size_t
+        L.gnnlm_transformer_lm_workspace_bytes.argtypes = [vp, vp]
+        L.gnnlm_transformer_lm_forward.argtypes = [vp, vp, vp, ctypes.c_size_t, vp]
         L.gnnlm_row_lse_pick.argtypes = [vp, i64, i64, vp, i32, vp, vp, vp, vp]
         L.gnnlm_lse_reduce.argtypes = [vp, i32, i64, vp, vp, vp]
         L.gnnlm_pq_encode.argtypes = [vp, i64, vp, vp, i32, i32, i64, vp, vp]

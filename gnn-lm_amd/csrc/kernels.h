@@ -150,6 +150,8 @@ int scatter_code_rows(const uint8_t* src, const int32_t* index, int64_t stride, 
 int mean2(const float* a, const float* b, float* out, int64_t n, hipStream_t stream);
 
 int gelu(float* x, int64_t n, hipStream_t stream);
+// x = max(x, 0) in place, NaN kept (transformer_lm.hip)
+int relu(float* x, int64_t n, hipStream_t stream);
 
 // the --invalid-neighbor-context rule of token_block_dataset.py:360-362 applied to a batch of neighbour-id rows
 int filter_neighbors(const int64_t* ids, const int64_t* pos, int64_t n, int kg, int64_t ctx, int64_t* out, hipStream_t stream);

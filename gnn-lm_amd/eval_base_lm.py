@@ -1,0 +1,269 @@
+"""The base transformer LM path of ``eval_lm`` (no ``--graph``): perplexity of a ``--arch transformer_lm*`` checkpoint over
+``DATA/{split}.bin/.idx`` and the "save features" loop of the recipe (gnnlm_scripts/wiki103/prepare_wiki103.sh:69-78):
+
+    python -m gnnlm_amd.eval_lm DATA --path base.pt --sample-break-mode complete --tokens-per-sample 3072 --max-tokens 3072 \\
+        --context-window 2560 --softmax-batch 1024 --gen-subset S --dstore-mmap DATA --save-knnlm-dstore --dstore-fp16
+
+Mirror of ``fairseq_cli/eval_lm.py:61-336`` with ``SequenceScorer.generate`` (fairseq/sequence_scorer.py) for one model:
+
+  tokens   the split's stream through the ``.bin/.idx`` reader.  Target = the stream, source = the stream shifted right by one
+           with ``eos`` in front of token 0 (``TokenBlockDataset.__getitem__`` with ``include_targets``).
+  samples  ``--sample-break-mode none | complete | complete_doc | eos`` through ``eval_lm.sample_blocks``, packed back to back up
+           to ``--max-tokens`` rows per batch (a sample longer than that is a batch of its own).
+  context  ``--context-window w`` = ``LMContextWindowDataset`` (fairseq/data/lm_context_window_dataset.py): the samples are cut
+           at ``tokens_per_sample - w`` and each carries the source tokens in front of it -- as many as the collater keeps:
+           min(w, what the previous sample left, tokens_per_sample - its own length) -- which are computed but not scored.  The
+           context is taken in CORPUS order.
+  scoring  the checkpoint's head on the scored rows only, read in place (row views of the feature buffer, no gather), in pieces
+           of at most ``--softmax-batch`` rows; score_sum and count in float64; the reference's two final lines.
+  dstore   ``--save-knnlm-dstore --dstore-mmap DIR [--dstore-fp16] [--knn-keytype last_ffn_input]``: row i = token i of the split.
+
+Not built here (refused): ``--knnlm`` without ``--graph``, more than one process, ``--graph-capture``.
+"""
+import json
+import logging
+import math
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import ops, token_blocks
+
+logger = logging.getLogger("gnnlm_amd.eval_lm")
+
+EOS = 2
+
+
+def shifted_source(tokens, eos=EOS):
+    """Source stream of a target stream: shifted right by one, ``eos`` in front (token_block_dataset.py:134-144)."""
+    tokens = np.asarray(tokens)
+    src = np.empty(tokens.shape[0], dtype=np.int64)
+    src[0:1] = eos
+    src[1:] = tokens[:-1]
+    return src
+
+
+def context_lengths(lengths, tokens_per_sample, context_window):
+    """How many context tokens the collater of LMContextWindowDataset puts in front of every sample, samples taken in order
+    (lm_context_window_dataset.py:46-56): ``prev_tokens`` is the last ``w`` tokens of the previous row (its own context included),
+    cut from the front so that context + sample <= tokens_per_sample + w.  ``tokens_per_sample`` is the value AFTER the driver's
+    ``tokens_per_sample -= w``."""
+    out, prev = [], 0
+    cap = tokens_per_sample + context_window
+    for n in lengths:
+        n = int(n)
+        prev = max(0, prev - max(0, prev + n - cap))
+        out.append(prev)
+        prev = min(context_window, prev + n)
+    return np.asarray(out, dtype=np.int64)
+
+
+def check_args(args):
+    if args.knnlm:
+        raise ValueError("--knnlm without --graph (kNN-LM on the base LM) is not built: run the GNN path, or save the datastore here "
+                         "and score with --graph --use-precompute-feat --knnlm")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise NotImplementedError("the base LM path runs in one process (WORLD_SIZE > 1 is not built)")
+    if getattr(args, "graph_capture", False):
+        raise ValueError("--graph-capture is not built for the base LM path")
+    if args.save_knnlm_dstore and not args.dstore_mmap:
+        raise ValueError("--save-knnlm-dstore needs --dstore-mmap")
+    for flag in ("sweep_lmbda", "sweep_temperature", "sweep_k", "sweep_orig_prob_ratio"):
+        if getattr(args, flag, None):
+            raise ValueError(f"--{flag.replace('_', '-')} belongs to the --graph path")
+    if getattr(args, "output_topk", 0):
+        raise ValueError("--output-topk belongs to the --graph path")
+    if args.output_knn_recall:
+        raise ValueError("--output-knn-recall needs --knnlm")
+    if getattr(args, "reinit_nfeat", False):
+        raise ValueError("--reinit-nfeat belongs to the --graph path")
+    if args.add_bos_token:
+        raise ValueError("--add-bos-token is not built for the base LM path")
+    if args.knn_keytype not in (None, "", "last_ffn_input"):
+        # (sequence_scorer.py:181-182: any other key type is absent from the decoder's extra and falls back to inner_states[-1])
+        logger.info("--knn-keytype %s is not a key of the base LM's outputs: inner_states[-1] is saved (as the reference)", args.knn_keytype)
+
+
+def main(args, model=None):
+    """-> the result dict of ``eval_lm.main`` (score_sum, count, ppl, tokens, seconds, ...) plus ``pos_scores`` (float32 numpy, one
+    log-probability per scored token in corpus order) when ``args.keep_pos_scores`` is set (tests, tools)."""
+    from .eval_lm import WordStat, fairseq_sentence_sizes, fairseq_token_stream, load_symbols, sample_blocks, word_outputs  # noqa: F401
+    from .ragged import BlockTable, packed_rows
+    from .transformer_lm import TransformerLM
+    import ast
+    check_args(args)
+    break_mode = getattr(args, "sample_break_mode", None) or "none"
+    if break_mode not in token_blocks.BREAK_MODES:
+        raise ValueError("Invalid break_mode: " + str(break_mode))
+    w = int(args.context_window)
+    if w < 0 or w >= args.tokens_per_sample:
+        raise ValueError(f"--context-window {w} must lie in [0, --tokens-per-sample {args.tokens_per_sample})")
+    if args.save_knnlm_dstore and break_mode == "complete_doc":
+        raise ValueError("--save-knnlm-dstore writes one row per token of the split in corpus order; --sample-break-mode complete_doc "
+                         "drops the document separators")
+    if w > 0 and break_mode == "complete_doc":
+        raise ValueError("--context-window with --sample-break-mode complete_doc is not built (the dropped separators leave gaps in the context)")
+    device = torch.device(args.device)
+    torch.cuda.set_device(device)
+    stream_np = fairseq_token_stream(args.data, args.gen_subset)
+    if stream_np is None:
+        raise FileNotFoundError(f"the base LM reads the binarised split {os.path.join(args.data, args.gen_subset)}.bin/.idx (fairseq's mmap "
+                                "dataset): not found or not in that format")
+    n_tok = int(stream_np.shape[0])
+    if n_tok == 0:
+        raise ValueError("the split is empty")
+    if model is None:
+        model, _ = TransformerLM.from_checkpoint(args.path, device, ast.literal_eval(args.model_overrides), precision="fp16" if args.fp16 else None)
+    elif args.fp16:
+        model.precision = "fp16"
+    if args.fp16:
+        logger.info("--fp16: float16 matrix-core GEMMs with float32 accumulation (transformer layers and output layer); embedding, "
+                    "attention and LayerNorm stay float32")
+    tgt_np = np.asarray(stream_np).astype(np.int64)
+    tgt = torch.from_numpy(tgt_np).to(device)
+    src = torch.from_numpy(shifted_source(tgt_np)).to(device)
+    vocab = model.embed.vocab
+    # ---- samples (corpus order), their context, the batches
+    T = args.tokens_per_sample - w
+    blocks = [(s, e) for _, s, e in sample_blocks(args.data, args.gen_subset, break_mode, T, n_tok, 0)]
+    if args.first > 0:
+        blocks = blocks[:args.first]
+    blocks = blocks[args.shard_id::args.num_shards]
+    if not blocks:
+        raise ValueError("no sample to score")
+    barr = np.asarray(blocks, dtype=np.int64).reshape(-1, 2)
+    n_s = barr[:, 1] - barr[:, 0]
+    abut = bool(np.all(barr[1:, 0] == barr[:-1, 1]))
+    if w > 0 and not abut:
+        raise ValueError("--context-window needs consecutive samples (no --num-shards > 1): the context is the text in front of a sample")
+    ctx = context_lengths(n_s, T, w) if w > 0 else np.zeros(len(blocks), dtype=np.int64)
+    ctx = np.minimum(ctx, barr[:, 0])                            # (never before the start of the split; the recurrence already ensures it)
+    rows = ctx + n_s
+    budget = int(args.max_tokens or 36000)
+    bounds, b0, tok = [], 0, 0
+    for j, n in enumerate(rows.tolist()):
+        if j > b0 and (tok + n > budget or (args.max_sentences and j - b0 >= args.max_sentences)):
+            bounds.append((b0, j))
+            b0, tok = j, 0
+        tok += n
+    bounds.append((b0, len(blocks)))
+    table = BlockTable(rows, device, batches=bounds)
+    first_dev = torch.from_numpy(np.ascontiguousarray(barr[:, 0] - ctx)).to(device)
+    start_dev = torch.from_numpy(np.ascontiguousarray(barr[:, 0])).to(device)
+    scored_off = torch.from_numpy(np.concatenate([[0], np.cumsum(n_s)])).to(device)
+    # ---- the datastore writer (fairseq_cli/eval_lm.py:178-205,222-242), file names and info.json as for the gcn_feat keys
+    save = None
+    keytype = args.knn_keytype or None
+    if args.save_knnlm_dstore:
+        fp16 = bool(args.dstore_fp16)
+        suffix = "" if not keytype else f"-{keytype}"
+        save_dir = os.path.join(args.dstore_mmap, f"{args.gen_subset}_dstore{suffix}")
+        os.makedirs(save_dir, exist_ok=True)
+        info = {"dstore_size": n_tok, "hidden_size": model.d, "vocab_size": int(vocab), "dstore_fp16": fp16, "val_size": 1}
+        logger.info(f"keytype being saved: {keytype}")
+        logger.info(f"dstore info: {info}")
+        json.dump(info, open(os.path.join(save_dir, "info.json"), "w"), indent=4, sort_keys=True)
+        save = {"dir": save_dir, "idx": 0, "size": n_tok,
+                "keys": np.memmap(os.path.join(save_dir, "keys.npy"), dtype=np.float16 if fp16 else np.float32, mode="w+", shape=(n_tok, model.d)),
+                "vals": np.memmap(os.path.join(save_dir, "vals.npy"), dtype=np.int16 if fp16 and vocab < 2 ** 15 else np.int32, mode="w+",
+                                  shape=(n_tok, 1))}
+    want_words = args.output_word_probs or args.output_word_stats
+    symbols, bpe_toks, bpe_len, word_stats = None, None, 0, dict()
+    if want_words or args.remove_bpe is not None:
+        symbols = load_symbols(args.data)
+    if args.remove_bpe is not None:
+        if args.remove_bpe == "sentencepiece":
+            raise NotImplementedError
+        if symbols is None:
+            raise ValueError("--remove-bpe needs the data directory's dict.txt (the continuation marker lives in the symbols)")
+        bpe_cont = args.remove_bpe.rstrip()
+        bpe_toks = {i for i in range(len(symbols)) if symbols[i].endswith(bpe_cont)}
+        bpe_len = len(bpe_cont)
+    acc = torch.zeros(1, device=device, dtype=torch.float64)
+    keep = [] if getattr(args, "keep_pos_scores", False) else None
+    count, ntok, timers = 0, 0, []
+    chunk = int(min(args.softmax_batch, 1 << 30))
+    torch.cuda.synchronize()
+    wall0 = time.perf_counter()
+    for bi, (b0, b1) in enumerate(bounds):
+        rb = table.batch(bi)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        c_b, n_b = ctx[b0:b1], n_s[b0:b1]
+        has_ctx = bool(c_b.any())
+        if not has_ctx and (b1 - b0 == 1 or bool(np.all(barr[b0 + 1:b1, 0] == barr[b0:b1 - 1, 1]))):
+            tokens = src[int(barr[b0, 0]):int(barr[b1 - 1, 1])]                    # back-to-back samples: a view
+        else:
+            tokens = src[packed_rows(rb.block_off, first_dev[b0:b1], rb.n_tok)]
+        x, extra = model.extract_features(tokens.contiguous(), rb, want_inner=save is not None and keytype != "last_ffn_input",
+                                          want_ffn_input=save is not None and keytype == "last_ffn_input", check=False)
+        n_scored = int(n_b.sum())
+        if b1 - b0 == 1 or bool(np.all(barr[b0 + 1:b1, 0] == barr[b0:b1 - 1, 1])):
+            target = tgt[int(barr[b0, 0]):int(barr[b1 - 1, 1])]
+        else:
+            target = tgt[packed_rows(scored_off[b0:b1 + 1], start_dev[b0:b1], n_scored)]
+        # the scored rows of the batch, as (first row, rows) runs of the feature buffer: everything without a context, else one
+        # run per sample -- the head reads them in place
+        runs = [(0, rb.n_tok)] if not has_ctx else [(int(rb.offsets[j] + c_b[j]), int(n_b[j])) for j in range(b1 - b0)]
+        logp = torch.empty(n_scored, device=device, dtype=torch.float32)
+        o = 0
+        for r0, n in runs:
+            for c0 in range(0, n, chunk):
+                c1 = min(n, c0 + chunk)
+                logp[o + c0:o + c1] = model.target_logp(x[r0 + c0:r0 + c1], target[o + c0:o + c1])
+            o += n
+        ops.masked_sum_f64(logp, None, acc)                                       # score_sum, in float64
+        count += n_scored
+        ntok += rb.n_tok
+        ev1.record()
+        timers.append((ev0, ev1))
+        if keep is not None:
+            keep.append(logp)
+        if save is not None:
+            keys = extra.get(keytype) if keytype else None
+            if keys is None:
+                keys = extra["inner_states"][-1]                                 # sequence_scorer.py:181-182
+            if has_ctx:
+                keys = torch.cat([keys[r0:r0 + n] for r0, n in runs])
+            n_new = min(n_scored, save["size"] - save["idx"])
+            if n_new < n_scored:
+                logger.warning("exceed offset at sample " + str(b0))
+            sl = slice(save["idx"], save["idx"] + n_new)
+            save["keys"][sl] = keys[:n_new].to(torch.float16 if save["keys"].dtype == np.float16 else torch.float32).cpu().numpy()
+            save["vals"][sl, 0] = target[:n_new].cpu().numpy().astype(save["vals"].dtype)
+            save["idx"] += n_new
+        if want_words or bpe_toks is not None:
+            hypos, o = [], 0
+            for j in range(b1 - b0):
+                n = int(n_b[j])
+                hypos.append([{"tokens": target[o:o + n], "positional_scores": logp[o:o + n], "knn_recall": None}])
+                o += n
+            count -= word_outputs(args, hypos, list(range(b0, b1)), symbols, bpe_toks, bpe_len, word_stats)
+    score_sum = acc.item()                                                        # the only host sync of a plain run
+    model.check_tokens()                                                          # ids outside the vocabulary: counted on the device, read here
+    wall = time.perf_counter() - wall0
+    if save is not None:
+        save["keys"].flush()
+        save["vals"].flush()
+        logger.info(f"Saved {save['idx']} data to {save['dir']}")
+    gen_time = sum(a.elapsed_time(b) for a, b in timers) / 1e3
+    avg_nll_loss = -score_sum / count / math.log(2)
+    line1 = "Evaluated {} tokens in {:.1f}s ({:.2f} tokens/s)".format(ntok, gen_time, ntok / max(gen_time, 1e-9))
+    line2 = "Loss (base 2): {:.4f}, Perplexity: {:.2f}".format(avg_nll_loss, 2 ** avg_nll_loss)
+    for line in (line1, line2):
+        logger.info(line)
+        print(line)
+    if args.output_word_stats:
+        for ws in sorted(word_stats.values(), key=lambda x: x.count, reverse=True):
+            logger.info(ws)
+    res = {"score_sum": score_sum, "count": count, "ppl": 2 ** avg_nll_loss, "tokens": ntok, "seconds": gen_time,
+           "wall_seconds": wall, "word_stats": word_stats if args.output_word_stats else None, "rank": 0, "world": 1,
+           "precision": model.precision, "head": "dense" if type(model.head).__name__ == "DenseSoftmax" else "adaptive", "path": "base_lm"}
+    if getattr(args, "result_json", None):
+        with open(args.result_json, "w") as fh:
+            json.dump({k_: v for k_, v in res.items() if k_ != "word_stats"}, fh)
+    if keep is not None:
+        res["pos_scores"] = torch.cat(keep).cpu().numpy()
+    return res

@@ -10,6 +10,9 @@ fairseq/models/transformer_lm.py:122-139; recipe values: gnnlm_scripts/wiki103/h
         [--knnlm --k 1024 --lmbda 0.25 --dstore-dir DATA/train_dstore --index-file ... --temperature 0.01 \\
          --knn-sim-func do_not_recomp_ip]
 
+Without ``--graph`` the run is the base transformer LM alone -- its perplexity over ``DATA/{split}.bin/.idx``, ``--context-window``, and
+the "save features" loop that writes ``{split}_dstore/keys.npy`` (``eval_base_lm.py``).
+
 What is NOT rebuilt (out of scope): the fairseq task/dataset/checkpoint machinery.
 The driver reads the data directory's own files instead: targets are ``{split}_dstore/vals.npy`` (the
 same tokens in the same order, eval_lm.py:238-242), features ``{split}_dstore/keys.npy``, graph
@@ -557,8 +560,13 @@ def main(args, tables=None, model=None):
     writing 13 GB of ``quantized-keys.npy`` first.  Everything else is the reference's loop."""
     if args.cpu or not torch.cuda.is_available():
         raise RuntimeError("gnnlm_amd.eval_lm needs an MI355X: the product path has no CPU fallback")
-    if not (args.graph and args.use_precompute_feat):
-        raise NotImplementedError("only the --graph --use-precompute-feat eval path is built (the base LM is out of scope)")
+    if not args.graph:
+        # the base transformer LM alone: perplexity, --context-window, the "save features" loop (eval_base_lm.py)
+        from . import eval_base_lm
+        return eval_base_lm.main(args, model=model)
+    if not args.use_precompute_feat:
+        raise NotImplementedError("--graph without --use-precompute-feat (the graph decoder over live base-LM features) is not built: "
+                                  "save the features with the base LM path first (eval_lm without --graph, --save-knnlm-dstore)")
     if args.save_knnlm_dstore and not args.dstore_mmap:
         raise ValueError("--save-knnlm-dstore needs --dstore-mmap")
     if args.knnlm and args.save_knnlm_dstore:
@@ -581,7 +589,8 @@ def main(args, tables=None, model=None):
     if args.context_window > 0:
         # LMContextWindowDataset (fairseq/data/lm_context_window_dataset.py) prepends context tokens and scores only the
         # new ones; shrinking the block without the prefix would silently give another ppl
-        raise NotImplementedError("--context-window > 0 is not built (the GNN-LM recipes use --gcn-context-window)")
+        raise NotImplementedError("--context-window > 0 is not built with --graph (the GNN-LM recipes use --gcn-context-window; the base "
+                                  "LM path, eval_lm without --graph, honours it)")
     # ---- one process per GPU (torch.distributed.run): token blocks are data parallel, the code table is range-sharded
     # (the reference has no multi-GPU eval path to mirror beyond --num-shards, fairseq_cli/eval_lm.py:131-132)
     dist = torch.distributed

@@ -353,6 +353,43 @@ def gelu_(x):
     return x
 
 
+def relu_(x):
+    """In place max(x, 0) (a NaN stays a NaN, as torch.relu): the feed-forward activation of the base transformer LM."""
+    _dev(x)
+    _f32(x)
+    assert x.is_contiguous()
+    call("gnnlm_relu", ptr(x), x.numel(), stream())
+    return x
+
+
+def lm_embed(tokens, E, block_off, P=None, pad_idx=1, scale=1.0, out=None, n_bad=None):
+    """x[r] = fl32(fl32(scale * E[tokens[r]]) + P[pad_idx + 1 + position of r in its block]) for the packed rows of ``block_off`` (a
+    :class:`ragged.RaggedBatch` or offsets [n_blocks + 1]): the input of the base transformer LM (transformer.py:753-759).  ``P`` None:
+    no positional embedding.  A token id outside [0, V) gives a zero row and is counted in ``n_bad`` (device int32 [1], added to).  A
+    block longer than ``P`` holds is refused before anything is launched."""
+    from .ragged import as_ragged
+    _f32(E, P, out)
+    _dtype(tokens, torch.int64, "tokens"), _dtype(n_bad, torch.int32, "n_bad")
+    _dev(tokens, E, P, out, n_bad)
+    rg = as_ragged(block_off, tokens.device)
+    if tokens.dim() != 1 or rg.n_tok != tokens.shape[0]:
+        raise ValueError("lm_embed: tokens must be [n_tok] with n_tok = block_off[-1] - block_off[0]")
+    d = E.shape[1]
+    if out is None:
+        out = torch.empty(rg.n_tok, d, device=tokens.device, dtype=torch.float32)
+    e = _lib.gnnlm_lm_embed_t()
+    e.tokens = tokens.data_ptr()
+    e.E, e.ld_e, e.n_vocab, e.d = E.data_ptr(), E.stride(0), E.shape[0], d
+    if P is not None:
+        e.P, e.ld_p, e.p_rows = P.data_ptr(), P.stride(0), P.shape[0]
+    e.pad_idx, e.scale, e.max_len = int(pad_idx), float(scale), int(rg.lengths.max()) if rg.n_blocks else 0
+    e.out, e.ldo = out.data_ptr(), out.stride(0)
+    e.n_bad = n_bad.data_ptr() if n_bad is not None else None
+    desc = rg.desc()
+    call("gnnlm_lm_embed", ctypes.byref(e), ctypes.byref(desc), stream())
+    return out
+
+
 def half_to_float(x):
     out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
     call("gnnlm_half_to_float", ptr(x), ptr(out), x.numel(), stream())

@@ -889,6 +889,84 @@ int gnnlm_hgt_forward_ragged(const gnnlm_hgt_t* model, const gnnlm_hgt_io_t* io,
                              size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Base transformer LM: the decoder whose features the whole pipeline starts from ({split}_dstore/keys.npy, the kNN keys and
+ * queries).  Additive to ABI 12: new structs and new entries, no existing member moved.
+ * Replaces: TransformerDecoder.extract_features (fairseq/models/transformer.py:700-841) over
+ *           TransformerDecoderLayer.forward (fairseq/modules/transformer_layer.py:223-331) for a decoder-only language model
+ *           (no encoder attention, decoder_normalize_before = True: transformer_lm.py:225) in eval mode (dropout and
+ *           layer-drop are the identity).  Samples are PACKED blocks (gnnlm_ragged_t): no padding, no padding mask.
+ * ---------------------------------------------------------------------------------------------- */
+/* x[r, :] = fl32(fl32(scale * E[tok[r], :]) + P[pad_idx + 1 + (r - block_off[b]), :]) for packed row r of block b: the token
+ * embedding times embed_scale, then the positional embedding of the row's position in its own block, rounded twice as
+ * transformer.py:753-759 does (no fused multiply-add).  P is the position table [p_rows, d] -- the sinusoidal one built on the
+ * host as SinusoidalPositionalEmbedding.get_embedding does (sinusoidal_positional_embedding.py:36-60), or the learned
+ * embed_positions.weight -- or NULL (no_token_positional_embeddings: x = fl32(scale * E[tok])).  One wave per row, 16-byte
+ * loads and stores: d % 4 == 0, ld_e, ld_p, ldo multiples of 4, E / P / out 16-byte aligned.
+ * A token id outside [0, n_vocab) is never followed: its row is written as zeros and counted in *n_bad (optional DEVICE int32,
+ * added to; the caller zeroes it), and so is a row whose position lies beyond the table (memory safety only, see max_len).
+ * `max_len` is HOST data, the longest block of the call (the lengths are host-known, as for gnnlm_ragged_tiles): with P,
+ * pad_idx + 1 + max_len > p_rows is refused with GNNLM_E_INVALID before anything is launched.  blocks->tiles is not read. */
+typedef struct gnnlm_lm_embed {
+    const int64_t* tokens;     /* [n_tok] */
+    const float* E;  int64_t ld_e;  int32_t n_vocab, d;   /* [n_vocab, d] (gnnlm_amd.token_embed) */
+    const float* P;  int64_t ld_p, p_rows;                /* optional [p_rows, d] */
+    int32_t pad_idx;
+    float scale;               /* sqrt(d), or 1 with no_scale_embedding; used as given (0 is 0) */
+    int64_t max_len;           /* HOST: the longest block */
+    float* out;  int64_t ldo;  /* [n_tok, d] */
+    int32_t* n_bad;            /* optional DEVICE int32 */
+} gnnlm_lm_embed_t;
+int gnnlm_lm_embed(const gnnlm_lm_embed_t* desc, const gnnlm_ragged_t* blocks, void* stream);
+
+/* x = max(x, 0) in place (activation_fn relu of the feed-forward block, transformer_layer.py:311; a NaN stays a NaN, as
+ * torch.relu).  gnnlm_gemm_nt's store epilogue has no activation: at 4 * ffn bytes per token and layer beside 4 * d * ffn
+ * flops of GEMM an in-place pass is the right size. */
+int gnnlm_relu(float* x, int64_t n, void* stream);
+
+typedef struct gnnlm_tlm_layer {
+    const float *ln1_g, *ln1_b;            /* self_attn_layer_norm [d] */
+    const float *wqkv, *bqkv;              /* [3d, d], [3d]: q | k | v rows (in_proj_weight, or q_proj / k_proj / v_proj concatenated) */
+    const float *wo, *bo;                  /* self_attn.out_proj [d, d], [d] */
+    const float *ln2_g, *ln2_b;            /* final_layer_norm [d] */
+    const float *w1, *b1, *w2, *b2;        /* fc1 [ffn, d], [ffn]; fc2 [d, ffn], [d] */
+} gnnlm_tlm_layer_t;
+
+/* The d_k^-0.5 of `q *= self.scaling` (multihead_attention.py) is FOLDED into the q rows of wqkv and bqkv by whoever
+ * prepares the weights (gnnlm_amd.transformer_lm): the orchestrator applies no scaling.  The fold is exact when d_k is a power of
+ * 4 (16, 64: a power of two) and one extra float32 rounding of the q weights otherwise (32, 128) -- inside the 5e-5 feature bar. */
+typedef struct gnnlm_tlm {
+    int32_t L, d, H, ffn;
+    int32_t act, precision;    /* act: 0 relu, 1 gelu (the exact erf form).  precision: of every GEMM, as gnnlm_gemm_t.precision (0 f32,
+                                  1 / 2 split-bf16, 3 fp16 operands with f32 accumulation); attention, LayerNorm and the embed stay f32 */
+    float ln_eps;              /* 0 is read as 1e-5 */
+    float scale;               /* embed_scale */
+    const float* E;  int64_t ld_e;  int32_t n_vocab, pad_idx;
+    const float* P;  int64_t ld_p, p_rows;                /* optional position table (gnnlm_lm_embed_t) */
+    const float *ln_emb_g, *ln_emb_b;      /* optional layernorm_embedding (both or none) */
+    const float *ln_out_g, *ln_out_b;      /* optional final layer_norm (both or none) */
+    const gnnlm_tlm_layer_t* layers;       /* HOST array [L] */
+} gnnlm_tlm_t;
+
+typedef struct gnnlm_tlm_io {
+    const int64_t* tokens;     /* [n_tok] source tokens of the packed blocks */
+    gnnlm_ragged_t blocks;     /* block_off and tiles (gnnlm_ragged_tiles) */
+    int64_t max_len;           /* HOST: the longest block (checked against the position table) */
+    float* out;                /* [n_tok, d]: the features, after the final layer_norm when there is one */
+    float* last_inner;         /* optional [n_tok, d]: inner_states[-1], before the final layer_norm */
+    float* last_ffn_input;     /* optional [n_tok, d]: the last layer's final_layer_norm output (transformer_layer.py:309-310) */
+    int32_t* n_bad;            /* optional DEVICE int32: token ids outside [0, n_vocab), added to (gnnlm_lm_embed_t) */
+} gnnlm_tlm_io_t;
+/* Per layer: LayerNorm, ONE q|k|v GEMM [n_tok, 3d], gnnlm_causal_attn_varlen, out-projection GEMM with bias and the residual as R
+ * (in place), LayerNorm, fc1 GEMM + bias, the activation in place, fc2 GEMM + bias + residual.  Only enqueues on `stream`: no
+ * allocation, no synchronisation.  GNNLM_E_INVALID before anything is launched or written: L < 1, d / H outside {16, 32, 64, 128},
+ * H * d_k != d, d or ffn not a positive multiple of 4, act outside 0..1, precision outside 0..3, a NULL tokens / out / E / layers or
+ * layer member, half a LayerNorm pair, n_tok >= 2^31, what gnnlm_lm_embed refuses, a NULL or too small workspace.  n_tok = 0 is
+ * accepted and touches nothing.  gnnlm_transformer_lm_workspace_bytes: n_tok * (3 d + max(3 d, ffn)) floats plus alignment. */
+size_t gnnlm_transformer_lm_workspace_bytes(const gnnlm_tlm_t* model, const gnnlm_tlm_io_t* io);
+int gnnlm_transformer_lm_forward(const gnnlm_tlm_t* model, const gnnlm_tlm_io_t* io, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sharded store, requester side: bucket the requested global rows by owning rank
  * (owner = row / rows_per_rank, out-of-range rows stay on `self_rank`).
  *   counts[world]   rows per owner (device, int64)
