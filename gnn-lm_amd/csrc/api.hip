@@ -736,7 +736,7 @@ size_t gnnlm_sizeof(const char* name) {
     GNNLM_SZ(gnnlm_group_assign_t) GNNLM_SZ(gnnlm_gemm_t) GNNLM_SZ(gnnlm_gather_t) GNNLM_SZ(gnnlm_token_gather_t) GNNLM_SZ(gnnlm_star_attn_t) GNNLM_SZ(gnnlm_chain_attn_t)
     GNNLM_SZ(gnnlm_adaptive_softmax_t) GNNLM_SZ(gnnlm_dense_softmax_t) GNNLM_SZ(gnnlm_knn_interp_t) GNNLM_SZ(gnnlm_knn_interp_grid_t) GNNLM_SZ(gnnlm_knn_mix_dense_t) GNNLM_SZ(gnnlm_knn_resim_t) GNNLM_SZ(gnnlm_hgt_layer_t)
     GNNLM_SZ(gnnlm_hgt_t) GNNLM_SZ(gnnlm_hgt_io_t) GNNLM_SZ(gnnlm_profile_entry_t) GNNLM_SZ(gnnlm_topk_t) GNNLM_SZ(gnnlm_ivfpq_scan_t) GNNLM_SZ(gnnlm_ivfpq_scan8_t) GNNLM_SZ(gnnlm_ivfpq_rescore_t) GNNLM_SZ(gnnlm_ivfpq_tau_t) GNNLM_SZ(gnnlm_ivfpq_tables_t) GNNLM_SZ(gnnlm_peer_gather_t) GNNLM_SZ(gnnlm_shards_t) GNNLM_SZ(gnnlm_ragged_t)
-    GNNLM_SZ(gnnlm_lm_embed_t) GNNLM_SZ(gnnlm_tlm_layer_t) GNNLM_SZ(gnnlm_tlm_t) GNNLM_SZ(gnnlm_tlm_io_t)
+    GNNLM_SZ(gnnlm_lm_embed_t) GNNLM_SZ(gnnlm_tlm_layer_t) GNNLM_SZ(gnnlm_tlm_t) GNNLM_SZ(gnnlm_tlm_io_t) GNNLM_SZ(gnnlm_pack_rows_t)
 #undef GNNLM_SZ
     return 0;
 }

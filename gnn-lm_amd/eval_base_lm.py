@@ -18,7 +18,15 @@ Mirror of ``fairseq_cli/eval_lm.py:61-336`` with ``SequenceScorer.generate`` (fa
            of at most ``--softmax-batch`` rows; score_sum and count in float64; the reference's two final lines.
   dstore   ``--save-knnlm-dstore --dstore-mmap DIR [--dstore-fp16] [--knn-keytype last_ffn_input]``: row i = token i of the split.
 
-Not built here (refused): ``--knnlm`` without ``--graph``, more than one process, ``--graph-capture``.
+  kNN-LM   ``--knnlm --k --lmbda --temperature --probe --dstore-dir --index-file --knn-sim-func --knn-keytype`` (sequence_scorer.py:
+           102-136): the queries are the scored rows of ``extra[knn_keytype]`` if the decoder offers that key, else of
+           ``inner_states[-1]``, packed (and scaled to unit length for a cosine index) by ``ops.pack_rows``; the search is enqueued before
+           the head and finished after it; ``--lmbda 0`` searches nothing.  Only the scored rows are searched (the reference searches
+           the context rows too and drops the results), and the queries are those of ALL scored rows whatever ``--softmax-batch`` is
+           (sequence_scorer.py:105-106 takes the last softmax piece's: its own "todo").  ``--sweep-lmbda / -temperature / -k``,
+           ``--output-topk``, ``--output-knn-recall`` as on the ``--graph`` path.
+
+Not built here (refused): ``--sweep-orig-prob-ratio`` (no second model to mix), more than one process, ``--graph-capture``.
 """
 import json
 import logging
@@ -61,22 +69,25 @@ def context_lengths(lengths, tokens_per_sample, context_window):
 
 
 def check_args(args):
-    if args.knnlm:
-        raise ValueError("--knnlm without --graph (kNN-LM on the base LM) is not built: run the GNN path, or save the datastore here "
-                         "and score with --graph --use-precompute-feat --knnlm")
+    """Host only, before any device work -> ``(sweep, topk)``: the tuning grid ``(ks, temperatures, lmbdas)`` of --sweep-* or None, and
+    N of --output-topk (0: off), both as the --graph driver reads them (``eval_lm.parse_sweep`` / ``check_output_topk``)."""
+    from .eval_lm import check_output_topk, parse_sweep
+    if args.knnlm and getattr(args, "knn_model", None) is None and not (args.dstore_dir and args.index_file):
+        raise ValueError("--knnlm needs --dstore-dir and --index-file")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise NotImplementedError("the base LM path runs in one process (WORLD_SIZE > 1 is not built)")
     if getattr(args, "graph_capture", False):
         raise ValueError("--graph-capture is not built for the base LM path")
     if args.save_knnlm_dstore and not args.dstore_mmap:
         raise ValueError("--save-knnlm-dstore needs --dstore-mmap")
-    for flag in ("sweep_lmbda", "sweep_temperature", "sweep_k", "sweep_orig_prob_ratio"):
-        if getattr(args, flag, None):
-            raise ValueError(f"--{flag.replace('_', '-')} belongs to the --graph path")
-    if getattr(args, "output_topk", 0):
-        raise ValueError("--output-topk belongs to the --graph path")
-    if args.output_knn_recall:
+    if getattr(args, "sweep_orig_prob_ratio", None) is not None:
+        raise ValueError("--sweep-orig-prob-ratio belongs to the --graph path (the base LM has no second model to mix)")
+    sweep = parse_sweep(args)                                    # (needs --knnlm; not with --save-knnlm-dstore; k' <= --k <= 1024)
+    topk = check_output_topk(args)                               # (not with --sweep-*, --save-knnlm-dstore)
+    if args.output_knn_recall and not args.knnlm:
         raise ValueError("--output-knn-recall needs --knnlm")
+    if args.knnlm and args.knn_sim_func not in ("do_not_recomp_ip", "do_not_recomp_l2", "ip", "l2"):
+        raise ValueError("Invalid knn similarity function!")
     if getattr(args, "reinit_nfeat", False):
         raise ValueError("--reinit-nfeat belongs to the --graph path")
     if args.add_bos_token:
@@ -84,16 +95,18 @@ def check_args(args):
     if args.knn_keytype not in (None, "", "last_ffn_input"):
         # (sequence_scorer.py:181-182: any other key type is absent from the decoder's extra and falls back to inner_states[-1])
         logger.info("--knn-keytype %s is not a key of the base LM's outputs: inner_states[-1] is saved (as the reference)", args.knn_keytype)
+    return sweep, topk
 
 
 def main(args, model=None):
     """-> the result dict of ``eval_lm.main`` (score_sum, count, ppl, tokens, seconds, ...) plus ``pos_scores`` (float32 numpy, one
     log-probability per scored token in corpus order) when ``args.keep_pos_scores`` is set (tests, tools)."""
-    from .eval_lm import WordStat, fairseq_sentence_sizes, fairseq_token_stream, load_symbols, sample_blocks, word_outputs  # noqa: F401
+    from .eval_lm import (WordStat, fairseq_sentence_sizes, fairseq_token_stream, load_symbols, report_sweep, report_topk,  # noqa: F401
+                          sample_blocks, word_outputs)
     from .ragged import BlockTable, packed_rows
     from .transformer_lm import TransformerLM
     import ast
-    check_args(args)
+    sweep, topk = check_args(args)
     break_mode = getattr(args, "sample_break_mode", None) or "none"
     if break_mode not in token_blocks.BREAK_MODES:
         raise ValueError("Invalid break_mode: " + str(break_mode))
@@ -153,9 +166,35 @@ def main(args, model=None):
     first_dev = torch.from_numpy(np.ascontiguousarray(barr[:, 0] - ctx)).to(device)
     start_dev = torch.from_numpy(np.ascontiguousarray(barr[:, 0])).to(device)
     scored_off = torch.from_numpy(np.concatenate([[0], np.cumsum(n_s)])).to(device)
+    keytype = args.knn_keytype or None
+    # ---- kNN-LM (sequence_scorer.py:102-136): the store, and the split's tables of ops.pack_rows -- how many rows in front of every
+    # sample are context, and where its scored rows start among the batch's (offsets relative to the batch: n + 1 entries per batch)
+    knn, search, pack = None, False, None
+    if args.knnlm:
+        from .knn_model import KNNModel
+        knn = getattr(args, "knn_model", None) or KNNModel(
+            index_file=args.index_file, dstore_dir=args.dstore_dir, probe=args.probe, cuda=-1, k=args.k,
+            no_load_keys=("do_not_recomp" in args.knn_sim_func), use_memory=True, metric_type=args.knn_sim_func, device=device)
+        width = getattr(knn, "hidden_size", None)
+        if width is not None and int(width) != model.d:
+            raise ValueError(f"--knnlm: the queries are the base LM's {'last_ffn_input' if keytype == 'last_ffn_input' else 'inner_states[-1]'} "
+                             f"rows of width {model.d}, the datastore {args.dstore_dir} holds keys of hidden_size {int(width)}")
+        search = args.lmbda > 0.0 or sweep is not None                  # :102 -- `--lmbda 0` scores the LM alone; a sweep always searches
+        if search and args.knn_sim_func in ("ip", "l2") and hasattr(knn, "keys_home"):
+            logger.info(knn.keys_home())
+    if search or topk:
+        rel = np.concatenate([np.concatenate([[0], np.cumsum(n_s[b0:b1])]) for b0, b1 in bounds])
+        pack = {"skip": torch.from_numpy(ctx.astype(np.int32)).to(device), "out_off": torch.from_numpy(rel.astype(np.int32)).to(device),
+                "n_bad": torch.zeros(1, device=device, dtype=torch.int32)}
+    n_grid = len(ops.grid_points(*sweep)) if sweep else 0
+    sweep_acc = torch.zeros(n_grid, device=device, dtype=torch.float64) if sweep else None
+    top_parts = []                                                      # (first sample, ids, logp, rank) per batch
+    vocab_head = None
+    if topk:
+        from .predict import head_vocab, predict_rows
+        vocab_head = head_vocab(model.head)
     # ---- the datastore writer (fairseq_cli/eval_lm.py:178-205,222-242), file names and info.json as for the gcn_feat keys
     save = None
-    keytype = args.knn_keytype or None
     if args.save_knnlm_dstore:
         fp16 = bool(args.dstore_fp16)
         suffix = "" if not keytype else f"-{keytype}"
@@ -197,9 +236,27 @@ def main(args, model=None):
             tokens = src[int(barr[b0, 0]):int(barr[b1 - 1, 1])]                    # back-to-back samples: a view
         else:
             tokens = src[packed_rows(rb.block_off, first_dev[b0:b1], rb.n_tok)]
-        x, extra = model.extract_features(tokens.contiguous(), rb, want_inner=save is not None and keytype != "last_ffn_input",
-                                          want_ffn_input=save is not None and keytype == "last_ffn_input", check=False)
+        want_keys = save is not None or search
+        x, extra = model.extract_features(tokens.contiguous(), rb, want_inner=want_keys and keytype != "last_ffn_input",
+                                          want_ffn_input=want_keys and keytype == "last_ffn_input", check=False)
         n_scored = int(n_b.sum())
+        pending = None
+        if search:
+            # the queries (:105): the scored rows of extra[knn_keytype] if the decoder offers that key, else of inner_states[-1] -- the
+            # context rows are not searched.  One launch packs them, and scales them for a cosine index; without a context the buffer
+            # already is the query matrix.  The search is enqueued BEFORE the head, its one host read is waited for after it.
+            feats = extra.get(keytype) if keytype else None
+            if feats is None:
+                feats = extra["inner_states"][-1]
+            cosine = bool(getattr(knn, "cosine", False))
+            queries = feats
+            if has_ctx or cosine:
+                rows_q, unit_q = ops.pack_rows(feats, rb.block_off, pack["skip"][b0:b1] if has_ctx else None, pack["out_off"][b0 + bi:b1 + bi + 1],
+                                               model.d, want_rows=not cosine, want_unit=cosine, n_bad=pack["n_bad"],
+                                               out=(torch.empty(n_scored, model.d, device=device) if not cosine else None,
+                                                    torch.empty(n_scored, model.d, device=device) if cosine else None))
+                queries = unit_q if cosine else rows_q
+            pending = knn.interpolate_begin(queries, unit=True) if cosine else knn.interpolate_begin(queries)
         if b1 - b0 == 1 or bool(np.all(barr[b0 + 1:b1, 0] == barr[b0:b1 - 1, 1])):
             target = tgt[int(barr[b0, 0]):int(barr[b1 - 1, 1])]
         else:
@@ -214,6 +271,25 @@ def main(args, model=None):
                 c1 = min(n, c0 + chunk)
                 logp[o + c0:o + c1] = model.target_logp(x[r0 + c0:r0 + c1], target[o + c0:o + c1])
             o += n
+        recall, found = None, None
+        if pending is not None:
+            # one search result, up to three consumers: the grid, the run's own setting, the dense rows of --output-topk
+            found = knn.search_finish(pending) if sweep or topk else pending
+            lm_logp = logp
+            if sweep:
+                ops.rows_sum_f64(knn.interpolate_grid_finish(found, target, lm_logp, *sweep)[0], sweep_acc)
+            if args.lmbda > 0.0:                                                  # (a sweep at --lmbda 0: the scores stay the LM's)
+                logp, _, recall = knn.interpolate_finish(found, target, lm_logp, args.temperature, args.lmbda)
+            else:
+                found = None
+        if topk:
+            xs = x
+            if has_ctx:                                                          # the scored rows of the features, contiguous for the chunks
+                xs = ops.pack_rows(x, rb.block_off, pack["skip"][b0:b1], pack["out_off"][b0 + bi:b1 + bi + 1], model.d, n_bad=pack["n_bad"],
+                                   out=(torch.empty(n_scored, model.d, device=device), None))[0]
+            mix = None if found is None else dict(knn.mix_labels(found), temperature=args.temperature, lmbda=args.lmbda)
+            t_ids, t_logp, t_rank, _ = predict_rows(lambda r0, r1: model.head.log_probs(xs[r0:r1]), n_scored, vocab_head, target, topk, mix)
+            top_parts.append((b0, t_ids.to(torch.int32), t_logp, t_rank))
         ops.masked_sum_f64(logp, None, acc)                                       # score_sum, in float64
         count += n_scored
         ntok += rb.n_tok
@@ -238,11 +314,15 @@ def main(args, model=None):
             hypos, o = [], 0
             for j in range(b1 - b0):
                 n = int(n_b[j])
-                hypos.append([{"tokens": target[o:o + n], "positional_scores": logp[o:o + n], "knn_recall": None}])
+                hypos.append([{"tokens": target[o:o + n], "positional_scores": logp[o:o + n],
+                               "knn_recall": None if recall is None else recall[o:o + n]}])
                 o += n
             count -= word_outputs(args, hypos, list(range(b0, b1)), symbols, bpe_toks, bpe_len, word_stats)
     score_sum = acc.item()                                                        # the only host sync of a plain run
     model.check_tokens()                                                          # ids outside the vocabulary: counted on the device, read here
+    if pack is not None and int(pack["n_bad"].item()):
+        raise RuntimeError("the scored-row tables handed to gnnlm_pack_rows were refused on the device (a driver bug: they are built here)")
+    sweep_sums = sweep_acc.tolist() if sweep else []
     wall = time.perf_counter() - wall0
     if save is not None:
         save["keys"].flush()
@@ -255,12 +335,17 @@ def main(args, model=None):
     for line in (line1, line2):
         logger.info(line)
         print(line)
+    sweep_rows = report_sweep(sweep, sweep_sums, count) if sweep else None
+    if topk:
+        report_topk(args, topk, top_parts)
     if args.output_word_stats:
         for ws in sorted(word_stats.values(), key=lambda x: x.count, reverse=True):
             logger.info(ws)
     res = {"score_sum": score_sum, "count": count, "ppl": 2 ** avg_nll_loss, "tokens": ntok, "seconds": gen_time,
            "wall_seconds": wall, "word_stats": word_stats if args.output_word_stats else None, "rank": 0, "world": 1,
            "precision": model.precision, "head": "dense" if type(model.head).__name__ == "DenseSoftmax" else "adaptive", "path": "base_lm"}
+    if sweep:
+        res["sweep"] = sweep_rows
     if getattr(args, "result_json", None):
         with open(args.result_json, "w") as fh:
             json.dump({k_: v for k_, v in res.items() if k_ != "word_stats"}, fh)

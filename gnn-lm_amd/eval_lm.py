@@ -11,7 +11,8 @@ fairseq/models/transformer_lm.py:122-139; recipe values: gnnlm_scripts/wiki103/h
          --knn-sim-func do_not_recomp_ip]
 
 Without ``--graph`` the run is the base transformer LM alone -- its perplexity over ``DATA/{split}.bin/.idx``, ``--context-window``, and
-the "save features" loop that writes ``{split}_dstore/keys.npy`` (``eval_base_lm.py``).
+the "save features" loop that writes ``{split}_dstore/keys.npy`` (``eval_base_lm.py``), and with ``--knnlm`` plain kNN-LM
+over such a datastore.
 
 What is NOT rebuilt (out of scope): the fairseq task/dataset/checkpoint machinery.
 The driver reads the data directory's own files instead: targets are ``{split}_dstore/vals.npy`` (the
@@ -381,6 +382,32 @@ def sweep_lines(rows):
             (" k={} temperature={:g} lmbda={:g}".format(r["k"], r["temperature"], r["lmbda"]) if "k" in r else "")
         lines.append(head + " loss={:.4f} ppl={:.2f}{}".format(r["loss"], r["ppl"], "  <- best" if i == best else ""))
     return lines
+
+
+def report_sweep(sweep, sums, count, quiet=False):
+    """The end of a sweep, shared by the drivers: the grid's table from its score sums, one ``sweep ...`` line per point logged and
+    printed (``quiet``: a rank that does not report) -> the rows, for the result's ``sweep`` key."""
+    rows = sweep_table(sweep, sums, count)
+    if not quiet:
+        for line in sweep_lines(rows):
+            logger.info(line)
+            print(line)
+    return rows
+
+
+def report_topk(args, topk, top_parts):
+    """The end of an ``--output-topk N`` run, shared by the drivers.  ``top_parts``: (first sample id, ids, logp, target rank) per batch
+    (device tensors); they are put in corpus order, the ``top-1 acc | top-N acc | MRR`` line is logged and ``--topk-out`` written."""
+    from .predict import topk_stats
+    top_parts.sort(key=lambda p_: p_[0])                                                    # corpus order (lanes finish in turn)
+    cat = lambda j, shape, dt: (torch.cat([p_[j] for p_ in top_parts]).cpu().numpy() if top_parts else np.zeros(shape, dt))
+    top_ids, top_logp, top_rank = cat(1, (0, topk), np.int32), cat(2, (0, topk), np.float32), cat(3, (0,), np.int32)
+    acc1, accn, mrr = topk_stats(top_rank, topk)
+    top_line = "top-1 acc {:.4f} | top-{} acc {:.4f} | MRR {:.4f}".format(acc1, topk, accn, mrr)
+    logger.info(top_line)
+    if getattr(args, "topk_out", None):
+        with open(args.topk_out, "wb") as fh:                                               # (a file object: np.savez appends no suffix)
+            np.savez(fh, ids=top_ids.astype(np.int32), logp=top_logp.astype(np.float32), target_rank=top_rank.astype(np.int32))
 
 
 def block_ranges(n_tokens, block, context_window=0):
@@ -967,28 +994,15 @@ def main(args, tables=None, model=None):
         logger.info(line2)
         print(line1)
         print(line2)
-    sweep_rows = sweep_table(sweep, sweep_sums, count) if sweep else None
-    if sweep and (rank == 0 or not (dist.is_available() and dist.is_initialized())):
-        for line in sweep_lines(sweep_rows):
-            logger.info(line)
-            print(line)
+    sweep_rows = report_sweep(sweep, sweep_sums, count, quiet=rank != 0 and dist.is_available() and dist.is_initialized()) if sweep else None
     # the same with the reference's float32 accumulation (fairseq_cli/eval_lm.py:273-274): logged, not printed --
     # the two lines above are the reference's output.  Per rank in a multi-process run (the reference has one accumulator).
     if count_rank:
         nll32 = -float(score_sum_f32) / count_rank / math.log(2)
         logger.info("float32 accumulation order (as the reference, rank {}): Loss (base 2): {:.4f}, Perplexity: {:.2f}".format(rank, nll32, 2 ** nll32))
     if topk:
-        from .predict import topk_stats
-        top_parts.sort(key=lambda p_: p_[0])                                                # corpus order (lanes finish in turn)
-        cat = lambda j, shape, dt: (torch.cat([p_[j] for p_ in top_parts]).cpu().numpy() if top_parts else np.zeros(shape, dt))
-        top_ids, top_logp, top_rank = cat(1, (0, topk), np.int32), cat(2, (0, topk), np.float32), cat(3, (0,), np.int32)
-        acc1, accn, mrr = topk_stats(top_rank, topk)
-        top_line = "top-1 acc {:.4f} | top-{} acc {:.4f} | MRR {:.4f}".format(acc1, topk, accn, mrr)
-        logger.info(top_line)
-        if getattr(args, "topk_out", None):
-            with open(args.topk_out, "wb") as fh:                                           # (a file object: np.savez appends no suffix)
-                np.savez(fh, ids=top_ids.astype(np.int32), logp=top_logp.astype(np.float32), target_rank=top_rank.astype(np.int32))
-    if args.output_word_stats:                                                              # :333-336
+        report_topk(args, topk, top_parts)
+    if args.output_word_stats:                                                             # :333-336
         for ws in sorted(word_stats.values(), key=lambda x: x.count, reverse=True):
             logger.info(ws)
     link_bytes = getattr(fetcher, "link_bytes", None)

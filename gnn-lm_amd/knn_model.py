@@ -266,11 +266,12 @@ class KNNModel(object):
         return "kNN sim func %s: the key table stays on the host; rows gathered through pinned memory in blocks of %d queries " \
                "(%d rows per block at k = %d)" % (self.metric_type, self._host_gather_rows(self.k), self._host_gather_rows(self.k) * self.k, self.k)
 
-    def search_sims(self, queries, k=0, with_vals=False):
-        """queries [n, d] (device) -> (sims [n,k] f32, knns [n,k] i64[, knn_vals [n,k] i32 or None]), before the -1 masking."""
+    def search_sims(self, queries, k=0, with_vals=False, unit=False):
+        """queries [n, d] (device) -> (sims [n,k] f32, knns [n,k] i64[, knn_vals [n,k] i32 or None]), before the -1 masking.
+        ``unit``: the queries are already at unit length (``ops.pack_rows``): a cosine index is searched with them as they are."""
         k = k or self.k
         q = queries.float()
-        if self.cosine:                                                                 # :181-184
+        if self.cosine and not unit:                                                    # :181-184
             q = q / (q ** 2).sum(-1, keepdims=True).sqrt()
         dists, knns, kvals = self._search(q, k)
         out = (self._sims(dists, knns, q).contiguous(), knns.contiguous())
@@ -299,13 +300,14 @@ class KNNModel(object):
                                       vals=vals if kvals is None else None, n_store=self.dstore_size, knn_vals=kvals)
         return (p, recall) if return_recall else p
 
-    def interpolate_begin(self, queries, k=0):
+    def interpolate_begin(self, queries, k=0, unit=False):
         """Start the search for ``interpolate`` and return a handle for ``interpolate_finish``: the scorer enqueues the language
         model's softmax in between, so the device has work while the host waits for the search's survivor count (an index without
-        ``search_begin`` is searched here and now)."""
+        ``search_begin`` is searched here and now).  ``unit``: the queries are already at unit length (``ops.pack_rows``): a cosine
+        index is searched with them as they are."""
         k = k or self.k
         q = queries.float()
-        if self.cosine:                                                                 # :181-184
+        if self.cosine and not unit:                                                    # :181-184
             q = q / (q ** 2).sum(-1, keepdims=True).sqrt()
         # `ip` / `l2` stay two-phase as long as the keys are in HBM: search_finish enqueues the recompute behind result()
         if getattr(self.index, "has_vals", False) and hasattr(self.index, "search_begin") and \

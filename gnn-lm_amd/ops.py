@@ -390,6 +390,58 @@ def lm_embed(tokens, E, block_off, P=None, pad_idx=1, scale=1.0, out=None, n_bad
     return out
 
 
+def pack_rows(src, block_off, skip, out_off, d, want_rows=True, want_unit=False, out=None, n_bad=None):
+    """The taken rows of packed blocks as contiguous matrices (``gnnlm_pack_rows``): block b of ``src`` [n_tok, >= d] (f32, row stride
+    free) is the rows ``block_off[b] - block_off[0] .. block_off[b + 1] - block_off[0]``, its first ``skip[b]`` rows (the context) are
+    left out, and the rest lands at output rows ``out_off[b] ..``.  ``block_off`` / ``out_off`` int32 [n_blocks + 1] and ``skip`` int32
+    [n_blocks] or None are DEVICE tensors (a driver keeps one table per split and hands views).  -> ``(rows, unit)``: the rows bit for
+    bit (``want_rows``) and ``row / sqrt(sum(row ** 2))`` in float32 (``want_unit``: the query of a cosine index, knn_model.py:181-184),
+    None for what is not wanted.  ``out``: a pair of [n_out, d] f32 tensors (row stride free) to write into, either may be None.
+    The tables are checked on the device: ``n_bad`` None -- the call waits for the count of violations (4 bytes) and raises before it
+    packs anything; ``n_bad`` (device int32 [1], added to) -- nothing is read back, the caller looks at it with its results (rows the
+    tables do not describe are never read or written)."""
+    _f32(src)
+    for t, what in ((block_off, "block_off"), (skip, "skip"), (out_off, "out_off"), (n_bad, "n_bad")):
+        _dtype(t, torch.int32, what)
+    _dev(src, block_off, skip, out_off, n_bad)
+    if src.dim() != 2 or block_off.dim() != 1 or out_off.shape != block_off.shape or (skip is not None and skip.shape[0] != block_off.shape[0] - 1):
+        raise ValueError("pack_rows: src [n_tok, ld], block_off / out_off [n_blocks + 1], skip [n_blocks]")
+    if not (want_rows or want_unit):
+        raise ValueError("pack_rows: nothing is wanted (want_rows and want_unit are both False)")
+    n_blocks = block_off.shape[0] - 1
+    d = int(d)
+    if d > src.shape[1]:
+        raise ValueError(f"pack_rows: d = {d}, src has {src.shape[1]} columns")
+    rows_out, unit_out = out if out is not None else (None, None)
+    if rows_out is None and unit_out is None:
+        n_out = int(out_off[-1].item())                      # (a convenience: a driver hands its output buffers and reads nothing back)
+    else:
+        n_out = int((rows_out if rows_out is not None else unit_out).shape[0])
+    if want_rows and rows_out is None:
+        rows_out = torch.empty(n_out, d, device=src.device, dtype=torch.float32)
+    if want_unit and unit_out is None:
+        unit_out = torch.empty(n_out, d, device=src.device, dtype=torch.float32)
+    rows_out, unit_out = rows_out if want_rows else None, unit_out if want_unit else None
+    _f32(rows_out, unit_out)
+    _dev(rows_out, unit_out)
+    for t in (rows_out, unit_out):
+        if t is not None and (t.dim() != 2 or t.shape[0] != n_out or t.shape[1] < d):
+            raise ValueError(f"pack_rows: an output must be [n_out = {n_out}, >= {d}]")
+    q = _lib.gnnlm_pack_rows_t()
+    q.src, q.ld_src = src.data_ptr(), src.stride(0)
+    q.block_off, q.out_off = block_off.data_ptr(), out_off.data_ptr()
+    q.skip = skip.data_ptr() if skip is not None else None
+    if rows_out is not None:
+        q.dst, q.ld_dst = rows_out.data_ptr(), rows_out.stride(0)
+    if unit_out is not None:
+        q.dst_unit, q.ld_unit = unit_out.data_ptr(), unit_out.stride(0)
+    q.n_blocks, q.d, q.n_tok, q.n_out = n_blocks, d, src.shape[0], n_out
+    count = n_bad if n_bad is not None else torch.zeros(1, device=src.device, dtype=torch.int32)
+    q.n_bad, q.wait = count.data_ptr(), int(n_bad is None)
+    call_desc("gnnlm_pack_rows", q)
+    return rows_out, unit_out
+
+
 def half_to_float(x):
     out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
     call("gnnlm_half_to_float", ptr(x), ptr(out), x.numel(), stream())

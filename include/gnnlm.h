@@ -967,6 +967,43 @@ int gnnlm_transformer_lm_forward(const gnnlm_tlm_t* model, const gnnlm_tlm_io_t*
                                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * kNN-LM on the base LM: the SCORED rows of packed samples (each sample = context rows, then scored rows: --context-window) as
+ * one contiguous [n_out, d] query matrix, and / or the same rows scaled to unit length for a cosine index -- one launch instead of
+ * one slice per sample + torch.cat + the four-op normalisation.  Additive to ABI 12: a new struct and a new entry.
+ * Replaces: the slice of sequence_scorer.py:115-118 (which searches every row, context included; here only the scored rows are
+ *           searched) and `queries / torch.sqrt(torch.sum(queries ** 2, dim=-1, keepdims=True))` of knn/knn_model.py:181-184.
+ * Output row r, r in [out_off[b], out_off[b + 1]), is source row (block_off[b] - block_off[0]) + skip[b] + (r - out_off[b]).
+ *   dst      the row as it is, bit for bit.
+ *   dst_unit fl32(x / fl32(sqrt(s))), s = the float32 sum of the row's d squares (order unspecified; products may be fused into the
+ *            sum): a correctly rounded square root, then a correctly rounded DIVISION per element -- the reference's expression, not
+ *            a multiplication by the reciprocal.  A zero row gives what the division gives (0 / 0 = NaN); it is not special-cased.
+ * One wave per output row, the row's block found by bisection of out_off (as gnnlm_lm_embed finds its block).  16-byte loads and
+ * stores when d, every stride in use and every pointer in use allow (multiples of 4 floats / 16 bytes); a scalar path otherwise.
+ * GNNLM_E_INVALID before anything is launched: d <= 0, a stride < d, both outputs NULL, a negative count, n_out >= 2^31, a missing
+ * table, a pointer that is not 4-byte aligned.
+ * The TABLES are checked on the device, by a one-block kernel that counts violations into *n_bad (DEVICE int32, zeroed by the
+ * caller, added to): skip[b] < 0, skip[b] > the block's length, a block of negative length, out_off[0] != 0,
+ * out_off[b + 1] - out_off[b] != length - skip, out_off[n_blocks] != n_out.  With wait != 0 the call waits for that count (4 bytes;
+ * the stream is synchronised) and refuses a violation with GNNLM_E_INVALID before the pack kernel is launched -- no output is
+ * touched.  With wait == 0 nothing is read back (the hot path: the caller looks at *n_bad when it looks at its results).  n_bad
+ * NULL: the tables are not checked.  In every mode the pack kernel itself follows no table entry it cannot verify: a row whose
+ * block is described outside [0, n_tok), whose skip is outside [0, length] or that lies beyond what its block yields is skipped,
+ * never read and never written. */
+typedef struct gnnlm_pack_rows {
+    const float* src;  int64_t ld_src;      /* [n_tok, ld_src], ld_src >= d */
+    const int32_t* block_off;               /* DEVICE [n_blocks + 1], as gnnlm_ragged_t: only differences from block_off[0] are read */
+    const int32_t* skip;                    /* DEVICE [n_blocks]: rows at the front of each block that are NOT taken; NULL = 0 */
+    const int32_t* out_off;                 /* DEVICE [n_blocks + 1]: prefix sums of (length - skip), out_off[0] = 0 */
+    float* dst;  int64_t ld_dst;            /* [n_out, d] the rows as they are; may be NULL */
+    float* dst_unit;  int64_t ld_unit;      /* [n_out, d] the rows scaled to unit length; may be NULL */
+    int32_t n_blocks, d;
+    int64_t n_tok, n_out;
+    int32_t* n_bad;                         /* optional DEVICE int32: table violations, added to */
+    int32_t wait;                           /* != 0 (needs n_bad): read the count back and refuse a violation before the pack kernel */
+} gnnlm_pack_rows_t;
+int gnnlm_pack_rows(const gnnlm_pack_rows_t* desc, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sharded store, requester side: bucket the requested global rows by owning rank
  * (owner = row / rows_per_rank, out-of-range rows stay on `self_rank`).
  *   counts[world]   rows per owner (device, int64)

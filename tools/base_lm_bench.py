@@ -12,6 +12,12 @@ Reports, each named for what it is:
   * the error of one sample against the float64 restatement (tests/transformer_lm_ref.py), max|dev - ref64| / max|ref64|;
   * the baseline: the float32 torch-CPU evaluation of that restatement, timed in the same run.
 Seeded synthetic weights; no output layer (the head's cost is tools/dense_head_bench.py's subject).
+
+    python tools/base_lm_bench.py --no-reference --knnlm > profiles/r18_base_knnlm_bench.txt
+
+adds the kNN-LM leg (``knnlm_leg``): forward, pack, search, head, interpolation and the whole batch at --max-tokens
+3072 and 36000 over a synthetic IVF-PQ index of --knn-keys keys (a plain tied output layer stands in for the head); the driver with
+and without --knnlm; gnnlm_pack_rows against the torch form it replaces at 1, 11 and 256 samples per batch.
 """
 import argparse
 import json
@@ -46,8 +52,150 @@ def device_clock_hz(props, index):
     return float(khz) * 1e3
 
 
+def median_ms(fns, steps, warmup):
+    """Device-event time of every callable of ``fns``, the callables taking turns (one round = each of them once, so that clock and
+    cache state are shared): ``warmup`` rounds, then the median of ``steps`` rounds each, in ms."""
+    times = [[] for _ in fns]
+    for r in range(warmup + steps):
+        for j, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if r >= warmup:
+                times[j].append(e0.elapsed_time(e1))
+    return [float(np.median(t)) for t in times], [(float(min(t)), float(max(t))) for t in times]
+
+
+class SyntheticKnn:
+    """The ``KNNModel`` the driver talks to, over a shape-true synthetic IVF-PQ index with labels attached (no files)."""
+
+    def __new__(cls, index, vals, k, d, dev):
+        from gnnlm_amd.knn_model import KNNModel
+        m = KNNModel.__new__(KNNModel)
+        m.index, m.k, m.metric_type, m.index_file = index, k, "do_not_recomp_ip", "synthetic.cosine"
+        m.dstore_size, m.hidden_size, m.device, m._vals_dev, m.data_store = int(vals.shape[0]), d, dev, vals, None
+        index.attach_vals(vals)
+        return m
+
+
+def knnlm_leg(A, model, m, dev):
+    """--knnlm: the stages of a batch of the recipe's shape (forward, pack, search, interpolation) and the whole batch through the
+    driver with and without --knnlm, at --max-tokens = one sample and 36000; then gnnlm_pack_rows against the torch form it
+    replaces.  Device events, the median of --steps rounds after --warmup, the compared forms taking turns."""
+    import tempfile
+    from gnnlm_amd import eval_base_lm, ops
+    from gnnlm_amd.dense_softmax import DenseSoftmax
+    from gnnlm_amd.eval_lm import get_parser
+    from gnnlm_amd.ragged import BlockTable
+    from gnnlm_amd.synthetic import synthetic_ivfpq_index
+    n, d, ctx = A.sample, A.d, A.context
+    scored = n - ctx
+    model.head = DenseSoftmax(torch.from_numpy(m["E"]), None, dev)
+    t0 = time.perf_counter()
+    index = synthetic_ivfpq_index(A.knn_keys, d, A.nlist, 64, dev, nprobe=A.nprobe)
+    vals = torch.randint(4, A.vocab, (A.knn_keys,), device=dev, dtype=torch.int32)
+    knn = SyntheticKnn(index, vals, A.k, d, dev)
+    torch.cuda.synchronize()
+    print(f"\n--knnlm leg: synthetic IVF-PQ index of {A.knn_keys:,} keys ({A.nlist} lists, PQ64, nprobe {A.nprobe}, k = {A.k}), built in "
+          f"{time.perf_counter() - t0:.1f} s; cosine (unit queries from gnnlm_pack_rows); do_not_recomp_ip")
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(3)
+    for max_tokens in (n, 36000):
+        ns = max(1, max_tokens // n)
+        rb = BlockTable([n] * ns, dev).batch(0)
+        tokens = torch.randint(0, A.vocab, (ns * n,), device=dev, generator=gen)
+        skip = torch.full((ns,), ctx, device=dev, dtype=torch.int32)
+        out_off = (torch.arange(ns + 1, device=dev, dtype=torch.int32) * scored).contiguous()
+        target = torch.randint(4, A.vocab, (ns * scored,), device=dev, generator=gen)
+        state = {}
+
+        def forward():
+            state["x"], state["extra"] = model.extract_features(tokens, rb, want_inner=True, want_ffn_input=False, check=False)
+
+        def pack():
+            state["q"] = ops.pack_rows(state["extra"]["inner_states"][-1], rb.block_off, skip, out_off, d, want_rows=False, want_unit=True,
+                                       n_bad=bad, out=(None, qbuf))[1]
+
+        def search():
+            state["found"] = knn.search_finish(knn.interpolate_begin(state["q"], unit=True))
+
+        def head():
+            state["lm"] = torch.cat([model.target_logp(state["x"][j * n + ctx:(j + 1) * n], target[j * scored:(j + 1) * scored]) for j in range(ns)])
+
+        def interp():
+            knn.interpolate_finish(state["found"], target, state["lm"], 1.0, 0.25)
+
+        bad = torch.zeros(1, device=dev, dtype=torch.int32)
+        qbuf = torch.empty(ns * scored, d, device=dev)
+
+        def batch():
+            forward(), pack()
+            pending = knn.interpolate_begin(state["q"], unit=True)
+            head()
+            knn.interpolate_finish(pending, target, state["lm"], 1.0, 0.25)
+
+        med, span = median_ms([forward, pack, search, head, interp, batch], A.steps, A.warmup)
+        print(f"  --max-tokens {max_tokens}: {ns} sample(s) of {n} rows, {ns * scored} scored (= searched; the reference searches all {ns * n})")
+        for name, v, (lo, hi) in zip(("forward", "pack (unit rows)", "search", "head (target log-probs)", "interpolation", "whole batch"), med, span):
+            print(f"    {name:26s} {v:9.3f} ms   (min {lo:.3f}, max {hi:.3f})")
+        print(f"    tokens/s scored: {ns * scored / med[5] * 1e3:,.0f} with kNN; forward + head alone {ns * scored / (med[0] + med[3]) * 1e3:,.0f}")
+    # ---- the driver itself, with and without --knnlm, over a synthetic split of 22 samples
+    with tempfile.TemporaryDirectory() as td:
+        n_tok = 22 * scored
+        # DATA/test.bin/.idx in fairseq's mmap format: one sentence of n_tok int32 tokens
+        import struct
+        with open(os.path.join(td, "test.idx"), "wb") as f:
+            f.write(b"MMIDIDX\x00\x00" + struct.pack("<Q", 1) + struct.pack("<B", 4) + struct.pack("<Q", 1))
+            f.write(np.asarray([n_tok], np.int32).tobytes() + np.asarray([0], np.int64).tobytes())
+        np.random.RandomState(4).randint(4, A.vocab, size=n_tok).astype(np.int32).tofile(os.path.join(td, "test.bin"))
+        for max_tokens in (n, 36000):
+            for with_knn in (False, True):
+                args = get_parser().parse_args([td, "--path", "-", "--gen-subset", "test", "--sample-break-mode", "none", "--tokens-per-sample", str(n),
+                                                "--context-window", str(ctx), "--max-tokens", str(max_tokens), "--softmax-batch", "1024"] +
+                                               (["--knnlm", "--k", str(A.k), "--lmbda", "0.25", "--probe", str(A.nprobe)] if with_knn else []))
+                args.knn_model = knn if with_knn else None
+                import contextlib
+                import io
+                runs = []
+                with contextlib.redirect_stdout(io.StringIO()):
+                    for _ in range(1 + 3):
+                        runs.append(eval_base_lm.main(args, model=model))
+                r = sorted(runs[1:], key=lambda r_: r_["seconds"])[1]
+                print(f"  driver, --max-tokens {max_tokens}{' --knnlm' if with_knn else ''}: {r['count']} scored of {r['tokens']} computed in {r['seconds'] * 1e3:.1f} ms "
+                      f"(median of 3 after 1 warm-up, batch event timers) = {r['count'] / r['seconds']:,.0f} tokens/s scored")
+    # ---- gnnlm_pack_rows against the torch form it replaces (per-sample slices + cat + the four-op normalisation)
+    print("  gnnlm_pack_rows (unit rows of the scored runs) against the torch form (slices + cat, then q / (q ** 2).sum(-1, keepdims=True).sqrt()):")
+    for ns in (1, 11, 256):
+        feats = torch.randn(ns * n, d, device=dev, generator=gen)
+        rb = BlockTable([n] * ns, dev).batch(0)
+        skip = torch.full((ns,), ctx, device=dev, dtype=torch.int32)
+        out_off = (torch.arange(ns + 1, device=dev, dtype=torch.int32) * scored).contiguous()
+        qbuf = torch.empty(ns * scored, d, device=dev)
+        bad = torch.zeros(1, device=dev, dtype=torch.int32)
+
+        def kernel():
+            ops.pack_rows(feats, rb.block_off, skip, out_off, d, want_rows=False, want_unit=True, n_bad=bad, out=(None, qbuf))
+
+        def torch_form():
+            q = torch.cat([feats[j * n + ctx:(j + 1) * n] for j in range(ns)])
+            return q / (q ** 2).sum(-1, keepdims=True).sqrt()
+
+        (tk, tt), _ = median_ms([kernel, torch_form], A.steps, A.warmup)
+        moved = 2.0 * ns * scored * d * 4
+        print(f"    {ns:4d} sample(s): kernel {tk * 1e3:8.1f} us ({moved / tk / 1e6:7.1f} GB/s of the {moved / 1e6:.1f} MB it must move)   "
+              f"torch {tt * 1e3:8.1f} us   ratio {tt / tk:.2f}x")
+        assert int(bad.item()) == 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--knnlm", action="store_true", help="add the kNN-LM leg (knnlm_leg)")
+    ap.add_argument("--knn-keys", type=int, default=103227021, help="keys of the synthetic IVF-PQ index (WikiText-103 train: 103,227,021)")
+    ap.add_argument("--nlist", type=int, default=4096)
+    ap.add_argument("--nprobe", type=int, default=32)
+    ap.add_argument("--k", type=int, default=1024)
     ap.add_argument("--layers", type=int, default=16)
     ap.add_argument("--d", type=int, default=1024)
     ap.add_argument("--heads", type=int, default=8)
@@ -141,6 +289,8 @@ def main():
               f"{n / t32:,.0f} tokens/s computed -> the device forward is {t32 / sec:,.0f}x faster   (float64: {t64:.2f} s)")
         res.update({"err_out": tr.rel_err(got["out"], ref["out"]), "cpu_f32_s": t32, "cpu_f64_s": t64})
     print(json.dumps({k: v for k, v in res.items() if k != "kernels"}))
+    if A.knnlm:
+        knnlm_leg(A, model, m, dev)
 
 
 if __name__ == "__main__":
