@@ -28,16 +28,14 @@ Mirror of ``fairseq_cli/eval_lm.py:61-336`` with ``SequenceScorer.generate`` (fa
 
 Not built here (refused): ``--sweep-orig-prob-ratio`` (no second model to mix), more than one process, ``--graph-capture``.
 """
-import json
 import logging
-import math
 import os
 import time
 
 import numpy as np
 import torch
 
-from . import ops, token_blocks
+from . import ops
 
 logger = logging.getLogger("gnnlm_amd.eval_lm")
 
@@ -101,21 +99,16 @@ def check_args(args):
 def main(args, model=None):
     """-> the result dict of ``eval_lm.main`` (score_sum, count, ppl, tokens, seconds, ...) plus ``pos_scores`` (float32 numpy, one
     log-probability per scored token in corpus order) when ``args.keep_pos_scores`` is set (tests, tools)."""
-    from .eval_lm import (WordStat, fairseq_sentence_sizes, fairseq_token_stream, load_symbols, report_sweep, report_topk,  # noqa: F401
-                          sample_blocks, word_outputs)
+    from .eval_lm import (DstoreWriter, budget_batches, check_break_mode, fairseq_token_stream, report_result, report_sweep, report_topk,
+                          sample_blocks, word_output_setup, word_outputs, write_result_json)
     from .ragged import BlockTable, packed_rows
     from .transformer_lm import TransformerLM
     import ast
     sweep, topk = check_args(args)
-    break_mode = getattr(args, "sample_break_mode", None) or "none"
-    if break_mode not in token_blocks.BREAK_MODES:
-        raise ValueError("Invalid break_mode: " + str(break_mode))
+    break_mode = check_break_mode(args)
     w = int(args.context_window)
     if w < 0 or w >= args.tokens_per_sample:
         raise ValueError(f"--context-window {w} must lie in [0, --tokens-per-sample {args.tokens_per_sample})")
-    if args.save_knnlm_dstore and break_mode == "complete_doc":
-        raise ValueError("--save-knnlm-dstore writes one row per token of the split in corpus order; --sample-break-mode complete_doc "
-                         "drops the document separators")
     if w > 0 and break_mode == "complete_doc":
         raise ValueError("--context-window with --sample-break-mode complete_doc is not built (the dropped separators leave gaps in the context)")
     device = torch.device(args.device)
@@ -154,14 +147,7 @@ def main(args, model=None):
     ctx = context_lengths(n_s, T, w) if w > 0 else np.zeros(len(blocks), dtype=np.int64)
     ctx = np.minimum(ctx, barr[:, 0])                            # (never before the start of the split; the recurrence already ensures it)
     rows = ctx + n_s
-    budget = int(args.max_tokens or 36000)
-    bounds, b0, tok = [], 0, 0
-    for j, n in enumerate(rows.tolist()):
-        if j > b0 and (tok + n > budget or (args.max_sentences and j - b0 >= args.max_sentences)):
-            bounds.append((b0, j))
-            b0, tok = j, 0
-        tok += n
-    bounds.append((b0, len(blocks)))
+    bounds = budget_batches(rows.tolist(), int(args.max_tokens or 36000), args.max_sentences)
     table = BlockTable(rows, device, batches=bounds)
     first_dev = torch.from_numpy(np.ascontiguousarray(barr[:, 0] - ctx)).to(device)
     start_dev = torch.from_numpy(np.ascontiguousarray(barr[:, 0])).to(device)
@@ -193,33 +179,12 @@ def main(args, model=None):
     if topk:
         from .predict import head_vocab, predict_rows
         vocab_head = head_vocab(model.head)
-    # ---- the datastore writer (fairseq_cli/eval_lm.py:178-205,222-242), file names and info.json as for the gcn_feat keys
+    # ---- the datastore writer (eval_lm.DstoreWriter): file names and info.json as for the gcn_feat keys
     save = None
     if args.save_knnlm_dstore:
-        fp16 = bool(args.dstore_fp16)
-        suffix = "" if not keytype else f"-{keytype}"
-        save_dir = os.path.join(args.dstore_mmap, f"{args.gen_subset}_dstore{suffix}")
-        os.makedirs(save_dir, exist_ok=True)
-        info = {"dstore_size": n_tok, "hidden_size": model.d, "vocab_size": int(vocab), "dstore_fp16": fp16, "val_size": 1}
-        logger.info(f"keytype being saved: {keytype}")
-        logger.info(f"dstore info: {info}")
-        json.dump(info, open(os.path.join(save_dir, "info.json"), "w"), indent=4, sort_keys=True)
-        save = {"dir": save_dir, "idx": 0, "size": n_tok,
-                "keys": np.memmap(os.path.join(save_dir, "keys.npy"), dtype=np.float16 if fp16 else np.float32, mode="w+", shape=(n_tok, model.d)),
-                "vals": np.memmap(os.path.join(save_dir, "vals.npy"), dtype=np.int16 if fp16 and vocab < 2 ** 15 else np.int32, mode="w+",
-                                  shape=(n_tok, 1))}
+        save = DstoreWriter(args.dstore_mmap, args.gen_subset, keytype, n_tok, model.d, vocab, bool(args.dstore_fp16))
     want_words = args.output_word_probs or args.output_word_stats
-    symbols, bpe_toks, bpe_len, word_stats = None, None, 0, dict()
-    if want_words or args.remove_bpe is not None:
-        symbols = load_symbols(args.data)
-    if args.remove_bpe is not None:
-        if args.remove_bpe == "sentencepiece":
-            raise NotImplementedError
-        if symbols is None:
-            raise ValueError("--remove-bpe needs the data directory's dict.txt (the continuation marker lives in the symbols)")
-        bpe_cont = args.remove_bpe.rstrip()
-        bpe_toks = {i for i in range(len(symbols)) if symbols[i].endswith(bpe_cont)}
-        bpe_len = len(bpe_cont)
+    (symbols, bpe_toks, bpe_len), word_stats = word_output_setup(args), dict()
     acc = torch.zeros(1, device=device, dtype=torch.float64)
     keep = [] if getattr(args, "keep_pos_scores", False) else None
     count, ntok, timers = 0, 0, []
@@ -303,13 +268,7 @@ def main(args, model=None):
                 keys = extra["inner_states"][-1]                                 # sequence_scorer.py:181-182
             if has_ctx:
                 keys = torch.cat([keys[r0:r0 + n] for r0, n in runs])
-            n_new = min(n_scored, save["size"] - save["idx"])
-            if n_new < n_scored:
-                logger.warning("exceed offset at sample " + str(b0))
-            sl = slice(save["idx"], save["idx"] + n_new)
-            save["keys"][sl] = keys[:n_new].to(torch.float16 if save["keys"].dtype == np.float16 else torch.float32).cpu().numpy()
-            save["vals"][sl, 0] = target[:n_new].cpu().numpy().astype(save["vals"].dtype)
-            save["idx"] += n_new
+            save.append(keys, target, b0)
         if want_words or bpe_toks is not None:
             hypos, o = [], 0
             for j in range(b1 - b0):
@@ -325,30 +284,21 @@ def main(args, model=None):
     sweep_sums = sweep_acc.tolist() if sweep else []
     wall = time.perf_counter() - wall0
     if save is not None:
-        save["keys"].flush()
-        save["vals"].flush()
-        logger.info(f"Saved {save['idx']} data to {save['dir']}")
+        save.close()
     gen_time = sum(a.elapsed_time(b) for a, b in timers) / 1e3
-    avg_nll_loss = -score_sum / count / math.log(2)
-    line1 = "Evaluated {} tokens in {:.1f}s ({:.2f} tokens/s)".format(ntok, gen_time, ntok / max(gen_time, 1e-9))
-    line2 = "Loss (base 2): {:.4f}, Perplexity: {:.2f}".format(avg_nll_loss, 2 ** avg_nll_loss)
-    for line in (line1, line2):
-        logger.info(line)
-        print(line)
+    ppl = report_result(score_sum, count, ntok, gen_time)
     sweep_rows = report_sweep(sweep, sweep_sums, count) if sweep else None
     if topk:
         report_topk(args, topk, top_parts)
     if args.output_word_stats:
         for ws in sorted(word_stats.values(), key=lambda x: x.count, reverse=True):
             logger.info(ws)
-    res = {"score_sum": score_sum, "count": count, "ppl": 2 ** avg_nll_loss, "tokens": ntok, "seconds": gen_time,
+    res = {"score_sum": score_sum, "count": count, "ppl": ppl, "tokens": ntok, "seconds": gen_time,
            "wall_seconds": wall, "word_stats": word_stats if args.output_word_stats else None, "rank": 0, "world": 1,
            "precision": model.precision, "head": "dense" if type(model.head).__name__ == "DenseSoftmax" else "adaptive", "path": "base_lm"}
     if sweep:
         res["sweep"] = sweep_rows
-    if getattr(args, "result_json", None):
-        with open(args.result_json, "w") as fh:
-            json.dump({k_: v for k_, v in res.items() if k_ != "word_stats"}, fh)
+    write_result_json(getattr(args, "result_json", None), res)
     if keep is not None:
         res["pos_scores"] = torch.cat(keep).cpu().numpy()
     return res

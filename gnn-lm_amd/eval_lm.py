@@ -410,6 +410,99 @@ def report_topk(args, topk, top_parts):
             np.savez(fh, ids=top_ids.astype(np.int32), logp=top_logp.astype(np.float32), target_rank=top_rank.astype(np.int32))
 
 
+def report_result(score_sum, count, ntok, gen_time, quiet=False):
+    """The reference's two final lines (fairseq_cli/eval_lm.py:325-331), logged and printed (``quiet``: a rank that does not
+    report) -> the perplexity."""
+    avg_nll_loss = -score_sum / count / math.log(2)
+    line1 = "Evaluated {} tokens in {:.1f}s ({:.2f} tokens/s)".format(ntok, gen_time, ntok / max(gen_time, 1e-9))
+    line2 = "Loss (base 2): {:.4f}, Perplexity: {:.2f}".format(avg_nll_loss, 2 ** avg_nll_loss)
+    if not quiet:
+        logger.info(line1)
+        logger.info(line2)
+        print(line1)
+        print(line2)
+    return 2 ** avg_nll_loss
+
+
+def write_result_json(path, res, rank=0, world=1):
+    """``--result-json PATH``: the result without ``word_stats``; of several processes rank r writes PATH.rank<r>, rank 0 also PATH."""
+    if not path:
+        return
+    js = {k_: v for k_, v in res.items() if k_ != "word_stats"}
+    for p_ in ([path + f".rank{rank}"] if world > 1 else []) + ([path] if rank == 0 else []):
+        with open(p_, "w") as fh:
+            json.dump(js, fh)
+
+
+def known_break_mode(break_mode):
+    """-> the mode (None is ``none``), or the reference's ``ValueError`` (token_block_utils_fast.pyx:102)."""
+    mode = "none" if break_mode is None else break_mode
+    if mode not in token_blocks.BREAK_MODES:
+        raise ValueError("Invalid break_mode: " + str(break_mode))
+    return mode
+
+
+def check_break_mode(args):
+    """-> ``--sample-break-mode`` (``none`` when absent or empty), checked before any device work."""
+    break_mode = known_break_mode(getattr(args, "sample_break_mode", None) or "none")
+    if args.save_knnlm_dstore and break_mode == "complete_doc":
+        raise ValueError("--save-knnlm-dstore writes one row per token of the split in corpus order; --sample-break-mode complete_doc "
+                         "drops the document separators")
+    return break_mode
+
+
+def word_output_setup(args):
+    """``(symbols, bpe_toks, bpe_len)`` of --output-word-probs / --output-word-stats / --remove-bpe (fairseq_cli/eval_lm.py:146-160):
+    the dictionary's symbols when words are printed, and the ids (and the length) of the BPE continuation marker."""
+    symbols, bpe_toks, bpe_len = None, None, 0
+    if args.output_word_probs or args.output_word_stats or args.remove_bpe is not None:
+        symbols = load_symbols(args.data)
+    if args.remove_bpe is not None:
+        if args.remove_bpe == "sentencepiece":
+            raise NotImplementedError                                        # as the reference (:148-149)
+        if symbols is None:
+            raise ValueError("--remove-bpe needs the data directory's dict.txt (the continuation marker lives in the symbols)")
+        bpe_cont = args.remove_bpe.rstrip()
+        bpe_toks = {i for i in range(len(symbols)) if symbols[i].endswith(bpe_cont)}
+        bpe_len = len(bpe_cont)
+    return symbols, bpe_toks, bpe_len
+
+
+class DstoreWriter:
+    """``--save-knnlm-dstore`` (fairseq_cli/eval_lm.py:103-104,178-205,222-242,322-323): ``{root}/{subset}_dstore[-keytype]/`` with
+    ``info.json`` and the raw memmaps ``keys.npy [size, dim]`` and ``vals.npy [size, 1]``, filled in the order of the appends."""
+
+    def __init__(self, root, subset, keytype, size, dim, vocab, fp16):
+        self.dir = os.path.join(root, f"{subset}_dstore" + ("" if not keytype else f"-{keytype}"))
+        os.makedirs(self.dir, exist_ok=True)
+        self.idx, self.size, self.dim = 0, size, dim
+        info = {"dstore_size": size, "hidden_size": dim, "vocab_size": int(vocab), "dstore_fp16": fp16, "val_size": 1}
+        logger.info(f"keytype being saved: {keytype}")
+        logger.info(f"dstore info: {info}")
+        json.dump(info, open(os.path.join(self.dir, "info.json"), "w"), indent=4, sort_keys=True)
+        self.keys = np.memmap(os.path.join(self.dir, "keys.npy"), dtype=np.float16 if fp16 else np.float32, mode="w+", shape=(size, dim))
+        self.vals = np.memmap(os.path.join(self.dir, "vals.npy"), dtype=np.int16 if fp16 and vocab < 2 ** 15 else np.int32, mode="w+",
+                              shape=(size, 1))
+
+    def append(self, keys, vals, where):
+        """``keys [n, dim]`` and their ``vals [n]`` (tensors): one device -> host copy each.  Rows past ``size`` are dropped, with the
+        reference's warning (:227-230) that names the sample ``where``."""
+        if keys.shape[-1] != self.dim:
+            raise ValueError(f"--save-knnlm-dstore: the scorer returned {keys.shape[-1]}-dimensional keys, the datastore was opened for {self.dim}")
+        n_new = min(keys.shape[0], self.size - self.idx)
+        if n_new < keys.shape[0]:
+            logger.warning("exceed offset at sample " + str(int(where)))
+        sl = slice(self.idx, self.idx + n_new)
+        self.keys[sl] = keys[:n_new].to(torch.float16 if self.keys.dtype == np.float16 else torch.float32).cpu().numpy()
+        self.vals[sl, 0] = vals[:n_new].cpu().numpy().astype(self.vals.dtype)
+        self.idx += n_new
+
+    def close(self):
+        self.keys.flush()
+        self.vals.flush()
+        logger.info(f"Saved {self.idx} data to {self.dir}")                             # :322-323
+
+
 def block_ranges(n_tokens, block, context_window=0):
     """(context_start, start, end) of every block under --sample-break-mode none
     (token_block_utils_fast.pyx:22-35) with the --gcn-context-window prefix of
@@ -444,9 +537,7 @@ def sample_blocks(data, split, break_mode, block, n_tokens, context_window=0):
     :func:`block_ranges` and needs nothing but the token count; ``complete`` / ``complete_doc`` / ``eos`` cut at the sentence
     boundaries of ``DATA/{split}.idx`` (token_blocks.py) and raise ``FileNotFoundError`` without it; anything else is the
     reference's ``ValueError('Invalid break_mode: ...')`` (token_block_utils_fast.pyx:102)."""
-    mode = "none" if break_mode is None else break_mode
-    if mode not in token_blocks.BREAK_MODES:
-        raise ValueError("Invalid break_mode: " + str(break_mode))
+    mode = known_break_mode(break_mode)
     if mode == "none":
         return block_ranges(n_tokens, block, context_window)
     sizes = fairseq_sentence_sizes(data, split)
@@ -457,6 +548,32 @@ def sample_blocks(data, split, break_mode, block, n_tokens, context_window=0):
     if total != n_tokens:
         raise ValueError(f"{os.path.join(data, split + '.idx')}: its sentences hold {total} tokens, the split's datastore {n_tokens}")
     return token_blocks.block_ranges(sizes, mode, block, context_window)
+
+
+def budget_batches(lengths, budget, max_sentences=0):
+    """Bounds ``(b0, b1)`` of the batches of ragged samples: consecutive items in order, a batch ends before the item that would take
+    it past ``budget`` tokens or once it holds ``max_sentences`` items (0 / None: any number); an item longer than the budget is a
+    batch of its own."""
+    bounds, b0, tok = [], 0, 0
+    for j, n in enumerate(lengths):
+        if j > b0 and (tok + n > budget or (max_sentences and j - b0 >= max_sentences)):
+            bounds.append((b0, j))
+            b0, tok = j, 0
+        tok += n
+    return bounds + [(b0, len(lengths))] if len(lengths) else bounds
+
+
+def equal_length_batches(blocks, per_batch):
+    """The batches of ``--sample-break-mode none``: runs of consecutive equally long blocks (context included), up to ``per_batch``."""
+    batches_, i = [], 0
+    while i < len(blocks):
+        group = [blocks[i]]
+        while len(group) < per_batch and i + len(group) < len(blocks) and \
+                (blocks[i + len(group)][2] - blocks[i + len(group)][0]) == (group[0][2] - group[0][0]):
+            group.append(blocks[i + len(group)])
+        i += len(group)
+        batches_.append(group)
+    return batches_
 
 
 def fairseq_token_stream(data, split):
@@ -604,15 +721,10 @@ def main(args, tables=None, model=None):
     reinit = bool(getattr(args, "reinit_nfeat", False))
     sweep = parse_sweep(args)
     args.sweep = sweep                                                                     # (read by the scorer)
-    break_mode = getattr(args, "sample_break_mode", None) or "none"
-    if break_mode not in token_blocks.BREAK_MODES:
-        raise ValueError("Invalid break_mode: " + str(break_mode))                         # token_block_utils_fast.pyx:102
+    break_mode = check_break_mode(args)
     ragged = break_mode != "none"                                                          # blocks of unequal length, packed
     if ragged and getattr(args, "graph_capture", False):
         raise ValueError(f"--graph-capture replays one graph per batch shape; the batches of --sample-break-mode {break_mode} all differ")
-    if ragged and args.save_knnlm_dstore and break_mode == "complete_doc":
-        raise ValueError("--save-knnlm-dstore writes one row per token of the split in corpus order; --sample-break-mode complete_doc "
-                         "drops the document separators")
     if args.context_window > 0:
         # LMContextWindowDataset (fairseq/data/lm_context_window_dataset.py) prepends context tokens and scores only the
         # new ones; shrinking the block without the prefix would silently give another ppl
@@ -735,39 +847,17 @@ def main(args, tables=None, model=None):
     # (`--knn-keytype`, here the HGT output "gcn_feat") and the target tokens, written as the split's datastore
     save = None
     if args.save_knnlm_dstore:
-        dstore_size = int(tabs["n_tok"])                                   # dataset.sizes.sum() (:104)
         # key dimension = what the scorer hands back for --knn-keytype: the HGT output ("gcn_feat", out_dim of the output
         # adapter if there is one) or the precomputed features (the inner_states[-1] fallback, sequence_scorer.py:105)
         hd = getattr(model, "hgt_decoder", None)
         dim = int(getattr(hd, "out_dim", tabs["d"])) if (args.knn_keytype == "gcn_feat" and not getattr(model, "short_cut", False)) \
             else int(tabs["d"])
-        fp16 = bool(args.dstore_fp16)
-        suffix = "" if not args.knn_keytype else f"-{args.knn_keytype}"
-        save_dir = os.path.join(args.dstore_mmap, f"{args.gen_subset}_dstore{suffix}")
-        os.makedirs(save_dir, exist_ok=True)
         vocab = tabs.get("vocab") or int(tabs["targets"].max().item()) + 1
-        info = {"dstore_size": dstore_size, "hidden_size": dim, "vocab_size": int(vocab), "dstore_fp16": fp16, "val_size": 1}
-        logger.info(f"keytype being saved: {args.knn_keytype}")
-        logger.info(f"dstore info: {info}")
-        json.dump(info, open(os.path.join(save_dir, "info.json"), "w"), indent=4, sort_keys=True)
-        save = {"dir": save_dir, "idx": 0, "size": dstore_size, "dim": dim,
-                "keys": np.memmap(os.path.join(save_dir, "keys.npy"), dtype=np.float16 if fp16 else np.float32, mode="w+",
-                                  shape=(dstore_size, dim)),
-                "vals": np.memmap(os.path.join(save_dir, "vals.npy"), dtype=np.int16 if fp16 and vocab < 2 ** 15 else np.int32,
-                                  mode="w+", shape=(dstore_size, 1))}
+        save = DstoreWriter(args.dstore_mmap, args.gen_subset, args.knn_keytype, int(tabs["n_tok"]), dim, vocab,   # (size: dataset.sizes.sum(), :104)
+                            bool(args.dstore_fp16))
     # --output-word-probs / --output-word-stats / --output-knn-recall / --remove-bpe (fairseq_cli/eval_lm.py:146-160,246-313,333-336)
     want_words = args.output_word_probs or args.output_word_stats
-    symbols, bpe_toks, bpe_len, word_stats = None, None, 0, dict()
-    if want_words or args.remove_bpe is not None:
-        symbols = load_symbols(args.data)
-    if args.remove_bpe is not None:
-        if args.remove_bpe == "sentencepiece":
-            raise NotImplementedError                                        # as the reference (:148-149)
-        if symbols is None:
-            raise ValueError("--remove-bpe needs the data directory's dict.txt (the continuation marker lives in the symbols)")
-        bpe_cont = args.remove_bpe.rstrip()
-        bpe_toks = {i for i in range(len(symbols)) if symbols[i].endswith(bpe_cont)}
-        bpe_len = len(bpe_cont)
+    (symbols, bpe_toks, bpe_len), word_stats = word_output_setup(args), dict()
     if args.output_knn_recall and not args.knnlm:
         raise ValueError("--output-knn-recall needs --knnlm (the scorer returns no recall otherwise)")
     acc = torch.zeros(1, device=device, dtype=torch.float64)
@@ -775,14 +865,7 @@ def main(args, tables=None, model=None):
     count, ntok = 0, 0
     timers = []             # gen_timer (eval_lm.py:214-219) as HIP event pairs on the stream: no per-batch host sync
     # the batches of this rank: runs of equally long blocks, up to per_batch of them
-    batches_, i = [], 0
-    while i < len(blocks) and not ragged:
-        group = [blocks[i]]
-        while len(group) < per_batch and i + len(group) < len(blocks) and \
-                (blocks[i + len(group)][2] - blocks[i + len(group)][0]) == (group[0][2] - group[0][0]):
-            group.append(blocks[i + len(group)])
-        i += len(group)
-        batches_.append(group)
+    batches_ = [] if ragged else equal_length_batches(blocks, per_batch)
     rtab = None
     if ragged and blocks:
         # ragged modes: consecutive blocks in corpus order up to the token budget the equal-length path would have packed (a block
@@ -790,14 +873,7 @@ def main(args, tables=None, model=None):
         # kernel's tile lists of every batch (ragged.BlockTable), where each block's rows start in the split, how many of them are
         # context, where its scored tokens start among the scored ones -- a batch is views into them, nothing per batch over PCIe
         from .ragged import BlockTable, packed_rows
-        budget, bounds, b0, tok = per_batch * T, [], 0, 0
-        for j, blk in enumerate(blocks):
-            n = blk[2] - blk[0]
-            if j > b0 and (tok + n > budget or (args.max_sentences and j - b0 >= args.max_sentences)):
-                bounds.append((b0, j))
-                b0, tok = j, 0
-            tok += n
-        bounds.append((b0, len(blocks)))
+        bounds = budget_batches([blk[2] - blk[0] for blk in blocks], per_batch * T, args.max_sentences)
         batches_ = [blocks[a:b] for a, b in bounds]
         barr = np.asarray([blk[:3] for blk in blocks], dtype=np.int64)
         rtab = {"table": BlockTable(barr[:, 2] - barr[:, 0], device, batches=bounds), "bounds": bounds,
@@ -846,17 +922,8 @@ def main(args, tables=None, model=None):
         state["ntok"] += sample["ntokens"]
         if save is not None:                                     # one device -> host copy per batch (this run is a writer anyway)
             kd = hypos[0][0]["dstore_keys"].shape[-1]
-            if kd != save["dim"]:
-                raise ValueError(f"--save-knnlm-dstore: the scorer returned {kd}-dimensional keys, the datastore was opened for {save['dim']}")
-            keys = torch.cat([h[0]["dstore_keys"].reshape(-1, kd) for h in hypos])
-            toks = torch.cat([h[0]["tokens"].reshape(-1) for h in hypos])
-            n_new = min(keys.shape[0], save["size"] - save["idx"])
-            if n_new < keys.shape[0]:
-                logger.warning("exceed offset at sample " + str(int(sample["id"][0])))          # :227-230
-            sl = slice(save["idx"], save["idx"] + n_new)
-            save["keys"][sl] = keys[:n_new].to(torch.float16 if save["keys"].dtype == np.float16 else torch.float32).cpu().numpy()
-            save["vals"][sl, 0] = toks[:n_new].cpu().numpy().astype(save["vals"].dtype)
-            save["idx"] += n_new
+            save.append(torch.cat([h[0]["dstore_keys"].reshape(-1, kd) for h in hypos]), torch.cat([h[0]["tokens"].reshape(-1) for h in hypos]),
+                        sample["id"][0])
         scored = handle.get("scored_pos") if handle is not None else None                   # ragged batch: the scorer's flat view and sums
         pos = scored.float().reshape(-1) if scored is not None else \
             torch.cat([h[0]["positional_scores"].float().reshape(-1) for h in hypos])     # one launch per batch
@@ -962,9 +1029,7 @@ def main(args, tables=None, model=None):
     score_sum = acc.item()                                                                  # the only host sync
     sweep_sums = sweep_accs[id(acc)].tolist() if sweep else []
     if save is not None:
-        save["keys"].flush()
-        save["vals"].flush()
-        logger.info(f"Saved {save['idx']} data to {save['dir']}")                           # :322-323
+        save.close()
     wall = time.perf_counter() - wall0                                                      # the loop as a whole ("wps", :316)
     gen_time = sum(a.elapsed_time(b) for a, b in timers) / 1e3
     if n_streams > 1:
@@ -986,15 +1051,9 @@ def main(args, tables=None, model=None):
         dist.all_reduce(tm, op=dist.ReduceOp.MAX)
         score_sum, count, ntok = t[0].item(), int(t[1].item()), int(t[2].item())
         gen_time, wall = tm[0].item(), tm[1].item()
-    avg_nll_loss = -score_sum / count / math.log(2)
-    line1 = "Evaluated {} tokens in {:.1f}s ({:.2f} tokens/s)".format(ntok, gen_time, ntok / max(gen_time, 1e-9))
-    line2 = "Loss (base 2): {:.4f}, Perplexity: {:.2f}".format(avg_nll_loss, 2 ** avg_nll_loss)
-    if rank == 0 or not (dist.is_available() and dist.is_initialized()):
-        logger.info(line1)
-        logger.info(line2)
-        print(line1)
-        print(line2)
-    sweep_rows = report_sweep(sweep, sweep_sums, count, quiet=rank != 0 and dist.is_available() and dist.is_initialized()) if sweep else None
+    quiet = rank != 0 and dist.is_available() and dist.is_initialized()
+    ppl = report_result(score_sum, count, ntok, gen_time, quiet)
+    sweep_rows = report_sweep(sweep, sweep_sums, count, quiet) if sweep else None
     # the same with the reference's float32 accumulation (fairseq_cli/eval_lm.py:273-274): logged, not printed --
     # the two lines above are the reference's output.  Per rank in a multi-process run (the reference has one accumulator).
     if count_rank:
@@ -1008,17 +1067,13 @@ def main(args, tables=None, model=None):
     link_bytes = getattr(fetcher, "link_bytes", None)
     if own_group:
         dist.destroy_process_group()
-    res = {"score_sum": score_sum, "count": count, "ppl": 2 ** avg_nll_loss, "tokens": ntok, "seconds": gen_time,
+    res = {"score_sum": score_sum, "count": count, "ppl": ppl, "tokens": ntok, "seconds": gen_time,
             "wall_seconds": wall, "word_stats": word_stats if args.output_word_stats else None,
             "score_sum_f32_order": float(score_sum_f32), "rank": rank, "world": world, "store": store_mode, "rank_score_sum": rank_score_sum, "rank_tokens": rank_tokens,
             "xgmi_bytes": link_bytes, "precision": precision, "head": head}
     if sweep:
         res["sweep"] = sweep_rows
-    if getattr(args, "result_json", None):
-        js = {k_: v for k_, v in res.items() if k_ != "word_stats"}
-        for path in ([args.result_json + f".rank{rank}"] if world > 1 else []) + ([args.result_json] if rank == 0 else []):
-            with open(path, "w") as fh:
-                json.dump(js, fh)
+    write_result_json(getattr(args, "result_json", None), res, rank, world)
     return res
 
 
