@@ -119,6 +119,19 @@ int causal_attn_fused(const float* Q, const float* K, const float* V, int64_t ld
 bool causal_attn_varlen_ok(int dk);
 int causal_attn_varlen(const float* Q, const float* K, const float* V, int64_t ld, float* out, int64_t ldo, const gnnlm_ragged_t& rg,
                        int H, int dk, int max_ctx, hipStream_t stream, bool accumulate = false);
+// one new row per sequence against a K/V cache (decode_attn.hip): chunks of GNNLM_DECODE_CHUNK keys per wave, combined in order
+bool decode_attn_ok(int dk);
+int check_kv_cache(const gnnlm_kv_cache_t& c);
+size_t decode_attn_workspace_bytes(int B, int H, int dk, int max_len);
+int decode_attn(const gnnlm_decode_attn_t& d, hipStream_t stream);
+// K' | V' of the packed q | k | v rows [n_tok, ld_src] -> cache rows [0, min(len_b, max_rows)) of sequence b = block b of `layer`
+int kv_cache_fill(const float* qkv, int64_t ld_src, const gnnlm_kv_cache_t& c, int layer, const gnnlm_ragged_t& rg, int max_rows,
+                  hipStream_t stream);
+// len[b] = min(block_off[b + 1] - block_off[b], max_rows);  len[b] += 1 for rows that are not done and hold 0 <= len[b] < bound
+int kv_len_set(const gnnlm_kv_cache_t& c, const int32_t* block_off, int max_rows, hipStream_t stream);
+int kv_len_advance(const gnnlm_kv_cache_t& c, int bound, hipStream_t stream);
+// the next token of every row from its sorted top-N (sample.hip)
+int sample_topk(const gnnlm_sample_topk_t& d, hipStream_t stream);
 // host: the (block, query tile) table of block_off [n_blocks + 1], heaviest tiles first; tiles == nullptr only counts.  -1: an empty block
 int64_t ragged_tiles(const int32_t* block_off, int n_blocks, int32_t* tiles);
 

@@ -60,6 +60,50 @@ __global__ __launch_bounds__(256) void lm_embed_kernel(EmbedParams p) {
     }
 }
 
+struct StepEmbedParams {
+    const int64_t* tokens;
+    const float* E; int64_t ld_e; int n_vocab, d4;
+    const float* P; int64_t ld_p, p_rows; int pad_idx;
+    float scale;
+    float* out; int64_t ldo;
+    const int32_t* len; int B, cap;
+    int32_t* n_bad;
+};
+
+// lm_embed_kernel for a decoding step: one wave per sequence, the position is pad_idx + 1 + len[b], read here.  The same two
+// roundings, the same zero row and count for an id outside the vocabulary -- and for a len[b] the cache cannot hold.
+__global__ __launch_bounds__(256) void lm_embed_step_kernel(StepEmbedParams p) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= p.B) return;
+    float4* o = reinterpret_cast<float4*>(p.out + b * p.ldo);
+    const int64_t tok = p.tokens[b];
+    const int len = p.len[b];
+    bool ok = tok >= 0 && tok < p.n_vocab && len >= 0 && len < p.cap;
+    const float4* pr = nullptr;
+    if (p.P) {
+        const int64_t pos = (int64_t)p.pad_idx + 1 + len;
+        ok = ok && pos < p.p_rows;                          // (the host refused a max_len beyond the table: memory safety only)
+        pr = reinterpret_cast<const float4*>(p.P + (ok ? pos : 0) * p.ld_p);
+    }
+    if (!ok) {
+        for (int e = lane; e < p.d4; e += 64) o[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (lane == 0 && p.n_bad) atomicAdd(p.n_bad, 1);
+        return;
+    }
+    const float4* er = reinterpret_cast<const float4*>(p.E + tok * p.ld_e);
+    const float s = p.scale;
+    for (int e = lane; e < p.d4; e += 64) {
+        const float4 v = er[e];
+        float4 x = make_float4(__fmul_rn(s, v.x), __fmul_rn(s, v.y), __fmul_rn(s, v.z), __fmul_rn(s, v.w));
+        if (pr) {
+            const float4 q = pr[e];
+            x = make_float4(__fadd_rn(x.x, q.x), __fadd_rn(x.y, q.y), __fadd_rn(x.z, q.z), __fadd_rn(x.w, q.w));
+        }
+        o[e] = x;
+    }
+}
+
 // v < 0 ? 0 : v keeps a NaN (both comparisons false), as torch.relu; fmaxf would drop it
 __device__ __forceinline__ float relu1(float v) { return v < 0.f ? 0.f : v; }
 __global__ __launch_bounds__(256) void relu4_kernel(float4* x, int64_t n4) {
@@ -160,9 +204,22 @@ int linear(const float* A, const float* W, const float* bias, float* C, int64_t 
     return gemm_nt(g, s);
 }
 
-int tlm_forward(const gnnlm_tlm_t& m, const gnnlm_tlm_io_t& io, void* ws, size_t ws_bytes, hipStream_t s) {
+int check_tlm_cache(const gnnlm_tlm_t& m, const gnnlm_kv_cache_t& c) {
+    TRY(check_kv_cache(c));
+    GNNLM_REQUIRE(c.d == m.d && c.L == m.L, "transformer_lm: the cache's d / L differ from the model's");
+    return OK;
+}
+
+// cache != nullptr (gnnlm_transformer_lm_prefill): block b is sequence b, its K' / V' rows are copied into the cache after each
+// layer's q|k|v GEMM and len is set at the end; the launches of the forward itself are the same either way
+int tlm_forward(const gnnlm_tlm_t& m, const gnnlm_tlm_io_t& io, void* ws, size_t ws_bytes, hipStream_t s, const gnnlm_kv_cache_t* cache = nullptr) {
     TRY(check_tlm(m));
     const gnnlm_ragged_t& rg = io.blocks;
+    if (cache) {
+        TRY(check_tlm_cache(m, *cache));
+        GNNLM_REQUIRE(rg.n_blocks == cache->B, "transformer_lm_prefill: n_blocks != the cache's B");
+        GNNLM_REQUIRE(io.max_len >= 0 && io.max_len <= cache->cap, "transformer_lm_prefill: a block is longer than the cache (max_len > cap)");
+    }
     const int64_t n = rg.n_tok;
     const int d = m.d, dk = m.d / m.H;
     const float eps = m.ln_eps == 0.f ? 1e-5f : m.ln_eps;
@@ -188,6 +245,7 @@ int tlm_forward(const gnnlm_tlm_t& m, const gnnlm_tlm_io_t& io, void* ws, size_t
         // self-attention block: x += out_proj(attn(LN(x)))
         TRY(layernorm(b.x, d, w.ln1_g, w.ln1_b, b.h, d, n, d, eps, nullptr, s));
         TRY(linear(b.h, w.wqkv, w.bqkv, b.wide, n, 3 * d, d, nullptr, s));
+        if (cache) TRY(kv_cache_fill(b.wide, 3 * (int64_t)d, *cache, l, rg, (int)io.max_len, s));
         TRY(causal_attn_varlen(b.wide, b.wide + d, b.wide + 2 * d, 3 * (int64_t)d, b.a, d, rg, m.H, dk, 0, s));
         TRY(linear(b.a, w.wo, w.bo, b.x, n, d, d, b.x, s));
         // feed-forward block: x += fc2(act(fc1(LN(x))))
@@ -203,6 +261,75 @@ int tlm_forward(const gnnlm_tlm_t& m, const gnnlm_tlm_io_t& io, void* ws, size_t
             else if (dst != io.out) GNNLM_HIP(hipMemcpyAsync(io.out, dst, (size_t)n * d * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
     }
+    if (cache) TRY(kv_len_set(*cache, rg.block_off, (int)io.max_len, s));
+    return OK;
+}
+
+size_t carve_step(const gnnlm_tlm_t& m, int B, int max_len, char* base, TlmBufs& b, float** attn_ws, size_t* attn_bytes) {
+    size_t off = carve_tlm(m, B, base, b) - 256;
+    off = (off + 255) & ~size_t(255);
+    const size_t n = decode_attn_workspace_bytes(B, m.H, m.H > 0 ? m.d / m.H : 0, max_len);
+    if (attn_ws) *attn_ws = base ? reinterpret_cast<float*>(base + off) : nullptr;
+    if (attn_bytes) *attn_bytes = n;
+    return off + n + 256;
+}
+
+int tlm_step(const gnnlm_tlm_t& m, const gnnlm_kv_cache_t& c, const gnnlm_tlm_step_io_t& io, void* ws, size_t ws_bytes, hipStream_t s) {
+    TRY(check_tlm(m));
+    TRY(check_tlm_cache(m, c));
+    const int B = c.B, d = m.d, dk = m.d / m.H;
+    const float eps = m.ln_eps == 0.f ? 1e-5f : m.ln_eps;
+    GNNLM_REQUIRE(io.max_len >= 1 && io.max_len <= c.cap, "transformer_lm_step: max_len outside [1, cap] (the cache is full)");
+    GNNLM_REQUIRE(m.E && m.ld_e >= d && m.ld_e % 4 == 0 && (uintptr_t)m.E % 16 == 0 && m.n_vocab > 0, "transformer_lm_step: E must be [n_vocab, d], 16-byte aligned, ld_e % 4 == 0");
+    if (m.P) {
+        GNNLM_REQUIRE(m.ld_p >= d && m.ld_p % 4 == 0 && (uintptr_t)m.P % 16 == 0 && m.pad_idx >= 0, "transformer_lm_step: P must be [p_rows, d], 16-byte aligned, ld_p % 4 == 0");
+        GNNLM_REQUIRE((int64_t)m.pad_idx + 1 + io.max_len <= m.p_rows,
+                      "transformer_lm_step: the position table does not hold the next position (pad_idx + 1 + max_len > p_rows)");
+    }
+    if (B == 0) return OK;
+    GNNLM_REQUIRE(io.tokens && io.out, "transformer_lm_step: tokens / out missing");
+    GNNLM_REQUIRE(((uintptr_t)io.out | (uintptr_t)io.last_inner | (uintptr_t)io.last_ffn_input) % 16 == 0, "transformer_lm_step: outputs must be 16-byte aligned");
+    TlmBufs b;
+    float* attn_ws = nullptr;
+    size_t attn_bytes = 0;
+    GNNLM_REQUIRE(ws && (uintptr_t)ws % 16 == 0 && carve_step(m, B, (int)io.max_len, nullptr, b, nullptr, nullptr) <= ws_bytes,
+                  "transformer_lm_step: workspace missing, misaligned or too small");
+    carve_step(m, B, (int)io.max_len, reinterpret_cast<char*>(ws), b, &attn_ws, &attn_bytes);
+    GemmPrecisionScope prec_scope(m.precision);
+
+    {
+        StepEmbedParams p{io.tokens, m.E, m.ld_e, m.n_vocab, d / 4, m.P, m.ld_p, m.p_rows, m.pad_idx, m.scale, b.x, d, c.len, B, (int)io.max_len, io.n_bad};
+        ProfScope prof(K_MISC, s, (m.P ? 2.0 : 1.0) * B * d, (m.P ? 12.0 : 8.0) * B * d + 12.0 * B);
+        hipLaunchKernelGGL(lm_embed_step_kernel, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, s, p);
+        GNNLM_LAUNCH_CHECK();
+    }
+    if (m.ln_emb_g) TRY(layernorm(b.x, d, m.ln_emb_g, m.ln_emb_b, b.x, d, B, d, eps, nullptr, s));
+    gnnlm_decode_attn_t a{};
+    a.q = b.wide; a.k_new = b.wide + d; a.v_new = b.wide + 2 * d; a.ld = 3 * (int64_t)d;
+    a.out = b.a; a.ldo = d;
+    a.cache = c; a.H = m.H; a.dk = dk; a.max_len = (int32_t)io.max_len;
+    a.workspace = attn_ws; a.workspace_bytes = attn_bytes;
+    for (int l = 0; l < m.L; ++l) {
+        const gnnlm_tlm_layer_t& w = m.layers[l];
+        const bool last = l == m.L - 1;
+        TRY(layernorm(b.x, d, w.ln1_g, w.ln1_b, b.h, d, B, d, eps, nullptr, s));
+        TRY(linear(b.h, w.wqkv, w.bqkv, b.wide, B, 3 * d, d, nullptr, s));
+        a.layer = l;
+        if (l > 0) a.cache.n_bad = nullptr;                 // a row out of range is counted once per step, not once per layer
+        TRY(decode_attn(a, s));
+        TRY(linear(b.a, w.wo, w.bo, b.x, B, d, d, b.x, s));
+        float* h2 = last && io.last_ffn_input ? io.last_ffn_input : b.h;
+        TRY(layernorm(b.x, d, w.ln2_g, w.ln2_b, h2, d, B, d, eps, nullptr, s));
+        TRY(linear(h2, w.w1, w.b1, b.wide, B, m.ffn, d, nullptr, s));
+        TRY(m.act == 0 ? relu(b.wide, (int64_t)B * m.ffn, s) : gelu(b.wide, (int64_t)B * m.ffn, s));
+        float* dst = !last ? b.x : (io.last_inner ? io.last_inner : (m.ln_out_g ? b.x : io.out));
+        TRY(linear(b.wide, w.w2, w.b2, dst, B, d, m.ffn, b.x, s));
+        if (last) {
+            if (m.ln_out_g) TRY(layernorm(dst, d, m.ln_out_g, m.ln_out_b, io.out, d, B, d, eps, nullptr, s));
+            else if (dst != io.out) GNNLM_HIP(hipMemcpyAsync(io.out, dst, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+    }
+    TRY(kv_len_advance(c, (int)io.max_len, s));
     return OK;
 }
 
@@ -252,6 +379,25 @@ int gnnlm_transformer_lm_forward(const gnnlm_tlm_t* m, const gnnlm_tlm_io_t* io,
     GNNLM_DESC(m);
     GNNLM_DESC(io);
     return tlm_forward(*m, *io, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int gnnlm_transformer_lm_prefill(const gnnlm_tlm_t* m, const gnnlm_tlm_io_t* io, const gnnlm_kv_cache_t* cache, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    GNNLM_DESC(m);
+    GNNLM_DESC(io);
+    GNNLM_DESC(cache);
+    return tlm_forward(*m, *io, workspace, workspace_bytes, (hipStream_t)stream, cache);
+}
+size_t gnnlm_transformer_lm_step_workspace_bytes(const gnnlm_tlm_t* m, const gnnlm_kv_cache_t* c, const gnnlm_tlm_step_io_t* io) {
+    if (!m || !c || !io || m->d <= 0 || m->ffn <= 0 || m->H <= 0 || c->B < 0 || io->max_len < 0 || io->max_len > c->cap) return 0;
+    TlmBufs b;
+    return carve_step(*m, c->B, (int)io->max_len, nullptr, b, nullptr, nullptr);
+}
+int gnnlm_transformer_lm_step(const gnnlm_tlm_t* m, const gnnlm_kv_cache_t* c, const gnnlm_tlm_step_io_t* io, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    GNNLM_DESC(m);
+    GNNLM_DESC(c);
+    GNNLM_DESC(io);
+    return tlm_step(*m, *c, *io, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

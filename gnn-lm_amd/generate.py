@@ -1,0 +1,281 @@
+"""Generate from the base transformer LM: K/V-cache decoding, greedy or top-k sampling, optionally mixed with kNN.
+
+    python -m gnnlm_amd.generate DATA --path base.pt --gen-subset test --n-prompts 8 --prompt-len 32 --max-len-b 64 \\
+        [--sampling --sampling-topk 10] [--temperature 0.8] [--unkpen X] [--seed 1] [--fp16] \\
+        [--knnlm --k 1024 --lmbda 0.25 --knn-temperature 1 --probe 32 --dstore-dir D --index-file F --knn-sim-func do_not_recomp_ip]
+
+Mirror of ``SequenceGenerator`` (fairseq/sequence_generator.py) with ``search.Sampling`` (fairseq/search.py:199-270) at beam 1 for
+one decoder-only model.  The loop:
+
+  prefill   ``TransformerLM.prefill`` over the packed prompts fills the K/V cache; the last row of every prompt goes on.
+  head      ``head.log_probs`` of the rows divided by the temperature -- sequence_generator.py:572-573 divides ``decoder_out[0]``,
+            which is the features under the adaptive softmax and the logits (rows and bias) under the plain output layer.
+  kNN       optional: the rows' ``extra[knn_keytype]`` (else ``inner_states[-1]``) searched through the ``KNNModel``'s index, mixed by
+            ``ops.knn_mix_dense`` exactly as ``predict.predict_rows`` feeds it.
+  rules     ``lprobs[:, pad] = -inf`` and ``lprobs[:, unk] -= unk_penalty`` (sequence_generator.py:279-280).
+  pick      ``ops.topk_merge`` with k = ``sampling_topk`` (1 when greedy), then ``ops.sample_topk`` with one uniform number per row from
+            a seeded device generator.
+  step      ``TransformerLM.step`` appends the picks; back to head.
+
+Without kNN the loop reads nothing back per token: ``done`` is looked at every 16 steps and at the end.
+
+Refused by name, never approximated: ``--beam`` > 1, ``--sampling-topp``, ``--sampling`` without ``--sampling-topk`` (pure sampling over the
+vocabulary), ``--sampling-topk`` > 2048, ``--no-repeat-ngram-size``, ``--min-len`` != 1, ``--graph``, ``--sweep-*``, more than one process.
+"""
+import argparse
+import logging
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import ops
+from .predict import MAX_TOPK, head_vocab
+
+logger = logging.getLogger("gnnlm_amd.generate")
+
+PAD, EOS, UNK = 1, 2, 3         # fairseq Dictionary
+DONE_EVERY = 16                 # steps between two looks at `done`
+
+
+class Generator:
+    def __init__(self, lm, knn=None, knn_keytype=None, k=0, lmbda=0.0, knn_temperature=1.0):
+        """lm: a ``TransformerLM`` with a head.  knn: a ``KNNModel`` (or anything with its ``interpolate_dense``) or None;
+        ``lmbda`` / ``knn_temperature`` / ``k`` are the mixture's settings (``k`` 0: the model's own)."""
+        if lm.head is None:
+            raise ValueError("Generator: this TransformerLM was built without an output layer")
+        self.lm, self.knn, self.knn_keytype = lm, knn, knn_keytype or None
+        self.k, self.lmbda, self.knn_temperature = int(k), float(lmbda), float(knn_temperature)
+        self.vocab = head_vocab(lm.head)
+        self._cool = {}
+
+    def _head(self, temperature):
+        """The head that gives log_softmax(decoder_out / temperature) of rows ALREADY divided by it: itself, or -- the plain output
+        layer with a bias -- a twin whose bias is divided too."""
+        head = self.lm.head
+        if temperature == 1.0 or getattr(head, "bias", None) is None:
+            return head
+        if temperature not in self._cool:
+            twin = type(head)(head.weight, head.bias / temperature)
+            self._cool = {temperature: twin}
+        twin = self._cool[temperature]
+        twin.gemm_precision = head.gemm_precision
+        return twin
+
+    def next_log_probs(self, x, extra, temperature=1.0, unk_penalty=0.0):
+        """Rows ``x`` [B, d] (and the ``extra`` they came with) -> the log-probs the pick is made from, [B, V] f32."""
+        rows = x if temperature == 1.0 else x / temperature
+        lp = self._head(temperature).log_probs(rows)
+        if self.knn is not None and self.lmbda > 0.0:
+            q = extra.get(self.knn_keytype) if self.knn_keytype else None
+            if q is None:
+                q = extra["inner_states"][-1]
+            lp = self.knn.interpolate_dense(q.contiguous(), lp, self.knn_temperature, self.lmbda, k=self.k)
+        lp[:, PAD] = float("-inf")
+        if unk_penalty:
+            lp[:, UNK] -= unk_penalty
+        return lp
+
+    @staticmethod
+    def check(max_new, sampling, sampling_topk, temperature, V):
+        if max_new < 1:
+            raise ValueError("max_new (--max-len-b) must be at least 1")
+        if not temperature > 0:
+            raise ValueError("--temperature must be greater than 0")
+        if sampling and sampling_topk < 1:
+            raise ValueError("--sampling without --sampling-topk (pure sampling over the vocabulary) is not built")
+        if sampling and sampling_topk > MAX_TOPK:
+            raise ValueError(f"--sampling-topk {sampling_topk}: at most {MAX_TOPK} (gnnlm_topk_merge's k)")
+        return min(sampling_topk, V) if sampling else 1
+
+    def generate(self, prompts, max_new, sampling=False, sampling_topk=-1, temperature=1.0, unk_penalty=0.0, seed=None):
+        """prompts: a list of non-empty lists of token ids, fed as they are -> ``(tokens int64 [B, max_new], logp f32 [B, max_new],
+        lengths int64 [B])`` on the device: row b's continuation is ``tokens[b, :lengths[b]]`` (its ``eos`` included when it came), ``pad``
+        behind it; ``logp`` the picks' own log-probabilities."""
+        lm, dev = self.lm, self.lm.device
+        k = self.check(max_new, sampling, sampling_topk, float(temperature), self.vocab)
+        if not prompts or any(len(p) < 1 for p in prompts):
+            raise ValueError("generate: every prompt needs at least one token")
+        B, lens = len(prompts), np.asarray([len(p) for p in prompts], dtype=np.int64)
+        off = np.concatenate([[0], np.cumsum(lens)])
+        tokens = torch.tensor([t for p in prompts for t in p], dtype=torch.int64, device=dev)
+        cache = lm.new_cache(B, int(lens.max()) + max_new - 1)
+        want_ffn = self.knn is not None and self.knn_keytype == "last_ffn_input"
+        x, extra = lm.prefill(tokens, torch.from_numpy(off.astype(np.int32)), cache, want_ffn_input=want_ffn, check=False)
+        last = torch.from_numpy(off[1:] - 1).to(dev)
+        x = x[last]
+        extra = {k_: ([v[0][last]] if isinstance(v, list) else v[last]) for k_, v in extra.items()}
+        out = torch.full((B, max_new), PAD, dtype=torch.int64, device=dev)
+        out_lp = torch.zeros(B, max_new, dtype=torch.float32, device=dev)
+        best_val = torch.empty(B, k, dtype=torch.float32, device=dev)
+        best_id = torch.empty(B, k, dtype=torch.int64, device=dev)
+        nxt = torch.empty(B, dtype=torch.int64, device=dev)
+        nxt_lp = torch.zeros(B, dtype=torch.float32, device=dev)
+        gen = None
+        if sampling:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed) if seed is not None else 1)
+        n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        for t in range(max_new):
+            lp = self.next_log_probs(x, extra, float(temperature), float(unk_penalty))
+            ops.topk_merge(lp, best_val, best_id, init=True)
+            u = torch.rand(B, generator=gen, device=dev, dtype=torch.float32) if sampling else None
+            nxt_lp.zero_()
+            ops.sample_topk(best_val, best_id, u=u, pad=PAD, eos=EOS, done=cache.done, n_bad=n_bad, out=nxt, out_logp=nxt_lp)
+            out[:, t] = nxt
+            out_lp[:, t] = nxt_lp
+            if t == max_new - 1 or ((t + 1) % DONE_EVERY == 0 and bool(cache.done.all())):
+                break
+            x, extra = lm.step(nxt, cache, want_ffn_input=want_ffn)
+        lm.check_tokens()
+        if int(n_bad.item()) or int(cache.n_bad.item()):
+            raise RuntimeError("generate: a row had nothing to pick from (non-finite log-probabilities) or left the cache's range")
+        is_eos = out == EOS
+        first = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full((B,), t + 1, device=dev))
+        return out, out_lp, first.to(torch.int64)
+
+
+# ------------------------------------------------------------------------------------------------ the driver
+def get_parser():
+    p = argparse.ArgumentParser(prog="python -m gnnlm_amd.generate", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("data", help="the data directory (DATA/<split>.bin/.idx, optionally dict.txt)")
+    p.add_argument("--path", required=True, help="the --arch transformer_lm* checkpoint")
+    p.add_argument("--model-overrides", default="{}")
+    p.add_argument("--device", default="cuda:0")
+    p.add_argument("--gen-subset", default="test")
+    p.add_argument("--n-prompts", type=int, default=8)
+    p.add_argument("--prompt-len", type=int, default=32)
+    p.add_argument("--prompt-ids", default=None, help="one prompt as comma-separated token ids (instead of cutting prompts from the split)")
+    p.add_argument("--max-len-b", type=int, default=64, help="tokens to generate per prompt (fairseq: max_len = a * src_len + b with a = 0)")
+    p.add_argument("--sampling", action="store_true")
+    p.add_argument("--sampling-topk", type=int, default=-1)
+    p.add_argument("--sampling-topp", type=float, default=-1.0, help="not built: refused")
+    p.add_argument("--temperature", type=float, default=1.0,
+                   help="the GENERATION temperature (fairseq/options.py:548): the decoder output is divided by it.  The kNN temperature, "
+                        "which eval_lm calls --temperature (options.py:496), is --knn-temperature here")
+    p.add_argument("--knn-temperature", type=float, default=1.0, help="the temperature of the kNN distribution (eval_lm's --temperature)")
+    p.add_argument("--unkpen", type=float, default=0.0)
+    p.add_argument("--seed", type=int, default=1)
+    p.add_argument("--fp16", action="store_true")
+    p.add_argument("--beam", type=int, default=1, help="beam search is not built: anything but 1 is refused")
+    p.add_argument("--no-repeat-ngram-size", type=int, default=0, help="not built: refused")
+    p.add_argument("--min-len", type=int, default=1, help="not built: anything but 1 is refused")
+    p.add_argument("--graph", action="store_true", help="not built (HGTLayer.infer): refused")
+    for name in ("--sweep-lmbda", "--sweep-temperature", "--sweep-k"):
+        p.add_argument(name, default=None, help="belongs to eval_lm: refused")
+    p.add_argument("--knnlm", action="store_true")
+    p.add_argument("--k", type=int, default=1024)
+    p.add_argument("--lmbda", type=float, default=0.25, help="weight of the kNN distribution with --knnlm; 0 is refused (it would load the "
+                   "datastore and generate from the base LM alone: drop --knnlm for that)")
+    p.add_argument("--probe", type=int, default=32)
+    p.add_argument("--dstore-dir", default=None)
+    p.add_argument("--index-file", default=None)
+    p.add_argument("--knn-sim-func", default="do_not_recomp_ip")
+    p.add_argument("--knn-keytype", default=None)
+    p.add_argument("--out", default=None, help="write tokens / logp / lengths / prompts to this .npz")
+    return p
+
+
+def check_args(args):
+    """Host only, before any device work: what this build does not compute is refused with the flag's name."""
+    if args.beam != 1:
+        raise ValueError(f"--beam {args.beam}: beam search is not built (only --beam 1)")
+    if args.sampling_topp > 0:
+        raise ValueError("--sampling-topp is not built")
+    if args.no_repeat_ngram_size:
+        raise ValueError("--no-repeat-ngram-size is not built")
+    if args.min_len != 1:
+        raise ValueError(f"--min-len {args.min_len} is not built (only --min-len 1)")
+    if args.graph:
+        raise ValueError("--graph: generation through the GNN (HGTLayer.infer) is not built")
+    for name in ("sweep_lmbda", "sweep_temperature", "sweep_k"):
+        if getattr(args, name) is not None:
+            raise ValueError(f"--{name.replace('_', '-')} belongs to eval_lm: generation runs one setting")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise NotImplementedError("generation runs in one process (WORLD_SIZE > 1 is not built)")
+    Generator.check(args.max_len_b, args.sampling, args.sampling_topk, args.temperature, MAX_TOPK)
+    if args.knnlm and getattr(args, "knn_model", None) is None and not (args.dstore_dir and args.index_file):
+        raise ValueError("--knnlm needs --dstore-dir and --index-file")
+    if args.knnlm and not 0.0 < args.lmbda < 1.0:
+        raise ValueError(f"--lmbda {args.lmbda} with --knnlm: the mixture needs 0 < lmbda < 1 (without kNN: drop --knnlm)")
+    if args.knnlm and args.knn_sim_func not in ("do_not_recomp_ip", "do_not_recomp_l2", "ip", "l2"):
+        raise ValueError("Invalid knn similarity function!")
+    if args.prompt_ids is None and (args.n_prompts < 1 or args.prompt_len < 1):
+        raise ValueError("--n-prompts and --prompt-len must be at least 1")
+
+
+def read_prompts(args):
+    """The prompts as fed: ``eos`` (the sentence start the language-modelling task feeds, token_block_dataset.py:134-144), then the
+    tokens of --prompt-ids or of ``--n-prompts`` consecutive pieces of ``--prompt-len`` tokens of the split."""
+    if args.prompt_ids is not None:
+        try:
+            ids = [int(s) for s in args.prompt_ids.split(",") if s.strip()]
+        except ValueError:
+            raise ValueError(f"--prompt-ids {args.prompt_ids!r}: comma-separated token ids") from None
+        return [[EOS] + ids]
+    from .eval_lm import fairseq_token_stream
+    stream = fairseq_token_stream(args.data, args.gen_subset)
+    if stream is None:
+        raise FileNotFoundError(f"the prompts are cut from {os.path.join(args.data, args.gen_subset)}.bin/.idx (fairseq's mmap dataset): "
+                                "not found or not in that format")
+    n = min(args.n_prompts, int(stream.shape[0]) // args.prompt_len)
+    if n < 1:
+        raise ValueError(f"the split holds fewer than --prompt-len {args.prompt_len} tokens")
+    return [[EOS] + [int(t) for t in stream[i * args.prompt_len:(i + 1) * args.prompt_len]] for i in range(n)]
+
+
+def main(args, model=None, file=None):
+    """-> dict(tokens, logp, lengths (numpy), prompts).  Prints fairseq's ``S-i`` / ``H-i`` lines to ``file`` (stdout)."""
+    import ast
+    from .eval_lm import load_symbols
+    from .transformer_lm import TransformerLM
+    check_args(args)
+    file = sys.stdout if file is None else file
+    device = torch.device(args.device)
+    torch.cuda.set_device(device)
+    prompts = read_prompts(args)
+    if model is None:
+        model, _ = TransformerLM.from_checkpoint(args.path, device, ast.literal_eval(args.model_overrides), precision="fp16" if args.fp16 else None)
+    elif args.fp16:
+        model.precision = "fp16"
+    logger.info("%d prompt(s), up to %d new tokens each, %s, precision %s", len(prompts), args.max_len_b,
+                f"top-{args.sampling_topk} sampling at temperature {args.temperature}" if args.sampling else "greedy", model.precision)
+    knn = None
+    if args.knnlm:
+        from .knn_model import KNNModel
+        knn = getattr(args, "knn_model", None) or KNNModel(
+            index_file=args.index_file, dstore_dir=args.dstore_dir, probe=args.probe, cuda=-1, k=args.k,
+            no_load_keys=("do_not_recomp" in args.knn_sim_func), use_memory=True, metric_type=args.knn_sim_func, device=device)
+        width = getattr(knn, "hidden_size", None)
+        if width is not None and int(width) != model.d:
+            raise ValueError(f"--knnlm: the queries have width {model.d}, the datastore {args.dstore_dir} holds keys of hidden_size {int(width)}")
+    g = Generator(model, knn, args.knn_keytype, k=args.k if args.knnlm else 0, lmbda=args.lmbda if args.knnlm else 0.0,
+                  knn_temperature=args.knn_temperature)
+    tokens, logp, lengths = g.generate(prompts, args.max_len_b, sampling=args.sampling, sampling_topk=args.sampling_topk,
+                                       temperature=args.temperature, unk_penalty=args.unkpen, seed=args.seed)
+    tokens, logp, lengths = tokens.cpu().numpy(), logp.cpu().numpy(), lengths.cpu().numpy()
+    symbols = load_symbols(args.data)
+    word = lambda t: symbols[t] if symbols is not None and 0 <= t < len(symbols) else str(t)
+    for i, p in enumerate(prompts):
+        n = int(lengths[i])
+        print(f"S-{i}\t" + " ".join(word(t) for t in p[1:]), file=file)
+        print(f"H-{i}\t{float(logp[i, :n].astype(np.float64).sum())}\t" + " ".join(word(int(t)) for t in tokens[i, :n]), file=file)
+    res = {"tokens": tokens, "logp": logp, "lengths": lengths, "prompts": prompts}
+    if args.out:
+        width = max(len(p) for p in prompts)
+        pr = np.full((len(prompts), width), PAD, dtype=np.int64)
+        for i, p in enumerate(prompts):
+            pr[i, :len(p)] = p
+        np.savez(args.out, tokens=tokens, logp=logp, lengths=lengths, prompts=pr, prompt_lengths=np.asarray([len(p) for p in prompts]))
+    return res
+
+
+def cli_main(argv=None):
+    logging.basicConfig(format="%(asctime)s | %(levelname)s | %(name)s | %(message)s", level=os.environ.get("LOGLEVEL", "INFO").upper(),
+                        stream=sys.stderr)
+    main(get_parser().parse_args(argv))
+
+
+if __name__ == "__main__":
+    cli_main()

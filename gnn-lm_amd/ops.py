@@ -321,6 +321,91 @@ def causal_attn_varlen(Q, K, V, block_off, H, max_ctx=0, out=None):
     return out
 
 
+def kv_cache_desc(k, v, lens, done=None, n_bad=None):
+    """A filled ``gnnlm_kv_cache_t`` over ``k`` / ``v`` f32 [L, B, cap, d] (views with wider strides welcome: unit element stride, the
+    rest multiples of 4), ``lens`` int32 [B], optional ``done`` int32 [B] and ``n_bad`` int32 [1] -- all on the device."""
+    _f32(k, v)
+    _dtype(lens, torch.int32, "lens"), _dtype(done, torch.int32, "done"), _dtype(n_bad, torch.int32, "n_bad")
+    for t in (k, v, lens, done, n_bad):
+        if t is not None and not t.is_cuda:
+            raise _lib.GnnlmError("gnnlm_amd kernels need device (HIP) tensors; there is no CPU fallback")
+    if k.dim() != 4 or v.shape != k.shape or v.stride() != k.stride() or (k.stride(3) != 1 and k.shape[3] > 1):
+        raise ValueError("kv_cache: k and v must be [L, B, cap, d] with the same strides and unit element stride")
+    L, B, cap, d = k.shape
+    if lens.shape != (B,) or not lens.is_contiguous() or (done is not None and (done.shape != (B,) or not done.is_contiguous())):
+        raise ValueError("kv_cache: lens / done must be contiguous [B]")
+    c = _lib.gnnlm_kv_cache_t()
+    c.k, c.v = k.data_ptr(), v.data_ptr()
+    c.ld_row = k.stride(2) if cap > 1 else max(k.stride(2), d)
+    c.ld_seq = k.stride(1) if B > 1 else max(k.stride(1), cap * c.ld_row)
+    c.ld_layer = k.stride(0) if L > 1 else max(k.stride(0), B * c.ld_seq)
+    c.L, c.B, c.cap, c.d = L, B, cap, d
+    c.len = lens.data_ptr()
+    c.done = done.data_ptr() if done is not None else None
+    c.n_bad = n_bad.data_ptr() if n_bad is not None else None
+    return c
+
+
+def decode_attn(q, k_new, v_new, k, v, lens, layer, H, done=None, n_bad=None, max_len=0, out=None, workspace=None):
+    """One new row per sequence against the K/V cache (``gnnlm_decode_attn``): ``q`` / ``k_new`` / ``v_new`` [B, H*dk] f32 sharing one row
+    stride (q already scaled), the cache as in :func:`kv_cache_desc` -> ``out`` [B, H*dk].  Row b with ``done[b] == 0`` and
+    ``0 <= lens[b] < cap`` gets ``k_new[b]`` / ``v_new[b]`` written to cache row ``lens[b]`` of ``layer`` and attends keys
+    ``0 .. lens[b]``; any other row gets zeros (one outside the range is counted in ``n_bad``).  ``lens`` is not changed.
+    ``max_len``: host bound on ``lens[b] + 1`` (0: cap).  d_k in {16, 32, 64, 128}; the result of a row is bit-reproducible and depends
+    on that row alone."""
+    _f32(q, k_new, v_new, out)
+    _dev(q, k_new, v_new, out)
+    c = kv_cache_desc(k, v, lens, done, n_bad)
+    if q.dim() != 2 or q.shape != (c.B, c.d) or k_new.shape != q.shape or v_new.shape != q.shape or \
+            k_new.stride(0) != q.stride(0) or v_new.stride(0) != q.stride(0):
+        raise ValueError("decode_attn: q, k_new, v_new must be [B, d] with one row stride")
+    if out is None:
+        out = torch.empty(c.B, c.d, device=q.device, dtype=torch.float32)
+    dk = c.d // H
+    need = _lib.lib().gnnlm_decode_attn_workspace_bytes(c.B, H, dk, max_len or c.cap)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 16), device=q.device, dtype=torch.uint8)
+    a = _lib.gnnlm_decode_attn_t()
+    a.q, a.k_new, a.v_new, a.ld = q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), max(q.stride(0), c.d)
+    a.out, a.ldo = out.data_ptr(), max(out.stride(0), c.d)
+    a.cache, a.layer, a.H, a.dk, a.max_len = c, int(layer), int(H), dk, int(max_len)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    call_desc("gnnlm_decode_attn", a)
+    return out
+
+
+def sample_topk(logp, ids, u=None, pad=1, eos=2, done=None, n_bad=None, out=None, out_logp=None, want_logp=True):
+    """The next token of every row from its sorted top-N (``gnnlm_sample_topk``): ``logp`` f32 / ``ids`` i64 [B, N] best first, as
+    :func:`topk_merge` leaves them.  ``u`` None: greedy (column 0); ``u`` f32 [B] in [0, 1): the smallest j whose inclusive prefix sum of
+    ``exp(logp_j - logp_0)`` exceeds ``u * total`` (search.py:231-247 with the caller's random numbers).  -> ``(next i64 [B], next_logp f32
+    [B] or None)``; ``done`` int32 [B] (optional, updated in place): a done row gets ``pad``, a pick of ``eos`` sets it."""
+    _dev(logp, ids, u, done, n_bad, out, out_logp)
+    _f32(logp, u, out_logp)
+    _dtype(ids, torch.int64, "ids"), _dtype(out, torch.int64, "out"), _dtype(done, torch.int32, "done"), _dtype(n_bad, torch.int32, "n_bad")
+    if logp.dim() != 2 or ids.shape != logp.shape:
+        raise ValueError("sample_topk: logp / ids [B, N]")
+    B, N = logp.shape
+    for t in (u, done, out, out_logp):
+        if t is not None and (t.shape != (B,) or not t.is_contiguous()):
+            raise ValueError("sample_topk: u / done / out / out_logp must be contiguous [B]")
+    if out is None:
+        out = torch.empty(B, device=logp.device, dtype=torch.int64)
+    if out_logp is None and want_logp:
+        out_logp = torch.empty(B, device=logp.device, dtype=torch.float32)
+    s = _lib.gnnlm_sample_topk_t()
+    s.logp, s.ld_logp = logp.data_ptr(), _row_stride(logp)
+    s.ids, s.ld_ids = ids.data_ptr(), _row_stride(ids)
+    s.B, s.N = B, N
+    s.u = u.data_ptr() if u is not None else None
+    s.pad, s.eos = int(pad), int(eos)
+    s.next = out.data_ptr()
+    s.next_logp = out_logp.data_ptr() if out_logp is not None else None
+    s.done = done.data_ptr() if done is not None else None
+    s.n_bad = n_bad.data_ptr() if n_bad is not None else None
+    call_desc("gnnlm_sample_topk", s)
+    return out, out_logp
+
+
 def ptr_strided(t):
     """Device pointer of a 2-D tensor whose rows are contiguous (row stride >= width)."""
     if t.dim() != 2 or t.stride(1) != 1:

@@ -80,6 +80,28 @@ def fused_qkv(sd, prefix, d):
     return w.clone(), b.clone()
 
 
+class KVCache:
+    """The K/V cache of :meth:`TransformerLM.prefill` / :meth:`TransformerLM.step` (``gnnlm_kv_cache_t``): ``k`` / ``v`` f32
+    [L, B, cap, d], ``len`` int32 [B] (keys held per sequence), ``done`` int32 [B], ``n_bad`` int32 [1] -- all on the device -- and
+    ``steps``, the HOST's upper bound on ``len.max()`` (the prompts' longest block plus the steps taken since): what ``max_len`` of the
+    C entries is computed from, so that no step has to read ``len`` back."""
+
+    def __init__(self, L, B, cap, d, device):
+        self.k = torch.empty(L, B, cap, d, device=device, dtype=torch.float32)
+        self.v = torch.empty(L, B, cap, d, device=device, dtype=torch.float32)
+        self.len = torch.zeros(B, device=device, dtype=torch.int32)
+        self.done = torch.zeros(B, device=device, dtype=torch.int32)
+        self.n_bad = torch.zeros(1, device=device, dtype=torch.int32)
+        self.L, self.B, self.cap, self.d, self.steps = L, B, cap, d, 0
+
+    def desc(self):
+        return ops.kv_cache_desc(self.k, self.v, self.len, self.done, self.n_bad)
+
+    def reset(self):
+        self.len.zero_(), self.done.zero_(), self.n_bad.zero_()
+        self.steps = 0
+
+
 class TransformerLM:
     def __init__(self, embed, layers, H, act="relu", scale=None, pos=None, learned_pos=False, ln_emb=None, ln_out=None, head=None,
                  device=None, precision=None, pad_idx=PAD_IDX, ln_eps=1e-5):
@@ -174,6 +196,68 @@ class TransformerLM:
         has one, ``inner_states[-1]`` before it, ``last_ffn_input`` the last layer's ``final_layer_norm`` output.
         ``check``: read the count of token ids outside the vocabulary together with the results (one synchronisation) and raise;
         a driver passes False and calls :meth:`check_tokens` once at the end."""
+        return self._forward(tokens, block_off, want_inner, want_ffn_input, check, None)
+
+    def new_cache(self, B, cap):
+        """An empty :class:`KVCache` for ``B`` sequences of up to ``cap`` tokens (prompt + continuation).  A sinusoidal position table
+        is grown HERE, once, to the ``cap`` positions the cache can hold: no step builds or uploads a table.  (Growing replaces the
+        table: a step captured in a graph before a LARGER cache was made must be captured again.)"""
+        if B < 1 or cap < 1:
+            raise ValueError("new_cache: B >= 1 and cap >= 1")
+        self._positions(int(cap))
+        return KVCache(self.L, int(B), int(cap), self.d, self.device)
+
+    def prefill(self, tokens, block_off, cache, want_inner=True, want_ffn_input=True, check=True):
+        """:meth:`extract_features` over packed prompts -- block b is sequence b of ``cache`` -- that also writes every layer's K' / V'
+        rows into the cache and sets ``cache.len`` (``gnnlm_transformer_lm_prefill``).  Returns ``(x, extra)`` exactly as
+        ``extract_features`` does, the same bits.  Refused before any launch: another number of blocks than ``cache.B``, a block longer
+        than ``cache.cap``."""
+        return self._forward(tokens, block_off, want_inner, want_ffn_input, check, cache)
+
+    def step(self, tokens, cache, want_inner=True, want_ffn_input=True, max_len=None):
+        """One decoding step (``gnnlm_transformer_lm_step``): ``tokens`` int64 [B] (device), token b is appended to sequence b ->
+        ``(x [B, d], extra)`` as :meth:`extract_features` names them -- the mirror of ``extract_features(prev_output_tokens,
+        incremental_state=...)``, which looks at the last token only (transformer.py:739-750).  Only enqueues: no host read, no
+        synchronisation, no allocation beyond the outputs once the stream's workspace is large enough (the sinusoidal table was sized for
+        ``cache.cap`` positions by :meth:`new_cache`, not here) -- a step can be captured in a graph.  ``max_len``: the host bound on ``len + 1`` (default ``cache.steps + 1``; for a captured step, the bound over every replay).
+        A full cache and a position beyond a learned table are refused before any launch."""
+        if tokens.dtype != torch.int64 or tokens.shape != (cache.B,):
+            raise TypeError("step: tokens must be int64 [B]")
+        if not tokens.is_cuda or not tokens.is_contiguous():
+            raise _lib.GnnlmError("gnnlm_amd kernels need contiguous device (HIP) tensors; there is no CPU fallback")
+        bound = cache.steps + 1 if max_len is None else int(max_len)
+        # the table of new_cache: cache.cap positions, whatever the bound (a cache made by hand is served here, once)
+        m = self._desc(self._positions(cache.cap))
+        c = cache.desc()
+        io = _lib.gnnlm_tlm_step_io_t()
+        io.tokens, io.max_len = tokens.data_ptr(), bound
+        new = lambda: torch.empty(cache.B, self.d, device=tokens.device, dtype=torch.float32)
+        x = new()
+        inner = new() if want_inner else None
+        ffn_in = new() if want_ffn_input else None
+        io.out = x.data_ptr()
+        io.last_inner = inner.data_ptr() if inner is not None else None
+        io.last_ffn_input = ffn_in.data_ptr() if ffn_in is not None else None
+        io.n_bad = self.n_bad.data_ptr()
+        L = _lib.lib()
+        need = L.gnnlm_transformer_lm_step_workspace_bytes(ctypes.byref(m), ctypes.byref(c), ctypes.byref(io))
+        ws = self._workspace(need, tokens.device)
+        _lib.check(L.gnnlm_transformer_lm_step(ctypes.byref(m), ctypes.byref(c), ctypes.byref(io), _lib.ptr(ws), ws.numel(), _lib.stream()),
+                   "gnnlm_transformer_lm_step")
+        cache.steps += 1                                        # (replays of a captured step: the caller adds them)
+        extra = {"inner_states": [inner]}
+        if ffn_in is not None:
+            extra["last_ffn_input"] = ffn_in
+        return x, extra
+
+    def _workspace(self, need, device):
+        key = _lib.raw_stream()                                 # one arena per stream
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[key] = torch.empty(need, device=device, dtype=torch.uint8)
+        return ws
+
+    def _forward(self, tokens, block_off, want_inner, want_ffn_input, check, cache):
         from .ragged import as_ragged
         if tokens.dtype != torch.int64 or tokens.dim() != 1:
             raise TypeError("extract_features: tokens must be int64 [n_tok]")
@@ -197,12 +281,15 @@ class TransformerLM:
         io.n_bad = self.n_bad.data_ptr()
         L = _lib.lib()
         need = L.gnnlm_transformer_lm_workspace_bytes(ctypes.byref(m), ctypes.byref(io))
-        key = _lib.raw_stream()                                 # one arena per stream
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = self._ws[key] = torch.empty(need, device=tokens.device, dtype=torch.uint8)
-        _lib.check(L.gnnlm_transformer_lm_forward(ctypes.byref(m), ctypes.byref(io), _lib.ptr(ws), ws.numel(), _lib.stream()),
-                   "gnnlm_transformer_lm_forward")
+        ws = self._workspace(need, tokens.device)
+        if cache is None:
+            _lib.check(L.gnnlm_transformer_lm_forward(ctypes.byref(m), ctypes.byref(io), _lib.ptr(ws), ws.numel(), _lib.stream()),
+                       "gnnlm_transformer_lm_forward")
+        else:
+            c = cache.desc()
+            _lib.check(L.gnnlm_transformer_lm_prefill(ctypes.byref(m), ctypes.byref(io), ctypes.byref(c), _lib.ptr(ws), ws.numel(),
+                                                      _lib.stream()), "gnnlm_transformer_lm_prefill")
+            cache.steps = max_len
         if check:
             self.check_tokens()
         extra = {"inner_states": [inner if inner is not None else None]}

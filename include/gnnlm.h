@@ -967,6 +967,115 @@ int gnnlm_transformer_lm_forward(const gnnlm_tlm_t* model, const gnnlm_tlm_io_t*
                                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Incremental decoding of the base transformer LM: a K/V cache, the attention of ONE new row per sequence against it, the
+ * prefill and the step that use them, and the pick of the next token.  Additive to ABI 12: new structs and new entries.
+ * Replaces: the incremental_state branches of MultiheadAttention.forward (fairseq/modules/multihead_attention.py: saved
+ *           prev_key / prev_value, concatenated with the new row) under TransformerDecoder.extract_features(...,
+ *           incremental_state=) (fairseq/models/transformer.py:739-750, which keeps the last token only), and the sampling step
+ *           of fairseq/search.py:231-265.
+ * ---------------------------------------------------------------------------------------------- */
+/* The cache is a DESCRIPTOR over caller-owned memory: nothing here allocates.  k and v are f32 [L][B][cap][d]: row u of sequence
+ * b in layer l starts at l * ld_layer + b * ld_seq + u * ld_row, holds K' (V') of the H heads side by side (head h at columns
+ * h * d_k ..), and is valid for u < len[b].  ld_row >= d, ld_seq >= cap * ld_row, ld_layer >= B * ld_seq, all multiples of 4; k
+ * and v 16-byte aligned.  len / done / n_bad live on the DEVICE: a kernel reads them when it runs, so a captured graph follows
+ * them from replay to replay.  A len[b] outside [0, cap) cannot be verified against the memory: the row is counted in *n_bad
+ * (added to; the caller zeroes it) and never followed -- nothing of sequence b is read or written. */
+#define GNNLM_DECODE_CHUNK 128            /* keys of one (b, h) that one wave takes: the unit of the split, fixed */
+typedef struct gnnlm_kv_cache {
+    float *k, *v;                         /* [L][B][cap][d] */
+    int64_t ld_row, ld_seq, ld_layer;     /* in floats */
+    int32_t L, B, cap, d;
+    int32_t* len;                         /* DEVICE [B]: keys held per sequence */
+    int32_t* done;                        /* optional DEVICE [B]: != 0 = the sequence has ended */
+    int32_t* n_bad;                       /* optional DEVICE int32: rows whose len is outside [0, cap), added to */
+} gnnlm_kv_cache_t;
+
+/* One layer, one new row per sequence.  For every row b with done[b] == 0 and 0 <= len[b] < cap:
+ *   cache row len[b] of layer `layer` := k_new[b], v_new[b]   (bit for bit; no other cache byte is written)
+ *   out[b, h*dk:(h+1)*dk] = sum_{u <= len[b]} softmax_u(q_bh . K_bhu) V_bhu
+ * q is used as given (the d_k^-0.5 is folded into wqkv: gnnlm_tlm_t).  All maths in f32.  A done row appends nothing and gets a
+ * zero out row; a row with len[b] outside [0, cap) appends nothing, gets zeros and is counted in *cache.n_bad (a done row is
+ * not counted).  len is NOT changed: the caller advances it once all layers have run (gnnlm_transformer_lm_step does).
+ * Split: the keys of one (b, h) are cut into chunks of GNNLM_DECODE_CHUNK; one wave takes one chunk -- K and V rows straight
+ * into registers with 16-byte loads, every cached byte once, a running (maximum, sum, accumulator) per lane group, merged
+ * inside the wave in a fixed order -- and stores its (maximum, sum, accumulator) in the workspace.  A second small launch
+ * combines the chunks of a (b, h) in ascending chunk order and writes out.  No float atomics: out[b] depends only on len[b],
+ * q[b], k_new[b], v_new[b] and the cache rows [0, len[b]) of b -- not on B, the other rows, cap or max_len -- and is the same bits
+ * on every run.  Cache rows above len[b] are never read.
+ * `max_len` is HOST data: an upper bound on len[b] + 1 over the rows that take part (it sizes the grid and the workspace; 0 is
+ * read as cap).  A row with len[b] + 1 > max_len is treated as out of range (zeros, counted).
+ * GNNLM_E_INVALID before anything is launched: dk outside {16, 32, 64, 128}, H < 1, H * dk != cache.d, layer outside [0, L),
+ * B < 0, cap < 1, max_len outside [0, cap], a stride that is too small or no multiple of 4, a pointer that is NULL or not
+ * 16-byte aligned, a workspace smaller than gnnlm_decode_attn_workspace_bytes.  B = 0 is accepted and touches nothing. */
+typedef struct gnnlm_decode_attn {
+    const float *q, *k_new, *v_new;  int64_t ld;     /* [B, H*dk] each, one row stride ld >= H*dk (the q | k | v GEMM output) */
+    float* out;  int64_t ldo;                        /* [B, H*dk] */
+    gnnlm_kv_cache_t cache;
+    int32_t layer, H, dk;
+    int32_t max_len;                                 /* HOST: len[b] + 1 <= max_len; 0 = cap */
+    void* workspace;  size_t workspace_bytes;
+} gnnlm_decode_attn_t;
+/* B * H * ceil(max_len / GNNLM_DECODE_CHUNK) * (dk + 4) floats; for a descriptor with max_len = 0 pass cap */
+size_t gnnlm_decode_attn_workspace_bytes(int32_t B, int32_t H, int32_t dk, int32_t max_len);
+int gnnlm_decode_attn(const gnnlm_decode_attn_t* desc, void* stream);
+
+/* gnnlm_transformer_lm_forward over packed prompts that also fills the cache: block b is sequence b.  After each layer's q|k|v
+ * GEMM one copy kernel writes the K' and V' rows of block b to cache rows [0, len_b) of sequence b of that layer; a last tiny
+ * launch sets len[b] = len_b.  done is not touched.  The forward itself enqueues exactly what gnnlm_transformer_lm_forward
+ * enqueues, so `io`'s outputs are the same bits.  Workspace: gnnlm_transformer_lm_workspace_bytes.  Refused before anything is
+ * launched, beyond what the forward refuses: io->blocks.n_blocks != cache->B, io->max_len > cache->cap (a block longer than
+ * the cache; max_len is host-known), cache->d != model->d, cache->L != model->L, a cache that gnnlm_decode_attn would refuse.  A
+ * block that turns out longer than io->max_len on the device is cut at io->max_len rows (memory safety only). */
+int gnnlm_transformer_lm_prefill(const gnnlm_tlm_t* model, const gnnlm_tlm_io_t* io, const gnnlm_kv_cache_t* cache,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* One decoding step: token b is appended to sequence b.  x[b] = fl32(fl32(scale * E[tok[b]]) + P[pad_idx + 1 + len[b]]) (the two
+ * roundings of gnnlm_lm_embed, the position read on the device; an id outside [0, n_vocab) or a len[b] outside [0, cap) gives a
+ * zero row and is counted in *n_bad), then per layer LayerNorm, the q|k|v GEMM with M = B, gnnlm_decode_attn, the out-projection
+ * with bias and residual, LayerNorm, fc1, the activation, fc2 with bias and residual; the optional final LayerNorm; and one last
+ * tiny launch does len[b] += 1 for the rows that are not done and in range.  The rows of a done sequence are computed from
+ * a zero attention output and mean nothing.
+ * `max_len` is HOST data: an upper bound on len[b] + 1 over EVERY execution of the enqueued work -- for a captured graph, over
+ * every replay.  max_len < 1, max_len > cache->cap and pad_idx + 1 + max_len > p_rows (with a position table) are refused before
+ * anything is launched, as is everything gnnlm_transformer_lm_forward and gnnlm_decode_attn refuse.  The call only enqueues: no
+ * allocation, no host read, no synchronisation -- it can be captured in a HIP graph. */
+typedef struct gnnlm_tlm_step_io {
+    const int64_t* tokens;     /* DEVICE [B] */
+    int64_t max_len;           /* HOST */
+    float* out;                /* [B, d] */
+    float* last_inner;         /* optional [B, d] */
+    float* last_ffn_input;     /* optional [B, d] */
+    int32_t* n_bad;            /* optional DEVICE int32: token ids outside the vocabulary, added to */
+} gnnlm_tlm_step_io_t;
+size_t gnnlm_transformer_lm_step_workspace_bytes(const gnnlm_tlm_t* model, const gnnlm_kv_cache_t* cache, const gnnlm_tlm_step_io_t* io);
+int gnnlm_transformer_lm_step(const gnnlm_tlm_t* model, const gnnlm_kv_cache_t* cache, const gnnlm_tlm_step_io_t* io,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* The next token of every row from its SORTED top-N (what gnnlm_topk_merge leaves: logp [B, N] best first, ids [B, N], N <= 2048).
+ *   u == NULL: greedy, column 0.
+ *   u given (DEVICE f32 [B], in [0, 1)): the smallest j with c_j > u[b] * c_{N-1}, c the inclusive prefix sum of
+ *   exp(logp_j - logp_0) in float32 (association order unspecified).  A -inf (or NaN) entry contributes 0 and is never picked.
+ *   This is probs = lprobs.topk(k).exp_(); torch.multinomial(probs, 1) of search.py:231-247 with the caller's random numbers.
+ * next[b] = ids[b, j]; next_logp[b] (optional) = logp[b, j], the column's own value, not renormalised (search.py:258-265).
+ * done (optional DEVICE int32 [B]): a done row gets next = pad and is otherwise untouched; a pick equal to eos sets done[b] = 1.
+ * A row whose logp[b, 0] is not finite has nothing to pick from: next = pad, done = 1 (if given), counted in *n_bad (optional
+ * DEVICE int32, added to); its next_logp is left alone.  One wave per row.
+ * GNNLM_E_INVALID before anything is launched: N outside [1, 2048], B < 0, ld_logp / ld_ids < N, a NULL logp / ids / next.
+ * B = 0 is accepted and touches nothing. */
+typedef struct gnnlm_sample_topk {
+    const float* logp;  int64_t ld_logp;  /* [B, N] */
+    const int64_t* ids;  int64_t ld_ids;  /* [B, N] */
+    int32_t B, N;
+    const float* u;                       /* optional [B] */
+    int64_t pad, eos;
+    int64_t* next;                        /* [B] */
+    float* next_logp;                     /* optional [B] */
+    int32_t* done;                        /* optional [B] */
+    int32_t* n_bad;                       /* optional */
+} gnnlm_sample_topk_t;
+int gnnlm_sample_topk(const gnnlm_sample_topk_t* desc, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * kNN-LM on the base LM: the SCORED rows of packed samples (each sample = context rows, then scored rows: --context-window) as
  * one contiguous [n_out, d] query matrix, and / or the same rows scaled to unit length for a cosine index -- one launch instead of
  * one slice per sample + torch.cat + the four-op normalisation.  Additive to ABI 12: a new struct and a new entry.
