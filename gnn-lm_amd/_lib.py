@@ -120,6 +120,7 @@ def lib():
         L.gnnlm_transformer_lm_step_workspace_bytes.restype = ctypes.c_size_t
         L.gnnlm_transformer_lm_step_workspace_bytes.argtypes = [vp, vp, vp]
         L.gnnlm_transformer_lm_step.argtypes = [vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.gnnlm_transformer_lm_step_beam.argtypes = [vp, vp, vp, vp, i64, vp, ctypes.c_size_t, vp]
         L.gnnlm_row_lse_pick.argtypes = [vp, i64, i64, vp, i32, vp, vp, vp, vp]
         L.gnnlm_lse_reduce.argtypes = [vp, i32, i64, vp, vp, vp]
         L.gnnlm_pq_encode.argtypes = [vp, i64, vp, vp, i32, i32, i64, vp, vp]
@@ -161,7 +162,8 @@ def lib():
         for nm in ("gnnlm_gemm_nt", "gnnlm_pq_gather_decode", "gnnlm_token_gather", "gnnlm_star_attn", "gnnlm_chain_attn",
                    "gnnlm_knn_interp", "gnnlm_knn_interp_grid", "gnnlm_knn_mix_dense", "gnnlm_knn_recompute_sims", "gnnlm_topk_merge", "gnnlm_ivfpq_scan", "gnnlm_gather_rows_peer",
                    "gnnlm_ivfpq_scan8", "gnnlm_ivfpq_rescore", "gnnlm_ivfpq_tau", "gnnlm_group_assign",
-                   "gnnlm_ivfpq_tables", "gnnlm_pack_rows", "gnnlm_decode_attn", "gnnlm_sample_topk"):
+                   "gnnlm_ivfpq_tables", "gnnlm_pack_rows", "gnnlm_decode_attn", "gnnlm_sample_topk", "gnnlm_beam_attn",
+                   "gnnlm_beam_select"):
             getattr(L, nm).argtypes = [vp, vp]
         if L.gnnlm_target_arch() != b"gfx950" or L.gnnlm_abi_version() != ABI_VERSION:
             raise GnnlmError(f"libgnnlm_hip.so is not the gfx950 / ABI-{ABI_VERSION} build")

@@ -26,12 +26,15 @@ struct DecParams {
     float* out; int64_t ldo;
     int B, H, n_chunk;
     int32_t* keys_out;                     // profiling only (else nullptr): the keys the launch really attends, summed over b
+    const int32_t* src; int64_t ld_src;    // IND only (gnnlm_beam_attn): key row u < len of b is row u of cache sequence src[b][u]
 };
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
-template <int DK>
+// IND (gnnlm_beam_attn): the cached rows are found through p.src; the loads, the arithmetic and their order are the same, so a row's
+// bits are those of the contiguous cache.  A table entry outside [0, B) is not followed and flags the chunk's partial (third float).
+template <int DK, bool IND = false>
 __global__ __launch_bounds__(256) void decode_attn_chunk_kernel(DecParams p) {
     constexpr int LPK = DK / 4;            // lanes per key row
     constexpr int G = 64 / LPK;            // key rows per wave-wide load
@@ -59,6 +62,8 @@ __global__ __launch_bounds__(256) void decode_attn_chunk_kernel(DecParams p) {
         st4(vb + (int64_t)len * p.ld_row, ld4(vnp));
     }
     const float4 q4 = ld4(qp);
+    [[maybe_unused]] const int32_t* tab = IND ? p.src + b * p.ld_src : nullptr;
+    [[maybe_unused]] bool bad = false;
     float m = -INFINITY, s = 0.f;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int it = 0; it < CHUNK / G; it += UNR) {
@@ -68,10 +73,25 @@ __global__ __launch_bounds__(256) void decode_attn_chunk_kernel(DecParams p) {
 #pragma unroll
         for (int j = 0; j < UNR; ++j) {
             const int u = u0 + (it + j) * G + g;
-            const bool valid = u <= len;
+            bool valid = u <= len;
             // the new row is read from k_new / v_new, not back from the cache; an invalid key reads nothing of the cache either
             const float* kp = u < len ? kb + (int64_t)u * p.ld_row : knp;
             const float* vp = u < len ? vb + (int64_t)u * p.ld_row : vnp;
+            if constexpr (IND) {
+                if (u < len) {
+                    const int slot = tab[u];
+                    if (slot >= 0 && slot < p.B) {
+                        const int64_t off = slot * p.ld_seq + col + (int64_t)u * p.ld_row;
+                        kp = p.kc + off;
+                        vp = p.vc + off;
+                    } else {                                   // never followed: nothing of the cache is read for this key
+                        kp = knp;
+                        vp = vnp;
+                        valid = false;
+                        bad = true;
+                    }
+                }
+            }
             const float4 k4 = ld4(kp);
             const float4 vv = ld4(vp);
             float dot = q4.x * k4.x;
@@ -117,12 +137,14 @@ __global__ __launch_bounds__(256) void decode_attn_chunk_kernel(DecParams p) {
         acc.w += __shfl_xor(acc.w, o, 64);
     }
     float* dst = p.part + item * (DK + 4);
-    if (lane == 0) st4(dst, make_float4(M, s, 0.f, 0.f));
+    float flag = 0.f;
+    if constexpr (IND) flag = __any(bad) ? 1.f : 0.f;
+    if (lane == 0) st4(dst, make_float4(M, s, flag, 0.f));
     if (g == 0) st4(dst + 4 + sub * 4, acc);
 }
 
 // The chunks of a (b, h) in ascending order; a wave takes G (b, h) pairs, each lane 4 output columns.
-template <int DK>
+template <int DK, bool IND = false>
 __global__ __launch_bounds__(64) void decode_attn_combine_kernel(DecParams p) {
     constexpr int LPK = DK / 4;
     constexpr int G = 64 / LPK;
@@ -142,7 +164,13 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(DecParams p) {
     float* o = p.out + b * p.ldo + (int64_t)h * DK + sub * 4;
     const bool dn = p.done && p.done[b] != 0;
     const int len = p.len[b];
-    const bool bad = len < 0 || len >= p.cap;
+    bool bad = len < 0 || len >= p.cap;
+    if constexpr (IND) {                                      // a chunk that met a table entry outside [0, B): the row is out of range
+        if (!dn && !bad) {
+            const float* f = p.part + bh * p.n_chunk * (DK + 4);
+            for (int c = 0; c < len / CHUNK + 1; ++c, f += DK + 4) bad |= f[2] != 0.f;
+        }
+    }
     if (dn || bad) {
         st4(o, make_float4(0.f, 0.f, 0.f, 0.f));
         if (!dn && h == 0 && sub == 0 && p.n_bad) atomicAdd(p.n_bad, 1);
@@ -229,7 +257,9 @@ size_t decode_attn_workspace_bytes(int B, int H, int dk, int max_len) {
     return (size_t)B * H * cdiv(max_len, CHUNK) * (dk + 4) * sizeof(float);
 }
 
-int decode_attn(const gnnlm_decode_attn_t& d, hipStream_t stream) {
+namespace {
+// src == nullptr: gnnlm_decode_attn, its two launches as they always were; else gnnlm_beam_attn
+int decode_attn_launch(const gnnlm_decode_attn_t& d, const int32_t* src, int64_t ld_src, bool beam, hipStream_t stream) {
     const gnnlm_kv_cache_t& c = d.cache;
     GNNLM_REQUIRE(decode_attn_ok(d.dk), "decode_attn: d_k must be 16, 32, 64 or 128");
     int rc = check_kv_cache(c);
@@ -238,19 +268,23 @@ int decode_attn(const gnnlm_decode_attn_t& d, hipStream_t stream) {
     GNNLM_REQUIRE(d.layer >= 0 && d.layer < c.L, "decode_attn: layer outside [0, L)");
     GNNLM_REQUIRE(d.max_len >= 0 && d.max_len <= c.cap, "decode_attn: max_len outside [0, cap]");
     GNNLM_REQUIRE(d.ld >= c.d && d.ld % 4 == 0 && d.ldo >= c.d && d.ldo % 4 == 0, "decode_attn: ld / ldo must be multiples of 4 and >= H * d_k");
+    if (beam) GNNLM_REQUIRE(ld_src >= c.cap, "beam_attn: ld_src < cache.cap");
     if (c.B == 0) return OK;
+    if (beam) GNNLM_REQUIRE(src && (uintptr_t)src % 4 == 0, "beam_attn: src missing or misaligned");
     GNNLM_REQUIRE(d.q && d.k_new && d.v_new && d.out, "decode_attn: q / k_new / v_new / out missing");
     GNNLM_REQUIRE(((uintptr_t)d.q | (uintptr_t)d.k_new | (uintptr_t)d.v_new | (uintptr_t)d.out) % 16 == 0, "decode_attn: q / k_new / v_new / out must be 16-byte aligned");
     const int bound = d.max_len ? d.max_len : c.cap;
     const size_t need = decode_attn_workspace_bytes(c.B, d.H, d.dk, bound);
     GNNLM_REQUIRE(d.workspace && (uintptr_t)d.workspace % 16 == 0 && d.workspace_bytes >= need, "decode_attn: workspace missing, misaligned or too small");
     DecParams p{d.q, d.k_new, d.v_new, d.ld, c.k + d.layer * c.ld_layer, c.v + d.layer * c.ld_layer, c.ld_row, c.ld_seq, bound,
-                c.len, c.done, c.n_bad, reinterpret_cast<float*>(d.workspace), d.out, d.ldo, c.B, d.H, (int)cdiv(bound, CHUNK), nullptr};
+                c.len, c.done, c.n_bad, reinterpret_cast<float*>(d.workspace), d.out, d.ldo, c.B, d.H, (int)cdiv(bound, CHUNK), nullptr,
+                src, ld_src};
     const int64_t items = (int64_t)c.B * d.H * p.n_chunk;
     GNNLM_REQUIRE(cdiv(items, 4) < (1ll << 31), "decode_attn: too many chunks for one launch");
     // work: K and V read once, the partials written and read once -- stated for B * bound keys, which is all the host knows, and
     // scaled by the keys the rows really hold (sum of len[b] + 1), which the combine kernel reports when a profile is open
-    ProfScope prof(K_CAUSAL, stream, 4.0 * c.B * bound * c.d, 8.0 * c.B * bound * c.d + 8.0 * items * (d.dk + 4) + 16.0 * c.B * c.d,
+    ProfScope prof(K_CAUSAL, stream, 4.0 * c.B * bound * c.d,
+                   8.0 * c.B * bound * c.d + 8.0 * items * (d.dk + 4) + 16.0 * c.B * c.d + (beam ? 4.0 * d.H * c.B * bound : 0.0),
                    c.len, (double)c.B * bound, true);
     if (!prof.slot) prof.sd = nullptr;                        // (no slot to be had: the bound stands, unscaled)
     p.keys_out = prof.slot;
@@ -260,10 +294,23 @@ int decode_attn(const gnnlm_decode_attn_t& d, hipStream_t stream) {
         hipLaunchKernelGGL(decode_attn_chunk_kernel<DK>, g1, dim3(256), 0, stream, p);                 \
         hipLaunchKernelGGL(decode_attn_combine_kernel<DK>, g2, dim3(64), 0, stream, p);                \
         break;
-    switch (d.dk) { GNNLM_DEC(16) GNNLM_DEC(32) GNNLM_DEC(64) GNNLM_DEC(128) }
+#define GNNLM_DEC_IND(DK)                                                                              \
+    case DK:                                                                                           \
+        hipLaunchKernelGGL((decode_attn_chunk_kernel<DK, true>), g1, dim3(256), 0, stream, p);         \
+        hipLaunchKernelGGL((decode_attn_combine_kernel<DK, true>), g2, dim3(64), 0, stream, p);        \
+        break;
+    if (!beam) switch (d.dk) { GNNLM_DEC(16) GNNLM_DEC(32) GNNLM_DEC(64) GNNLM_DEC(128) }
+    else switch (d.dk) { GNNLM_DEC_IND(16) GNNLM_DEC_IND(32) GNNLM_DEC_IND(64) GNNLM_DEC_IND(128) }
 #undef GNNLM_DEC
+#undef GNNLM_DEC_IND
     GNNLM_LAUNCH_CHECK();
     return OK;
+}
+}  // namespace
+
+int decode_attn(const gnnlm_decode_attn_t& d, hipStream_t stream) { return decode_attn_launch(d, nullptr, 0, false, stream); }
+int beam_attn(const gnnlm_decode_attn_t& d, const int32_t* src, int64_t ld_src, hipStream_t stream) {
+    return decode_attn_launch(d, src, ld_src, true, stream);
 }
 
 int kv_cache_fill(const float* qkv, int64_t ld_src, const gnnlm_kv_cache_t& c, int layer, const gnnlm_ragged_t& rg, int max_rows,
@@ -306,6 +353,13 @@ int gnnlm_decode_attn(const gnnlm_decode_attn_t* d, void* stream) {
         return E_INVALID;
     }
     return decode_attn(*d, (hipStream_t)stream);
+}
+int gnnlm_beam_attn(const gnnlm_beam_attn_t* d, void* stream) {
+    if (!d) {
+        set_error("invalid argument: null descriptor");
+        return E_INVALID;
+    }
+    return beam_attn(d->a, d->src, d->ld_src, (hipStream_t)stream);
 }
 
 }  // extern "C"

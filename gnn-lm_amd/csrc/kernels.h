@@ -124,6 +124,10 @@ bool decode_attn_ok(int dk);
 int check_kv_cache(const gnnlm_kv_cache_t& c);
 size_t decode_attn_workspace_bytes(int B, int H, int dk, int max_len);
 int decode_attn(const gnnlm_decode_attn_t& d, hipStream_t stream);
+// the same through a table of cache slots (gnnlm_beam_attn): key row u < len of sequence b is row u of sequence src[b][u]
+int beam_attn(const gnnlm_decode_attn_t& d, const int32_t* src, int64_t ld_src, hipStream_t stream);
+// one beam-search step of every sentence (beam.hip)
+int beam_select(const gnnlm_beam_select_t& d, hipStream_t stream);
 // K' | V' of the packed q | k | v rows [n_tok, ld_src] -> cache rows [0, min(len_b, max_rows)) of sequence b = block b of `layer`
 int kv_cache_fill(const float* qkv, int64_t ld_src, const gnnlm_kv_cache_t& c, int layer, const gnnlm_ragged_t& rg, int max_rows,
                   hipStream_t stream);

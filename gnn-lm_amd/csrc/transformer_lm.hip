@@ -274,7 +274,9 @@ size_t carve_step(const gnnlm_tlm_t& m, int B, int max_len, char* base, TlmBufs&
     return off + n + 256;
 }
 
-int tlm_step(const gnnlm_tlm_t& m, const gnnlm_kv_cache_t& c, const gnnlm_tlm_step_io_t& io, void* ws, size_t ws_bytes, hipStream_t s) {
+// beam (gnnlm_transformer_lm_step_beam): every layer's attention reads its cached rows through the table src
+int tlm_step(const gnnlm_tlm_t& m, const gnnlm_kv_cache_t& c, const gnnlm_tlm_step_io_t& io, void* ws, size_t ws_bytes, hipStream_t s,
+             bool beam = false, const int32_t* src = nullptr, int64_t ld_src = 0) {
     TRY(check_tlm(m));
     TRY(check_tlm_cache(m, c));
     const int B = c.B, d = m.d, dk = m.d / m.H;
@@ -316,7 +318,7 @@ int tlm_step(const gnnlm_tlm_t& m, const gnnlm_kv_cache_t& c, const gnnlm_tlm_st
         TRY(linear(b.h, w.wqkv, w.bqkv, b.wide, B, 3 * d, d, nullptr, s));
         a.layer = l;
         if (l > 0) a.cache.n_bad = nullptr;                 // a row out of range is counted once per step, not once per layer
-        TRY(decode_attn(a, s));
+        TRY(beam ? beam_attn(a, src, ld_src, s) : decode_attn(a, s));
         TRY(linear(b.a, w.wo, w.bo, b.x, B, d, d, b.x, s));
         float* h2 = last && io.last_ffn_input ? io.last_ffn_input : b.h;
         TRY(layernorm(b.x, d, w.ln2_g, w.ln2_b, h2, d, B, d, eps, nullptr, s));
@@ -398,6 +400,13 @@ int gnnlm_transformer_lm_step(const gnnlm_tlm_t* m, const gnnlm_kv_cache_t* c, c
     GNNLM_DESC(c);
     GNNLM_DESC(io);
     return tlm_step(*m, *c, *io, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int gnnlm_transformer_lm_step_beam(const gnnlm_tlm_t* m, const gnnlm_kv_cache_t* c, const gnnlm_tlm_step_io_t* io, const int32_t* src,
+                                   int64_t ld_src, void* workspace, size_t workspace_bytes, void* stream) {
+    GNNLM_DESC(m);
+    GNNLM_DESC(c);
+    GNNLM_DESC(io);
+    return tlm_step(*m, *c, *io, workspace, workspace_bytes, (hipStream_t)stream, true, src, ld_src);
 }
 
 }  // extern "C"

@@ -180,7 +180,7 @@ def get_parser():
 def check_args(args):
     """Host only, before any device work: what this build does not compute is refused with the flag's name."""
     if args.beam != 1:
-        raise ValueError(f"--beam {args.beam}: beam search is not built (only --beam 1)")
+        raise ValueError(f"--beam {args.beam}: this driver decodes at --beam 1 only; beam search is python -m gnnlm_amd.beam_search")
     if args.sampling_topp > 0:
         raise ValueError("--sampling-topp is not built")
     if args.no_repeat_ngram_size:

@@ -346,6 +346,27 @@ def kv_cache_desc(k, v, lens, done=None, n_bad=None):
     return c
 
 
+def _decode_attn_desc(a, what, q, k_new, v_new, k, v, lens, layer, H, done, n_bad, max_len, out, workspace):
+    """Fill the ``gnnlm_decode_attn_t`` ``a`` (checks, the output and the workspace included) -> (out, workspace, the cache descriptor)."""
+    _f32(q, k_new, v_new, out)
+    _dev(q, k_new, v_new, out)
+    c = kv_cache_desc(k, v, lens, done, n_bad)
+    if q.dim() != 2 or q.shape != (c.B, c.d) or k_new.shape != q.shape or v_new.shape != q.shape or \
+            k_new.stride(0) != q.stride(0) or v_new.stride(0) != q.stride(0):
+        raise ValueError(f"{what}: q, k_new, v_new must be [B, d] with one row stride")
+    if out is None:
+        out = torch.empty(c.B, c.d, device=q.device, dtype=torch.float32)
+    dk = c.d // H
+    need = _lib.lib().gnnlm_decode_attn_workspace_bytes(c.B, H, dk, max_len or c.cap)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 16), device=q.device, dtype=torch.uint8)
+    a.q, a.k_new, a.v_new, a.ld = q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), max(q.stride(0), c.d)
+    a.out, a.ldo = out.data_ptr(), max(out.stride(0), c.d)
+    a.cache, a.layer, a.H, a.dk, a.max_len = c, int(layer), int(H), dk, int(max_len)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    return out, workspace, c
+
+
 def decode_attn(q, k_new, v_new, k, v, lens, layer, H, done=None, n_bad=None, max_len=0, out=None, workspace=None):
     """One new row per sequence against the K/V cache (``gnnlm_decode_attn``): ``q`` / ``k_new`` / ``v_new`` [B, H*dk] f32 sharing one row
     stride (q already scaled), the cache as in :func:`kv_cache_desc` -> ``out`` [B, H*dk].  Row b with ``done[b] == 0`` and
@@ -353,23 +374,8 @@ def decode_attn(q, k_new, v_new, k, v, lens, layer, H, done=None, n_bad=None, ma
     ``0 .. lens[b]``; any other row gets zeros (one outside the range is counted in ``n_bad``).  ``lens`` is not changed.
     ``max_len``: host bound on ``lens[b] + 1`` (0: cap).  d_k in {16, 32, 64, 128}; the result of a row is bit-reproducible and depends
     on that row alone."""
-    _f32(q, k_new, v_new, out)
-    _dev(q, k_new, v_new, out)
-    c = kv_cache_desc(k, v, lens, done, n_bad)
-    if q.dim() != 2 or q.shape != (c.B, c.d) or k_new.shape != q.shape or v_new.shape != q.shape or \
-            k_new.stride(0) != q.stride(0) or v_new.stride(0) != q.stride(0):
-        raise ValueError("decode_attn: q, k_new, v_new must be [B, d] with one row stride")
-    if out is None:
-        out = torch.empty(c.B, c.d, device=q.device, dtype=torch.float32)
-    dk = c.d // H
-    need = _lib.lib().gnnlm_decode_attn_workspace_bytes(c.B, H, dk, max_len or c.cap)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 16), device=q.device, dtype=torch.uint8)
     a = _lib.gnnlm_decode_attn_t()
-    a.q, a.k_new, a.v_new, a.ld = q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), max(q.stride(0), c.d)
-    a.out, a.ldo = out.data_ptr(), max(out.stride(0), c.d)
-    a.cache, a.layer, a.H, a.dk, a.max_len = c, int(layer), int(H), dk, int(max_len)
-    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    out, workspace, _ = _decode_attn_desc(a, "decode_attn", q, k_new, v_new, k, v, lens, layer, H, done, n_bad, max_len, out, workspace)
     call_desc("gnnlm_decode_attn", a)
     return out
 
@@ -404,6 +410,74 @@ def sample_topk(logp, ids, u=None, pad=1, eos=2, done=None, n_bad=None, out=None
     s.n_bad = n_bad.data_ptr() if n_bad is not None else None
     call_desc("gnnlm_sample_topk", s)
     return out, out_logp
+
+
+def _src_table(src, B, cap, what):
+    _dtype(src, torch.int32, "src")
+    if not src.is_cuda or src.dim() != 2 or src.shape[0] != B or src.shape[1] < cap or (src.stride(1) != 1 and src.shape[1] > 1) or \
+            (B > 1 and src.stride(0) < src.shape[1]):
+        raise ValueError(f"{what}: src must be a device int32 [{B}, >= {cap}] table with contiguous rows")
+    return max(src.stride(0), src.shape[1])
+
+
+def beam_attn(q, k_new, v_new, k, v, lens, src, layer, H, done=None, n_bad=None, max_len=0, out=None, workspace=None):
+    """:func:`decode_attn` through a table of cache slots (``gnnlm_beam_attn``): ``src`` int32 [B, >= cap], key row ``u < lens[s]`` of
+    hypothesis s is row u of cache sequence ``src[s, u]``; the new row goes to row ``lens[s]`` of sequence s itself.  Given the same
+    rows in the same order the output is the bits of :func:`decode_attn` on a contiguous cache.  An entry outside [0, B) below
+    ``lens[s]`` is never followed: the row gets zeros and is counted in ``n_bad``."""
+    b = _lib.gnnlm_beam_attn_t()
+    out, workspace, c = _decode_attn_desc(b.a, "beam_attn", q, k_new, v_new, k, v, lens, layer, H, done, n_bad, max_len, out, workspace)
+    b.src, b.ld_src = src.data_ptr(), _src_table(src, c.B, c.cap, "beam_attn")
+    call_desc("gnnlm_beam_attn", b)
+    return out
+
+
+def beam_select(cand_val, cand_id, state, src=None, src_out=None, eos=2, pad=1):
+    """One beam-search step of every sentence (``gnnlm_beam_select``): ``cand_val`` f32 / ``cand_id`` i64 [B * beam_in, N], the sorted
+    top-N of every hypothesis row as :func:`topk_merge` leaves it (``beam_in`` 1 at the first step, ``beam`` afterwards; N >= 2 * beam).
+    ``state``: anything with the attributes ``beam``, ``max_new`` and the device tensors ``score`` f32 [B, beam] (updated in place), ``t`` /
+    ``finished`` / ``fin_n`` int32 [B], ``len`` / ``done`` int32 [B * beam] (the cache's), ``next`` i64 / ``parent`` int32 [B * beam],
+    ``hist_tok`` i64 / ``hist_par`` int32 / ``hist_score`` f32 [B, max_new + 1, beam], ``fin_tok`` i64 / ``fin_cum`` f32 [B, beam, max_new + 1],
+    ``fin_len`` int32 / ``fin_score`` f32 [B, beam] (``beam_search.BeamState`` is one).  ``src`` int32 [B * beam, cap]: the table of cache
+    slots, updated in place (or into ``src_out``).  The rules are the header's; nothing is read back."""
+    _dev(cand_val, cand_id)
+    _f32(cand_val, state.score, state.hist_score, state.fin_cum, state.fin_score)
+    _dtype(cand_id, torch.int64, "cand_id")
+    for name in ("next", "hist_tok", "fin_tok"):
+        _dtype(getattr(state, name), torch.int64, name)
+    for name in ("t", "finished", "fin_n", "len", "done", "parent", "hist_par", "fin_len"):
+        _dtype(getattr(state, name), torch.int32, name)
+    B, beam, T1 = state.t.shape[0], int(state.beam), int(state.max_new) + 1
+    if cand_val.dim() != 2 or cand_id.shape != cand_val.shape or (B and cand_val.shape[0] % B):
+        raise ValueError("beam_select: cand_val / cand_id [B * beam_in, N]")
+    shapes = {"score": (B, beam), "t": (B,), "finished": (B,), "fin_n": (B,), "len": (B * beam,), "done": (B * beam,), "next": (B * beam,),
+              "parent": (B * beam,), "hist_tok": (B, T1, beam), "hist_par": (B, T1, beam), "hist_score": (B, T1, beam),
+              "fin_tok": (B, beam, T1), "fin_cum": (B, beam, T1), "fin_len": (B, beam), "fin_score": (B, beam)}
+    for name, shp in shapes.items():
+        x = getattr(state, name)
+        if tuple(x.shape) != shp or not x.is_cuda or not x.is_contiguous():
+            raise ValueError(f"beam_select: state.{name} must be a contiguous device tensor {shp}")
+    d = _lib.gnnlm_beam_select_t()
+    d.cand_val, d.ld_val = cand_val.data_ptr(), _row_stride(cand_val)
+    d.cand_id, d.ld_id = cand_id.data_ptr(), _row_stride(cand_id)
+    d.B, d.beam, d.beam_in, d.N = B, beam, cand_val.shape[0] // B if B else 1, cand_val.shape[1]
+    d.eos, d.pad, d.max_new = int(eos), int(pad), int(state.max_new)
+    d.score_in = d.score_out = state.score.data_ptr()
+    d.t, d.finished, d.fin_n = state.t.data_ptr(), state.finished.data_ptr(), state.fin_n.data_ptr()
+    d.len, d.done = state.len.data_ptr(), state.done.data_ptr()
+    d.next, d.parent = state.next.data_ptr(), state.parent.data_ptr()
+    d.hist_tok, d.hist_par, d.hist_score = state.hist_tok.data_ptr(), state.hist_par.data_ptr(), state.hist_score.data_ptr()
+    d.fin_tok, d.fin_cum = state.fin_tok.data_ptr(), state.fin_cum.data_ptr()
+    d.fin_len, d.fin_score = state.fin_len.data_ptr(), state.fin_score.data_ptr()
+    if src is not None:
+        dst = src if src_out is None else src_out
+        d.cap = src.shape[1]
+        d.ld_src = _src_table(src, B * beam, d.cap, "beam_select")
+        if _src_table(dst, B * beam, d.cap, "beam_select") != d.ld_src or dst.shape != src.shape:
+            raise ValueError("beam_select: src and src_out must share shape and row stride")
+        d.src_in, d.src_out = src.data_ptr(), dst.data_ptr()
+    call_desc("gnnlm_beam_select", d)
+    return state.next, state.parent
 
 
 def ptr_strided(t):

@@ -101,6 +101,25 @@ class KVCache:
         self.len.zero_(), self.done.zero_(), self.n_bad.zero_()
         self.steps = 0
 
+    def prompt_view(self, beam):
+        """Beam search: the ``B / beam`` sequences ``0, beam, 2 * beam, ..`` of this cache as a cache of their own (the same memory,
+        ``ld_seq`` multiplied by ``beam``) -- what the prompts of ``B / beam`` sentences are prefilled into, once per sentence.  Its
+        ``len`` is a tensor of its own: :meth:`spread` copies it to the ``beam`` slots of every sentence."""
+        if beam < 1 or self.B % beam:
+            raise ValueError(f"prompt_view: the cache's {self.B} sequences are no multiple of beam {beam}")
+        view = object.__new__(KVCache)
+        view.k, view.v = self.k[:, ::beam], self.v[:, ::beam]
+        view.len = torch.zeros(self.B // beam, device=self.k.device, dtype=torch.int32)
+        view.done, view.n_bad = None, self.n_bad
+        view.L, view.B, view.cap, view.d, view.steps = self.L, self.B // beam, self.cap, self.d, 0
+        return view
+
+    def spread(self, view):
+        """After a prefill into :meth:`prompt_view`: every slot of a sentence holds the sentence's ``len``."""
+        beam = self.B // view.B
+        self.len.view(view.B, beam).copy_(view.len.unsqueeze(1).expand(view.B, beam))
+        self.steps = view.steps
+
 
 class TransformerLM:
     def __init__(self, embed, layers, H, act="relu", scale=None, pos=None, learned_pos=False, ln_emb=None, ln_out=None, head=None,
@@ -214,15 +233,18 @@ class TransformerLM:
         than ``cache.cap``."""
         return self._forward(tokens, block_off, want_inner, want_ffn_input, check, cache)
 
-    def step(self, tokens, cache, want_inner=True, want_ffn_input=True, max_len=None):
+    def step(self, tokens, cache, want_inner=True, want_ffn_input=True, max_len=None, src=None):
         """One decoding step (``gnnlm_transformer_lm_step``): ``tokens`` int64 [B] (device), token b is appended to sequence b ->
         ``(x [B, d], extra)`` as :meth:`extract_features` names them -- the mirror of ``extract_features(prev_output_tokens,
         incremental_state=...)``, which looks at the last token only (transformer.py:739-750).  Only enqueues: no host read, no
         synchronisation, no allocation beyond the outputs once the stream's workspace is large enough (the sinusoidal table was sized for
         ``cache.cap`` positions by :meth:`new_cache`, not here) -- a step can be captured in a graph.  ``max_len``: the host bound on ``len + 1`` (default ``cache.steps + 1``; for a captured step, the bound over every replay).
-        A full cache and a position beyond a learned table are refused before any launch."""
+        A full cache and a position beyond a learned table are refused before any launch.
+        ``src`` (beam search): the int32 [B, >= cap] table of cache slots -- key row u of sequence b is row u of sequence ``src[b, u]``
+        (``gnnlm_transformer_lm_step_beam``, every layer through ``gnnlm_beam_attn``); without it the step is what it always was."""
         if tokens.dtype != torch.int64 or tokens.shape != (cache.B,):
             raise TypeError("step: tokens must be int64 [B]")
+        ld_src = ops._src_table(src, cache.B, cache.cap, "step") if src is not None else 0
         if not tokens.is_cuda or not tokens.is_contiguous():
             raise _lib.GnnlmError("gnnlm_amd kernels need contiguous device (HIP) tensors; there is no CPU fallback")
         bound = cache.steps + 1 if max_len is None else int(max_len)
@@ -242,8 +264,12 @@ class TransformerLM:
         L = _lib.lib()
         need = L.gnnlm_transformer_lm_step_workspace_bytes(ctypes.byref(m), ctypes.byref(c), ctypes.byref(io))
         ws = self._workspace(need, tokens.device)
-        _lib.check(L.gnnlm_transformer_lm_step(ctypes.byref(m), ctypes.byref(c), ctypes.byref(io), _lib.ptr(ws), ws.numel(), _lib.stream()),
-                   "gnnlm_transformer_lm_step")
+        if src is None:
+            _lib.check(L.gnnlm_transformer_lm_step(ctypes.byref(m), ctypes.byref(c), ctypes.byref(io), _lib.ptr(ws), ws.numel(), _lib.stream()),
+                       "gnnlm_transformer_lm_step")
+        else:
+            _lib.check(L.gnnlm_transformer_lm_step_beam(ctypes.byref(m), ctypes.byref(c), ctypes.byref(io), ctypes.c_void_p(src.data_ptr()),
+                                                        ld_src, _lib.ptr(ws), ws.numel(), _lib.stream()), "gnnlm_transformer_lm_step_beam")
         cache.steps += 1                                        # (replays of a captured step: the caller adds them)
         extra = {"inner_states": [inner]}
         if ffn_in is not None:

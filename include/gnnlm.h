@@ -1076,6 +1076,80 @@ typedef struct gnnlm_sample_topk {
 int gnnlm_sample_topk(const gnnlm_sample_topk_t* desc, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Beam search on the K/V cache: the decode attention through a per-hypothesis table of cache slots, the step that uses it, and
+ * the selection of the next hypotheses.  Additive to ABI 12: new structs and new entries; nothing above launches anything else.
+ * Replaces: search.BeamSearch.step (fairseq/search.py:49-85), the selection half of SequenceGenerator._generate
+ *           (fairseq/sequence_generator.py:359-497) and reorder_incremental_state (:266-271), which index-selects every layer's
+ *           saved K and V by parent after every step.  Here a hypothesis is a cache sequence ("slot") s; its key row u lives in
+ *           slot src[s][u], so a reorder copies 4 bytes per key and the keys of a shared prompt are held once.
+ * ---------------------------------------------------------------------------------------------- */
+/* gnnlm_decode_attn with the table: `a` exactly as gnnlm_decode_attn takes it (B = a.cache.B hypotheses), src DEVICE int32
+ * [a.cache.B][ld_src], ld_src >= cache.cap.  For u < len[s] key row u of hypothesis s is row u of slot src[s][u]; the new row
+ * len[s] is read from k_new / v_new and written to row len[s] of slot s ITSELF, exactly as gnnlm_decode_attn writes it.  Chunks,
+ * lane groups, unroll, butterfly, the combine launch, the workspace size and the done / n_bad / max_len rules are those of
+ * gnnlm_decode_attn: given the same q, len and the same key and value rows in the same u order, out[s] is the same bits as on a
+ * contiguous cache.  A table entry outside [0, cache.B) at u < len[s] is never followed: the row gets zeros and is counted in
+ * *n_bad (its new row is still appended).  Entries at u >= len[s] are never read.  Refused like gnnlm_decode_attn, and: src NULL
+ * or not 4-byte aligned (with B > 0), ld_src < cache.cap. */
+typedef struct gnnlm_beam_attn {
+    gnnlm_decode_attn_t a;
+    const int32_t* src;  int64_t ld_src;
+} gnnlm_beam_attn_t;
+int gnnlm_beam_attn(const gnnlm_beam_attn_t* desc, void* stream);
+
+/* gnnlm_transformer_lm_step with gnnlm_beam_attn in place of gnnlm_decode_attn in every layer; everything else -- arguments,
+ * workspace (gnnlm_transformer_lm_step_workspace_bytes), refusals, the launches around the attention -- is that entry's.  Only
+ * enqueues. */
+int gnnlm_transformer_lm_step_beam(const gnnlm_tlm_t* model, const gnnlm_kv_cache_t* cache, const gnnlm_tlm_step_io_t* io,
+                                   const int32_t* src, int64_t ld_src, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One beam-search step of every sentence: one launch, one workgroup per sentence b; hypothesis j of b is slot b * beam + j.
+ * Nothing is read back; every count lives on the device, so a captured step replays with fixed pointers.
+ * A sentence with finished[b] != 0 (or t[b] outside [0, max_new]) is left untouched.  Otherwise, with t = t[b]:
+ *   candidates  (j, c), j < beam_in, c < N: value fl32(score_in[b * beam + j] + cand_val[b * beam_in + j, c]) -- one float32 add,
+ *               lprobs.add_(scores) -- token cand_id[b * beam_in + j, c].  Absent: cand_val not finite, or a sum that is not finite.
+ *   order       value descending, then j ascending, then token ascending (the flat index order j * V + token; torch.topk leaves
+ *               ties unspecified).  The first C = min(2 * beam, present) candidates are the step's.
+ *   finalize    scanning the first min(beam, C) in order, a candidate whose token is eos is finalized while fin_n[b] < beam, into
+ *               slot f = fin_n[b]++: fin_tok[b, f, 0 .. t] = its parent's tokens of steps 0 .. t - 1, then eos; fin_cum[b, f, 0 .. t]
+ *               = the parent's cumulative scores, then the value; fin_len[b, f] = t + 1; fin_score[b, f] = the value (raw: the
+ *               length normalisation is the host's).
+ *   survive     the first beam candidates among the C whose token is not eos become hypotheses 0 .. beam - 1: next = token,
+ *               parent = b * beam + j (the slot), score_out = value; the step is recorded as hist_tok / hist_par (j) / hist_score
+ *               [b, t, .] (backpointers: a finalized hypothesis is read back along them).  Hypotheses beyond the survivors are
+ *               dead: next = pad, score_out = -inf, parent = the slot itself -- all their later candidates are absent.
+ *   table       (src_out given) with len = len[b * beam], for u < min(len, cap): src_out[b * beam + j][u] = src_in[parent][u]
+ *               (beam_in == 1: src_in is not read, the entry is b * beam, the slot of the prompt); and if len < cap,
+ *               src_out[b * beam + j][len] = b * beam + j.  src_in == src_out is allowed (a column is read whole before it is
+ *               written), as is score_in == score_out.
+ *   finish      if fin_n[b] == beam or t == max_new (where the host has left only eos): finished[b] = 1 and done[b * beam + j] = 1
+ *               for every j.  Last, t[b] = t + 1.
+ * GNNLM_E_INVALID before anything is launched: beam outside [1, 32], N < 2 * beam, beam_in not 1 or beam, beam_in * N > 8192
+ * (the candidates of a sentence are held in 32 KB of LDS), B < 0, max_new < 0, ld_val / ld_id < N, a NULL cand_val / cand_id /
+ * score_in / score_out / t / finished / len / done / next / parent / hist_* / fin_*, src_out with ld_src < cap or cap < 0 or
+ * (beam_in == beam) without src_in, a misaligned pointer.  B = 0 is accepted and touches nothing. */
+typedef struct gnnlm_beam_select {
+    const float* cand_val;  int64_t ld_val;     /* [B * beam_in, N] sorted, as gnnlm_topk_merge leaves it */
+    const int64_t* cand_id;  int64_t ld_id;     /* [B * beam_in, N] */
+    int32_t B, beam, beam_in, N;
+    int64_t eos, pad;
+    int32_t max_new;                            /* steps are 0 .. max_new */
+    int32_t cap;                                /* table columns: u < cap <= ld_src */
+    const float* score_in;  float* score_out;   /* [B, beam]; beam_in == 1 reads column 0 only */
+    int32_t* t;                                 /* DEVICE [B]: the step counter */
+    int32_t* finished;                          /* DEVICE [B] */
+    const int32_t* len;                         /* DEVICE [B * beam]: the cache's len (slot b * beam is read) */
+    int32_t* done;                              /* DEVICE [B * beam]: the cache's done */
+    int64_t* next;  int32_t* parent;            /* [B * beam] */
+    const int32_t* src_in;  int32_t* src_out;  int64_t ld_src;   /* optional [B * beam][ld_src] */
+    int64_t* hist_tok;  int32_t* hist_par;  float* hist_score;   /* [B][max_new + 1][beam] */
+    int32_t* fin_n;                             /* DEVICE [B]: finalized hypotheses held */
+    int64_t* fin_tok;  float* fin_cum;          /* [B][beam][max_new + 1] */
+    int32_t* fin_len;  float* fin_score;        /* [B][beam] */
+} gnnlm_beam_select_t;
+int gnnlm_beam_select(const gnnlm_beam_select_t* desc, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * kNN-LM on the base LM: the SCORED rows of packed samples (each sample = context rows, then scored rows: --context-window) as
  * one contiguous [n_out, d] query matrix, and / or the same rows scaled to unit length for a cosine index -- one launch instead of
  * one slice per sample + torch.cat + the four-op normalisation.  Additive to ABI 12: a new struct and a new entry.
