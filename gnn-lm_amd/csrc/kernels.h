@@ -27,6 +27,9 @@ int ivfpq_rescore(const gnnlm_ivfpq_rescore_t& d, hipStream_t stream);
 int ivfpq_tables(const gnnlm_ivfpq_tables_t& d, hipStream_t stream);
 int ivfpq_split_payload(int64_t* idx, int64_t n, int label_bits, int32_t val_last, int32_t* out_vals, hipStream_t stream);
 int ivfpq_tau(const gnnlm_ivfpq_tau_t& d, hipStream_t stream);
+// the search's probe selection and final k-selection in kernels of their own (ivfpq_select.hip)
+int ivfpq_select_probes(const gnnlm_ivfpq_select_probes_t& d, hipStream_t stream);
+int ivfpq_select_final(const gnnlm_ivfpq_select_final_t& d, hipStream_t stream);
 
 int gemm_nt(const GemmParams& p, hipStream_t stream);
 // big-tile split-bf16 path (gemm_split.hip): taken by gemm_nt for precision != 0 when the problem fills the chip

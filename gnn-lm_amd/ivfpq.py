@@ -10,7 +10,8 @@ The algorithm is faiss's published IVFADC with residual codes and an OPQ pre-rot
     search: the nprobe lists with the largest <q', c_l>, then the k best scores among their members.
 
 Search path (everything on the device, nothing [n, N]-sized): rotation, coarse scores and look-up tables on the f32
-MFMA GEMM (``gnnlm_gemm_nt``), probe selection and k-selection by ``gnnlm_topk_merge``, the list scan by
+MFMA GEMM (``gnnlm_gemm_nt``), probe selection and k-selection by ``gnnlm_ivfpq_select_probes`` / ``gnnlm_ivfpq_select_final``
+(``gnnlm_topk_merge`` for the float32 scan's rounds and for shapes beyond their limits), the list scan by
 ``gnnlm_ivfpq_scan`` in two rounds -- the best ``dense_probes`` lists of every query are scored in full and give its
 k-th-best threshold, the remaining lists only emit scores above that threshold.
 
@@ -65,11 +66,12 @@ class _LazyStats(dict):
 class _PendingSearch:
     """Handle of ``IVFPQIndex.search_begin``."""
 
-    def __init__(self, index, q, k, query_block, return_vals, stats, val, idx, over, worst, ev, cap):
+    def __init__(self, index, q, k, query_block, return_vals, stats, val, idx, over, worst, ev, cap, split=None):
         self.index, self.q, self.k, self.query_block, self.return_vals = index, q, k, query_block, return_vals
         self.stats = stats                               # work counters of THIS search: index.stats once it has finished
         self.val, self.idx, self.over, self.worst, self.ev = val, idx, over, worst, ev
         self.cap = cap                                   # survivor capacity the buffers of THIS search were allocated with
+        self.split = split                               # (labels | None,) if the final selection has split the payloads already, else None
         self._out = None
 
     def result(self):
@@ -388,7 +390,7 @@ class IVFPQIndex:
         q = q.to(self.device, torch.float32).contiguous()
         stats = self._new_stats(q.shape[0])
         cap = self.cand_cap                                                  # the capacity THIS search's buffers were allocated with
-        val, idx, over = self._search_once(q, k, query_block, self.dense_probes, cap, stats)
+        val, idx, over, split = self._search_once(q, k, query_block, self.dense_probes, cap, stats, return_vals)
         worst = ev = None
         if over is not None:
             if getattr(self, "_worst_host", None) is None:                    # pinned landing slots, one per search in flight (a ring of 8)
@@ -398,14 +400,14 @@ class IVFPQIndex:
             worst.copy_(over.max().reshape(1), non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-        return _PendingSearch(self, q, k, query_block, return_vals, stats, val, idx, over, worst, ev, cap)
+        return _PendingSearch(self, q, k, query_block, return_vals, stats, val, idx, over, worst, ev, cap, split)
 
     def _new_stats(self, n):
         return _LazyStats(pairs=0, survivors=0, candidates=0, queries=n, M=self.M, requeried=0)
 
     def _finish(self, h):
         q, k, query_block = h.q, h.k, h.query_block
-        val, idx, over = h.val, h.idx, h.over
+        val, idx, over, split = h.val, h.idx, h.over, h.split
         cap = h.cap                                                           # (not self.cand_cap: another search in flight may have raised it since)
         while over is not None:
             if h.ev is not None:
@@ -421,18 +423,19 @@ class IVFPQIndex:
             if n_under > self.sample_fail_frac * q.shape[0] and self.threshold_sample > 1:   # the sample does not stand for its lists on this data: stop sampling
                 self.threshold_sample = 1
                 h.stats = self._new_stats(q.shape[0])
-                val, idx, over = self._search_once(q, k, query_block, self.dense_probes, cap, h.stats)
+                val, idx, over, split = self._search_once(q, k, query_block, self.dense_probes, cap, h.stats, h.return_vals)
                 continue
             if (bad.numel() - n_under - n_cols) * 8 > q.shape[0] and cap < (1 << 18):
                 cap *= 2
                 self.cand_cap = max(self.cand_cap, cap)
                 h.stats = self._new_stats(q.shape[0])
-                val, idx, over = self._search_once(q, k, query_block, self.dense_probes, cap, h.stats)
+                val, idx, over, split = self._search_once(q, k, query_block, self.dense_probes, cap, h.stats, h.return_vals)
                 continue
             sub, cap2 = q[bad].contiguous(), cap
             while True:                                                       # every probed list in the threshold / dense round
                 # (the counters describe the main pass: the re-search's go to a throw-away set)
-                v2, i2, o2 = self._search_once(sub, k, query_block, self.nprobe, cap2, _LazyStats())
+                # (`split` of the main pass decides for its rows: the re-searched ones come back in the same state, split once or not at all)
+                v2, i2, o2, s2 = self._search_once(sub, k, query_block, self.nprobe, cap2, _LazyStats(), h.return_vals, fold=split is not None)
                 if o2 is None or int(o2.max().item()) <= cap2:
                     break
                 if cap2 >= (1 << 22):                                         # survivors beyond the capacity would be dropped silently
@@ -440,6 +443,8 @@ class IVFPQIndex:
                                           f"capacity ({cap2}); lower k / nprobe or search this index with scan='f32'")
                 cap2 *= 2
             val[bad], idx[bad] = v2, i2
+            if split is not None and split[0] is not None:
+                split[0][bad] = s2[0]
             dict.__setitem__(h.stats, "requeried", int(bad.numel()))
             break
         self.stats = h.stats
@@ -447,17 +452,29 @@ class IVFPQIndex:
             val = -val                                                        # scores are -distance: squared distances, ascending, +inf padded
         if not self.has_vals:
             return (val, idx, None) if h.return_vals else (val, idx)
+        if split is not None:                                                 # the final selection stored (id, label) itself: no pass over [n, k]
+            return (val, idx, split[0]) if h.return_vals else (val, idx)
         # payload -> (id in place, label): one pass (gnnlm_ivfpq_split_payload) instead of five elementwise torch kernels over [n, k]
         vals = torch.empty(idx.shape, dtype=torch.int32, device=idx.device) if h.return_vals else None
         _lib.call("gnnlm_ivfpq_split_payload", _lib.ptr(idx), idx.numel(), self.LABEL_BITS, self.val_last, _lib.ptr(vals), _lib.stream())
         return (val, idx, vals) if h.return_vals else (val, idx)
 
-    def _search_once(self, q, k, query_block, dense_probes, cap, stats):
+    @staticmethod
+    def _select_on():
+        """GNNLM_IVF_SELECT=0: the selections by gnnlm_topk_merge and the split pass of their own, as before csrc/ivfpq_select.hip (A/B runs)"""
+        return os.environ.get("GNNLM_IVF_SELECT", "1") != "0"
+
+    def _search_once(self, q, k, query_block, dense_probes, cap, stats, return_vals=False, fold=None):
+        """-> (val, idx, over, split).  split: None = idx holds the payloads as the index carries them (``_finish`` splits them if they
+        have labels); (labels | None,) = the final selection has stored ids (and labels [n, k] int32 with ``return_vals``) already."""
         n, dev = q.shape[0], self.device
         nprobe = min(self.nprobe, self.nlist)
         dense = max(1, min(dense_probes, nprobe))
         val = torch.empty(n, k, device=dev, dtype=torch.float32)
         idx = torch.empty(n, k, device=dev, dtype=torch.int64)
+        if fold is None:
+            fold = self.has_vals and self.tiles is not None and k <= 1024 and self._select_on()
+        split = ((torch.empty(n, k, dtype=torch.int32, device=dev) if return_vals else None),) if fold else None
         if query_block is None:                                               # groups of 8 queries per list want many queries per block
             # (the int8 filter groups 8 queries per list: the more queries a block holds, the fuller its groups and the longer a list's bytes
             # stay in the XCD's L2 -- per 8192 queries 12.2 ms in blocks of 8192, 11.4 of 16384, 11.0 of 32768; ~18 GB of temporaries at 32768)
@@ -466,12 +483,24 @@ class IVFPQIndex:
         qb = query_block if self.tiles is not None else max(1, min(query_block, self.score_bytes // max(1, 4 * dense * max(self.max_list, 1))))
         over = None
         for q0 in range(0, n, qb):
-            o = self._search_block(q[q0:q0 + qb], k, val[q0:q0 + qb], idx[q0:q0 + qb], nprobe, dense, cap, stats)
+            bl = None if split is None else (None if split[0] is None else split[0][q0:q0 + qb],)
+            o = self._search_block(q[q0:q0 + qb], k, val[q0:q0 + qb], idx[q0:q0 + qb], nprobe, dense, cap, stats, bl)
             if o is not None:
                 over = o if over is None else torch.cat([over, o])
-        return val, idx, over
+        return val, idx, over, split
 
-    def _search_block(self, qs, k, bv, bi, nprobe, dense, cap, stats):
+    def _select_probes(self, cs, pv, pi, col_bias=None):
+        """the nprobe best lists of every query, best first (csrc/ivfpq_select.hip); shapes it does not take go to gnnlm_topk_merge"""
+        if not self._select_on() or cs.shape[1] > 4096 or pv.shape[1] > 64:
+            return ops.topk_merge(cs, pv, pi, largest=True, init=True, col_bias=col_bias)
+        d = _lib.gnnlm_ivfpq_select_probes_t()
+        d.scores, d.ld, d.n, d.ncols = cs.data_ptr(), cs.stride(0), cs.shape[0], cs.shape[1]
+        if col_bias is not None:
+            d.col_bias = col_bias.data_ptr()
+        d.k, d.largest, d.out_val, d.out_id = pv.shape[1], 1, pv.data_ptr(), pi.data_ptr()
+        _lib.call_desc("gnnlm_ivfpq_select_probes", d)
+
+    def _search_block(self, qs, k, bv, bi, nprobe, dense, cap, stats, split=None):
         dev = self.device
         nq = qs.shape[0]
         qr = ops.gemm_nt(qs, self.R)                                            # q' = R q
@@ -482,10 +511,10 @@ class IVFPQIndex:
         pv = torch.empty(nq, nprobe, device=dev, dtype=torch.float32)
         pi = torch.empty(nq, nprobe, device=dev, dtype=torch.int64)
         if self.metric == "l2":                                                 # the nprobe NEAREST lists: argmax <q', c> - |c|^2 / 2
-            ops.topk_merge(cs, pv, pi, largest=True, init=True, col_bias=-0.5 * self.coarse_n2)
+            self._select_probes(cs, pv, pi, col_bias=-0.5 * self.coarse_n2)
             pv = (2.0 * pv - (qr ** 2).sum(1, keepdim=True)).contiguous()      # the list's bias: -|q' - c_l|^2
         else:
-            ops.topk_merge(cs, pv, pi, largest=True, init=True)                 # the nprobe best lists, best first
+            self._select_probes(cs, pv, pi)                                     # the nprobe best lists, best first
         stats.add("pairs", lambda pi=pi: (self.list_off[1:] - self.list_off[:-1])[pi.clamp(min=0)].masked_fill(pi < 0, 0).sum().double())
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)                       # (lut / tables were allocated on THIS stream: no record_stream needed)
@@ -496,7 +525,7 @@ class IVFPQIndex:
         ci = torch.empty(nq, ccap, device=dev, dtype=torch.int64)
         cc = torch.zeros(nq, device=dev, dtype=torch.int32)
         if self.tiles is not None:
-            return self._search_block_mfma(k, bv, bi, nprobe, dense, cs, pv, pi, lut, tables, cv, ci, cc, cap, stats)
+            return self._search_block_mfma(k, bv, bi, nprobe, dense, cs, pv, pi, lut, tables, cv, ci, cc, cap, stats, split)
         lut_s = lut
         if self.packed_codes is not None:
             lut_s = torch.empty_like(lut)
@@ -568,7 +597,7 @@ class IVFPQIndex:
                 _lib.call("gnnlm_ivfpq_quantize_lut", _lib.ptr(lut), lut.stride(0), nq, self.M, _lib.ptr(tables[0]), _lib.ptr(tables[1]), _lib.stream())
         return lut, tables, side
 
-    def _search_block_mfma(self, k, bv, bi, nprobe, dense, cs, pv, pi, lut, tables, cv, ci, cc, cap, stats):
+    def _search_block_mfma(self, k, bv, bi, nprobe, dense, cs, pv, pi, lut, tables, cv, ci, cc, cap, stats, split=None):
         """M = 64: everything on the int8 matrix cores (csrc/ivfpq_mfma.hip).  (1) threshold pass: histograms of the integer sums of the
         first `dense` lists -> a lower bound tau of the query's k-th best score (no per-key output, no selection); (2) filter: every probed
         list, keys whose integer sum can reach tau; (3) exact float32 scores of the survivors, score > tau -> candidates;
@@ -612,8 +641,20 @@ class IVFPQIndex:
         stats.add("candidates", lambda cc=cc: cc.sum().double())
         if getattr(self, "keep_candidates", False):
             self.last_candidates = (cv, ci, cc, tau)
-        ops.topk_merge(cv, bv, bi, ids=ci, largest=True, init=True, row_ncols=cc.clamp(max=ccap))
-        over = sc                                                              # every candidate is a survivor: sc >= cc
+        if k <= 1024 and (split is not None or self._select_on()):
+            # the k best candidates, ranked inside value bins (csrc/ivfpq_select.hip); with `split` the payloads leave as (id, label)
+            rn = cc.clamp(max=ccap)
+            f = _lib.gnnlm_ivfpq_select_final_t()
+            f.cand_val, f.ld_val, f.cand_id, f.ld_id = cv.data_ptr(), cv.stride(0), ci.data_ptr(), ci.stride(0)
+            f.row_ncols, f.n, f.cap, f.k, f.out_val, f.out_id = rn.data_ptr(), nq, ccap, k, bv.data_ptr(), bi.data_ptr()
+            if split is not None:
+                f.label_bits, f.val_last = self.LABEL_BITS, self.val_last
+                if split[0] is not None:
+                    f.out_vals = split[0].data_ptr()
+            _lib.call_desc("gnnlm_ivfpq_select_final", f)
+        else:
+            ops.topk_merge(cv, bv, bi, ids=ci, largest=True, init=True, row_ncols=cc.clamp(max=ccap))
+        over = sc                                                             # every candidate is a survivor: sc >= cc
         if ccap < cap:                                                         # more candidates than columns: an overflow like any other
             over = torch.where(cc > ccap, torch.full_like(sc, self.COLUMNS), over)
         if S > 1:                                                              # the sampled threshold's proof: k candidates above it (or every key there is)

@@ -714,6 +714,37 @@ int gnnlm_ivfpq_tau(const gnnlm_ivfpq_tau_t* desc, void* stream);
 /* ABI 7.  Results of a search over an index that carries labels (payload = id << label_bits | label, -1 = no result): idx [n]
  * -> the ids in place, out_vals [n] (optional) the labels, `val_last` where there is no result (numpy's vals[-1], knn_model.py:198) */
 int gnnlm_ivfpq_split_payload(int64_t* idx, int64_t n, int32_t label_bits, int32_t val_last, int32_t* out_vals, void* stream);
+/* The two k-selections of the search in kernels of their own (csrc/ivfpq_select.hip).  Each returns bit for bit what
+ * gnnlm_topk_merge returns with init = 1 on the same operands (the rules of gnnlm_topk_t: value rounded after each step, an entry
+ * is absent if its id is < 0 or its value is NaN or the worst infinity, better value first, then ascending id, -0 == +0, padding
+ * id -1 with -inf / +inf); shapes outside the limits are refused with nothing written and the caller uses gnnlm_topk_merge.
+ *
+ * Probe selection: the k <= 64 best of ncols <= 4096 columns per row, value = scores[r, c] + col_bias[c] (col_bias optional: the
+ * L2 route's -|c|^2 / 2), id = c.  One wave per row, the row in registers, no barrier.  ncols = 0 writes the padding (scores may be
+ * NULL), n = 0 touches nothing. */
+typedef struct gnnlm_ivfpq_select_probes {
+    const float* scores;  int64_t ld;     /* [n, ncols], row stride ld elements */
+    int64_t n;  int32_t ncols;            /* ncols <= 4096 */
+    const float* col_bias;                /* optional [ncols] */
+    int32_t k;                            /* <= 64 */
+    int32_t largest;                      /* 1: the k largest values, 0: the k smallest */
+    float* out_val;  int64_t* out_id;     /* [n, k] */
+} gnnlm_ivfpq_select_probes_t;
+int gnnlm_ivfpq_select_probes(const gnnlm_ivfpq_select_probes_t* desc, void* stream);
+/* Final selection: the k <= 1024 largest of a ragged candidate row -- row r holds min(cap, row_ncols[r]) candidates (row_ncols NULL:
+ * cap; <= 0: none), cap <= 16384, value cand_val[r, c], id cand_id[r, c] (a 64-bit payload; payloads need not be unique within a
+ * row: equal (value, payload) pairs are interchangeable).  With label_bits > 0 the payload split of gnnlm_ivfpq_split_payload is
+ * part of the store: out_id gets payload >> label_bits, out_vals (optional, [n, k]) payload & (2^label_bits - 1), padding slots
+ * id -1 and val_last; label_bits = 0 stores the payloads as they are. */
+typedef struct gnnlm_ivfpq_select_final {
+    const float* cand_val;  int64_t ld_val;   /* [n, cap] */
+    const int64_t* cand_id;  int64_t ld_id;   /* [n, cap] */
+    const int32_t* row_ncols;                 /* optional [n] */
+    int64_t n;  int32_t cap;  int32_t k;
+    float* out_val;  int64_t* out_id;         /* [n, k] */
+    int32_t label_bits;  int32_t val_last;  int32_t* out_vals;
+} gnnlm_ivfpq_select_final_t;
+int gnnlm_ivfpq_select_final(const gnnlm_ivfpq_select_final_t* desc, void* stream);
 typedef struct gnnlm_ivfpq_rescore {
     const uint8_t* codes;  const int64_t* payload;    /* [N, M] list-ordered codes, [N] what a candidate carries (key id, or id << 24 | label) */
     int32_t M;                                        /* 64 */
