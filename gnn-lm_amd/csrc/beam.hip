@@ -8,7 +8,7 @@
 // the smaller token wherever it stood.  Lane 0 scans the drawn list (at most 64 entries) for the finalized and the surviving
 // hypotheses; the histories are backpointers, walked only when a hypothesis is finalized; the table of cache slots is permuted
 // column by column, a column read whole (LDS, the staging area again) before it is written, so it may be updated in place.
-#include "kernels.h"
+#include "host.h"
 
 namespace gnnlm {
 namespace {
@@ -197,9 +197,6 @@ int beam_select(const gnnlm_beam_select_t& d, hipStream_t stream) {
 using namespace gnnlm;
 
 extern "C" int gnnlm_beam_select(const gnnlm_beam_select_t* d, void* stream) {
-    if (!d) {
-        set_error("invalid argument: null descriptor");
-        return E_INVALID;
-    }
+    GNNLM_DESC(d);
     return beam_select(*d, (hipStream_t)stream);
 }

@@ -8,7 +8,7 @@
 // (each lane 4 columns) and keeps its own running (maximum, sum, accumulator) over the keys g, g + G, ... of the chunk; the groups
 // are merged once at the end of the chunk in a fixed butterfly.  The chunk's triple goes to the workspace and a second launch
 // combines the chunks of a (b, h) in ascending order -- no float atomics, so a row's bits depend on that row alone.
-#include "kernels.h"
+#include "host.h"
 
 namespace gnnlm {
 namespace {
@@ -348,17 +348,11 @@ size_t gnnlm_decode_attn_workspace_bytes(int32_t B, int32_t H, int32_t dk, int32
     return decode_attn_workspace_bytes(B, H, dk, max_len);
 }
 int gnnlm_decode_attn(const gnnlm_decode_attn_t* d, void* stream) {
-    if (!d) {
-        set_error("invalid argument: null descriptor");
-        return E_INVALID;
-    }
+    GNNLM_DESC(d);
     return decode_attn(*d, (hipStream_t)stream);
 }
 int gnnlm_beam_attn(const gnnlm_beam_attn_t* d, void* stream) {
-    if (!d) {
-        set_error("invalid argument: null descriptor");
-        return E_INVALID;
-    }
+    GNNLM_DESC(d);
     return beam_attn(d->a, d->src, d->ld_src, (hipStream_t)stream);
 }
 

@@ -28,9 +28,8 @@
 //                    atomics, the same bits on every call -- and its at most k label columns overwritten from lm_logp.
 //                    A label outside [0, V) (and a row outside the shard / store, as for gnnlm_knn_interp) takes part in the
 //                    softmax's denominator but writes nothing.
-#include <algorithm>
 
-#include "kernels.h"
+#include "host.h"
 
 namespace gnnlm {
 namespace {
@@ -77,18 +76,6 @@ int head_finish(const FinishArgs& a, int64_t rows, hipStream_t s) {
     return OK;
 }
 
-struct Carve {
-    char* base;
-    size_t off = 0;
-    explicit Carve(void* b) : base(reinterpret_cast<char*>(b)) {}
-    template <class T>
-    T* take(int64_t n) {
-        off = (off + 255) & ~size_t(255);
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += (size_t)std::max<int64_t>(n, 0) * sizeof(T);
-        return p;
-    }
-};
 
 // ---- adaptive head ----
 struct AdaptiveBufs { float *head, *xi, *lse; };
@@ -96,7 +83,7 @@ int64_t pad4(int64_t v) { return (v + 3) & ~3ll; }
 size_t carve_adaptive(const gnnlm_adaptive_softmax_t& w, int64_t chunk, void* ws, AdaptiveBufs& b) {
     int64_t max_dim = 0;
     for (int i = 1; i < w.n_bands; ++i) max_dim = std::max<int64_t>(max_dim, w.dim[i]);
-    Carve c(ws);
+    Carver c(ws);
     b.head = c.take<float>(chunk * pad4((int64_t)w.cutoff[0] + w.n_bands - 1));
     b.xi = c.take<float>(chunk * max_dim);
     b.lse = c.take<float>(chunk * w.n_bands);
@@ -146,7 +133,6 @@ int adaptive_dense_impl(const gnnlm_adaptive_softmax_t& w, const float* x, int64
     GemmPrecisionScope prec_scope(w.gemm_precision);
     const int nt = w.n_bands - 1, head_n = w.cutoff[0] + nt;
     const int64_t ld_head = pad4(head_n);
-    int rc;
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t rows = std::min(chunk, n - r0);
         const float* xc = x + r0 * ldx;
@@ -155,32 +141,32 @@ int adaptive_dense_impl(const gnnlm_adaptive_softmax_t& w, const float* x, int64
             GemmParams g{};
             g.A = xc; g.lda = ldx; g.W = w.head_w; g.ldw = w.d; g.C = b.head; g.ldc = ld_head;
             g.M = (int)rows; g.N = head_n; g.K = w.d;
-            if ((rc = gemm_nt(g, s)) != OK) return rc;
+            GNNLM_TRY(gemm_nt(g, s));
         }
-        if ((rc = row_lse_pick(b.head, ld_head, rows, nullptr, head_n, nullptr, b.lse, nullptr, s)) != OK) return rc;
+        GNNLM_TRY(row_lse_pick(b.head, ld_head, rows, nullptr, head_n, nullptr, b.lse, nullptr, s));
         for (int i = 1; i < w.n_bands; ++i) {   // tails (adaptive_softmax.py:91-115,199-203), every row
             const int size = w.cutoff[i] - w.cutoff[i - 1];
             GemmParams g{};
             g.A = xc; g.lda = ldx; g.W = w.proj_t[i]; g.ldw = w.d; g.C = b.xi; g.ldc = w.dim[i];
             g.M = (int)rows; g.N = w.dim[i]; g.K = w.d;
-            if ((rc = gemm_nt(g, s)) != OK) return rc;
+            GNNLM_TRY(gemm_nt(g, s));
             GemmParams t{};
             t.A = b.xi; t.lda = w.dim[i]; t.W = w.emb[i]; t.ldw = w.dim[i]; t.C = oc + w.cutoff[i - 1]; t.ldc = ldo;
             t.M = (int)rows; t.N = size; t.K = w.dim[i];
-            if ((rc = gemm_nt(t, s)) != OK) return rc;
-            if ((rc = row_lse_pick(oc + w.cutoff[i - 1], ldo, rows, nullptr, size, nullptr, b.lse + (int64_t)i * chunk, nullptr, s)) != OK) return rc;
+            GNNLM_TRY(gemm_nt(t, s));
+            GNNLM_TRY(row_lse_pick(oc + w.cutoff[i - 1], ldo, rows, nullptr, size, nullptr, b.lse + (int64_t)i * chunk, nullptr, s));
         }
         FinishArgs f{};
         f.head = b.head; f.ld_head = ld_head; f.out = oc; f.ldo = ldo; f.lse = b.lse; f.ld_lse = chunk; f.n_bands = w.n_bands;
         for (int i = 0; i < w.n_bands; ++i) f.cutoff[i] = w.cutoff[i];
-        if ((rc = head_finish(f, rows, s)) != OK) return rc;
+        GNNLM_TRY(head_finish(f, rows, s));
     }
     return OK;
 }
 
 // ---- plain head ----
 size_t carve_plain(int64_t chunk, void* ws, float*& lse) {
-    Carve c(ws);
+    Carver c(ws);
     lse = c.take<float>(chunk);
     return c.off + 256;
 }
@@ -203,7 +189,6 @@ int plain_dense_impl(const gnnlm_dense_softmax_t& w, const float* x, int64_t ldx
     chunk = std::max<int64_t>(1, std::min(chunk, OFFSET_CAP / std::max(ldo, ldx)));
     carve_plain(chunk, ws, lse);
     GemmPrecisionScope prec_scope(w.gemm_precision);
-    int rc;
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t rows = std::min(chunk, n - r0);
         float* oc = out + r0 * ldo;
@@ -211,12 +196,12 @@ int plain_dense_impl(const gnnlm_dense_softmax_t& w, const float* x, int64_t ldx
         g.A = x + r0 * ldx; g.lda = ldx; g.W = w.w; g.ldw = w.ldw; g.C = oc; g.ldc = ldo;
         if (w.bias) { g.bias = w.bias; g.bias_mode = 1; }       // xl_bias: added in f32 under every precision
         g.M = (int)rows; g.N = w.vocab; g.K = w.d;
-        if ((rc = gemm_nt(g, s)) != OK) return rc;
-        if ((rc = row_lse_pick(oc, ldo, rows, nullptr, w.vocab, nullptr, lse, nullptr, s)) != OK) return rc;
+        GNNLM_TRY(gemm_nt(g, s));
+        GNNLM_TRY(row_lse_pick(oc, ldo, rows, nullptr, w.vocab, nullptr, lse, nullptr, s));
         FinishArgs f{};
         f.head = oc; f.ld_head = ldo; f.out = oc; f.ldo = ldo; f.lse = lse; f.ld_lse = chunk; f.n_bands = 1;
         f.cutoff[0] = w.vocab;
-        if ((rc = head_finish(f, rows, s)) != OK) return rc;
+        GNNLM_TRY(head_finish(f, rows, s));
     }
     return OK;
 }
@@ -411,12 +396,6 @@ int row_rank(const float* logp, int64_t ld, int64_t n, int V, const int64_t* tar
 }  // namespace gnnlm
 
 using namespace gnnlm;
-
-#define GNNLM_DESC(d)                                       \
-    if (!(d)) {                                             \
-        set_error("invalid argument: null descriptor");     \
-        return E_INVALID;                                   \
-    }
 
 extern "C" {
 

@@ -40,10 +40,9 @@
 //    logits to HBM.  Rows are cut into chunks so that the logits of a chunk stay below LOGITS_CAP = 64 MiB (a quarter of the
 //    256 MiB Infinity Cache: the row pass re-reads what the GEMM just wrote without going to HBM); a caller may hand in less
 //    workspace, down to gnnlm_dense_workspace_bytes_min (128-row chunks).
-#include <algorithm>
 #include <cstdlib>
 
-#include "kernels.h"
+#include "host.h"
 
 namespace gnnlm {
 namespace {
@@ -299,18 +298,6 @@ __global__ void dense_finish_kernel(const float* picked, const float* lse, const
     }
 }
 
-struct Carve {
-    char* base;
-    size_t off = 0;
-    explicit Carve(void* b) : base(reinterpret_cast<char*>(b)) {}
-    template <class T>
-    T* take(int64_t n) {
-        off = (off + 255) & ~size_t(255);
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += (size_t)std::max<int64_t>(n, 0) * sizeof(T);
-        return p;
-    }
-};
 struct GeneralBufs {
     int32_t* pick;
     float *picked, *lse, *part, *logits;
@@ -318,7 +305,7 @@ struct GeneralBufs {
 int64_t logits_ld(int vocab) { return ((int64_t)vocab + 3) & ~3ll; }
 // the workspace of the general route for chunks of `chunk` rows (with a bias) -> bytes
 size_t carve_general(const gnnlm_dense_softmax_t& w, int64_t n, int64_t chunk, void* ws, GeneralBufs& b) {
-    Carve c(ws);
+    Carver c(ws);
     b.pick = c.take<int32_t>(n);
     b.picked = c.take<float>(n);
     b.lse = c.take<float>(n);
@@ -356,8 +343,7 @@ int dense_validate(const gnnlm_dense_softmax_t& w) {
 
 int dense_impl(const gnnlm_dense_softmax_t& w, const float* x, int64_t ldx, const int64_t* target, int64_t n, float* lm_logp,
                void* ws, size_t ws_bytes, hipStream_t s) {
-    const int rc = dense_validate(w);
-    if (rc != OK) return rc;
+    GNNLM_TRY(dense_validate(w));
     GNNLM_REQUIRE(n >= 0 && n < (1ll << 31), "dense: bad row count");
     const int route = dense_route(w);
     GeneralBufs b{};
@@ -390,15 +376,14 @@ int dense_impl(const gnnlm_dense_softmax_t& w, const float* x, int64_t ldx, cons
     const unsigned blocks = (unsigned)cdiv(n, 256);
     hipLaunchKernelGGL(dense_pick_kernel, dim3(blocks), dim3(256), 0, s, target, n, w.vocab, b.pick);
     GNNLM_LAUNCH_CHECK();
-    int rc2;
     if (!w.bias) {                                      // the adaptive head's own path: logits reduced in the epilogue, never written
         GemmParams g{};
         g.A = x; g.lda = ldx; g.W = w.w; g.ldw = w.ldw;
         g.lse_part = b.part; g.lse_pick = b.pick; g.lse_picked = b.picked;
         g.M = (int)n; g.N = w.vocab; g.K = w.d;
-        if (n >= 1024) g.tile_order = 2 + 4;            // as the adaptive head (api.hip): bands of 4 m-tiles
-        if ((rc2 = gemm_nt(g, s)) != OK) return rc2;
-        if ((rc2 = lse_reduce(b.part, 2 * (int)cdiv(w.vocab, 128), n, nullptr, b.lse, s)) != OK) return rc2;
+        if (n >= 1024) g.tile_order = 2 + 4;            // as the adaptive head (adaptive_logp.hip): bands of 4 m-tiles
+        GNNLM_TRY(gemm_nt(g, s));
+        GNNLM_TRY(lse_reduce(b.part, 2 * (int)cdiv(w.vocab, 128), n, nullptr, b.lse, s));
     } else {                                            // xl_bias: logits of a chunk of rows through the workspace
         const int64_t ldc = logits_ld(w.vocab);
         for (int64_t r0 = 0; r0 < n; r0 += chunk) {
@@ -407,8 +392,8 @@ int dense_impl(const gnnlm_dense_softmax_t& w, const float* x, int64_t ldx, cons
             g.A = x + r0 * ldx; g.lda = ldx; g.W = w.w; g.ldw = w.ldw;
             g.C = b.logits; g.ldc = ldc; g.bias = w.bias; g.bias_mode = 1;
             g.M = (int)rows; g.N = w.vocab; g.K = w.d;
-            if ((rc2 = gemm_nt(g, s)) != OK) return rc2;
-            if ((rc2 = row_lse_pick(b.logits, ldc, rows, nullptr, w.vocab, b.pick + r0, b.lse + r0, b.picked + r0, s)) != OK) return rc2;
+            GNNLM_TRY(gemm_nt(g, s));
+            GNNLM_TRY(row_lse_pick(b.logits, ldc, rows, nullptr, w.vocab, b.pick + r0, b.lse + r0, b.picked + r0, s));
         }
     }
     hipLaunchKernelGGL(dense_finish_kernel, dim3(blocks), dim3(256), 0, s, b.picked, b.lse, target, n, w.vocab, lm_logp);
@@ -435,10 +420,7 @@ size_t gnnlm_dense_workspace_bytes(const gnnlm_dense_softmax_t* w, int64_t n) { 
 size_t gnnlm_dense_workspace_bytes_min(const gnnlm_dense_softmax_t* w, int64_t n) { return dense_workspace(w, n, true); }
 int gnnlm_dense_target_logp(const gnnlm_dense_softmax_t* w, const float* x, int64_t ldx, const int64_t* target, int64_t n,
                             float* lm_logp, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!w) {
-        set_error("invalid argument: null descriptor");
-        return E_INVALID;
-    }
+    GNNLM_DESC(w);
     return dense_impl(*w, x, ldx, target, n, lm_logp, workspace, workspace_bytes, (hipStream_t)stream);
 }
 

@@ -4,7 +4,7 @@
 //
 // Memory-bound row kernel: one wave per output row, 16-byte accesses, the row held in registers between the sum and the scaling
 // (d <= 1024; longer rows are read a second time, from L2).
-#include "kernels.h"
+#include "host.h"
 
 namespace gnnlm {
 namespace {
@@ -160,9 +160,6 @@ int pack_rows(const gnnlm_pack_rows_t& q, hipStream_t stream) {
 using namespace gnnlm;
 
 extern "C" int gnnlm_pack_rows(const gnnlm_pack_rows_t* desc, void* stream) {
-    if (!desc) {
-        set_error("invalid argument: null descriptor");
-        return E_INVALID;
-    }
+    GNNLM_DESC(desc);
     return pack_rows(*desc, (hipStream_t)stream);
 }

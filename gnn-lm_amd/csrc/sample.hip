@@ -4,7 +4,7 @@
 // One wave per row.  Lane l owns the run of `per` = ceil(N / 64) consecutive columns [l * per, (l + 1) * per); the prefix sum is
 // c_j = (the wave scan of the runs of the lanes below l) + (the run's columns up to j, summed in ascending order), and c_{N-1} the
 // scan's last value.  Should u * c_{N-1} round up to c_{N-1} itself, the last column with mass is taken.
-#include "kernels.h"
+#include "host.h"
 
 namespace gnnlm {
 namespace {
@@ -93,9 +93,6 @@ int sample_topk(const gnnlm_sample_topk_t& d, hipStream_t stream) {
 using namespace gnnlm;
 
 extern "C" int gnnlm_sample_topk(const gnnlm_sample_topk_t* d, void* stream) {
-    if (!d) {
-        set_error("invalid argument: null descriptor");
-        return E_INVALID;
-    }
+    GNNLM_DESC(d);
     return sample_topk(*d, (hipStream_t)stream);
 }

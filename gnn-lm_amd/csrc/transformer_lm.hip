@@ -4,9 +4,7 @@
 //
 // New device code: two row kernels.  Everything heavy is an entry point the library already has (gemm_nt with bias / residual,
 // causal_attn_varlen, layernorm, gelu); the orchestrator only enqueues them on the caller's stream.
-#include "kernels.h"
-
-#include <algorithm>
+#include "host.h"
 
 namespace gnnlm {
 namespace {
@@ -118,12 +116,6 @@ __global__ __launch_bounds__(256) void relu1_kernel(float* x, int64_t n) {
     if (i < n) x[i] = relu1(x[i]);
 }
 
-#define TRY(x)                 \
-    do {                       \
-        int _rc = (x);         \
-        if (_rc != OK) return _rc; \
-    } while (0)
-
 int check_embed(const gnnlm_lm_embed_t& e, const gnnlm_ragged_t& rg) {
     GNNLM_REQUIRE(rg.n_tok >= 0 && rg.n_tok < (1ll << 31) && rg.n_blocks >= 0, "lm_embed: bad block table");
     GNNLM_REQUIRE(e.d > 0 && e.d % 4 == 0, "lm_embed: d % 4 != 0");
@@ -153,19 +145,16 @@ int launch_embed(const gnnlm_lm_embed_t& e, const gnnlm_ragged_t& rg, hipStream_
 }
 
 struct TlmBufs { float *x, *h, *a, *wide; };
+void take_tlm(const gnnlm_tlm_t& m, int64_t n, Carver& c, TlmBufs& b) {
+    b.x = c.take<float>(n * m.d);
+    b.h = c.take<float>(n * m.d);
+    b.a = c.take<float>(n * m.d);
+    b.wide = c.take<float>(n * std::max<int64_t>(3 * (int64_t)m.d, m.ffn));      // q | k | v of the attention block, then the fc1 output
+}
 size_t carve_tlm(const gnnlm_tlm_t& m, int64_t n, char* base, TlmBufs& b) {
-    size_t off = 0;
-    auto take = [&](int64_t elems) {
-        off = (off + 255) & ~size_t(255);
-        float* ptr = base ? reinterpret_cast<float*>(base + off) : nullptr;
-        off += (size_t)elems * sizeof(float);
-        return ptr;
-    };
-    b.x = take(n * m.d);
-    b.h = take(n * m.d);
-    b.a = take(n * m.d);
-    b.wide = take(n * std::max<int64_t>(3 * (int64_t)m.d, m.ffn));      // q | k | v of the attention block, then the fc1 output
-    return off + 256;
+    Carver c(base);
+    take_tlm(m, n, c, b);
+    return c.off + 256;
 }
 
 int check_tlm(const gnnlm_tlm_t& m) {
@@ -195,17 +184,8 @@ gnnlm_lm_embed_t embed_of(const gnnlm_tlm_t& m, const gnnlm_tlm_io_t& io, float*
     return e;
 }
 
-int linear(const float* A, const float* W, const float* bias, float* C, int64_t M, int N, int K, const float* R, hipStream_t s) {
-    GemmParams g{};
-    g.A = A; g.lda = K; g.W = W; g.ldw = K; g.C = C; g.ldc = N;
-    g.bias = bias; g.bias_mode = 1;
-    g.R = R; g.ldr = N;
-    g.M = (int)M; g.N = N; g.K = K;
-    return gemm_nt(g, s);
-}
-
 int check_tlm_cache(const gnnlm_tlm_t& m, const gnnlm_kv_cache_t& c) {
-    TRY(check_kv_cache(c));
+    GNNLM_TRY(check_kv_cache(c));
     GNNLM_REQUIRE(c.d == m.d && c.L == m.L, "transformer_lm: the cache's d / L differ from the model's");
     return OK;
 }
@@ -213,10 +193,10 @@ int check_tlm_cache(const gnnlm_tlm_t& m, const gnnlm_kv_cache_t& c) {
 // cache != nullptr (gnnlm_transformer_lm_prefill): block b is sequence b, its K' / V' rows are copied into the cache after each
 // layer's q|k|v GEMM and len is set at the end; the launches of the forward itself are the same either way
 int tlm_forward(const gnnlm_tlm_t& m, const gnnlm_tlm_io_t& io, void* ws, size_t ws_bytes, hipStream_t s, const gnnlm_kv_cache_t* cache = nullptr) {
-    TRY(check_tlm(m));
+    GNNLM_TRY(check_tlm(m));
     const gnnlm_ragged_t& rg = io.blocks;
     if (cache) {
-        TRY(check_tlm_cache(m, *cache));
+        GNNLM_TRY(check_tlm_cache(m, *cache));
         GNNLM_REQUIRE(rg.n_blocks == cache->B, "transformer_lm_prefill: n_blocks != the cache's B");
         GNNLM_REQUIRE(io.max_len >= 0 && io.max_len <= cache->cap, "transformer_lm_prefill: a block is longer than the cache (max_len > cap)");
     }
@@ -225,7 +205,7 @@ int tlm_forward(const gnnlm_tlm_t& m, const gnnlm_tlm_io_t& io, void* ws, size_t
     const float eps = m.ln_eps == 0.f ? 1e-5f : m.ln_eps;
     {
         const gnnlm_lm_embed_t probe = embed_of(m, io, reinterpret_cast<float*>(ws));
-        TRY(check_embed(probe, rg));
+        GNNLM_TRY(check_embed(probe, rg));
     }
     if (n == 0) return OK;
     GNNLM_REQUIRE(io.tokens && io.out, "transformer_lm: tokens / out missing");
@@ -237,48 +217,49 @@ int tlm_forward(const gnnlm_tlm_t& m, const gnnlm_tlm_io_t& io, void* ws, size_t
     carve_tlm(m, n, reinterpret_cast<char*>(ws), b);
     GemmPrecisionScope prec_scope(m.precision);
 
-    TRY(launch_embed(embed_of(m, io, b.x), rg, s));
-    if (m.ln_emb_g) TRY(layernorm(b.x, d, m.ln_emb_g, m.ln_emb_b, b.x, d, n, d, eps, nullptr, s));
+    GNNLM_TRY(launch_embed(embed_of(m, io, b.x), rg, s));
+    if (m.ln_emb_g) GNNLM_TRY(layernorm(b.x, d, m.ln_emb_g, m.ln_emb_b, b.x, d, n, d, eps, nullptr, s));
     for (int l = 0; l < m.L; ++l) {
         const gnnlm_tlm_layer_t& w = m.layers[l];
         const bool last = l == m.L - 1;
         // self-attention block: x += out_proj(attn(LN(x)))
-        TRY(layernorm(b.x, d, w.ln1_g, w.ln1_b, b.h, d, n, d, eps, nullptr, s));
-        TRY(linear(b.h, w.wqkv, w.bqkv, b.wide, n, 3 * d, d, nullptr, s));
-        if (cache) TRY(kv_cache_fill(b.wide, 3 * (int64_t)d, *cache, l, rg, (int)io.max_len, s));
-        TRY(causal_attn_varlen(b.wide, b.wide + d, b.wide + 2 * d, 3 * (int64_t)d, b.a, d, rg, m.H, dk, 0, s));
-        TRY(linear(b.a, w.wo, w.bo, b.x, n, d, d, b.x, s));
+        GNNLM_TRY(layernorm(b.x, d, w.ln1_g, w.ln1_b, b.h, d, n, d, eps, nullptr, s));
+        GNNLM_TRY(linear(b.h, d, w.wqkv, w.bqkv, b.wide, n, 3 * d, d, nullptr, ALPHA_UNSET, s));
+        if (cache) GNNLM_TRY(kv_cache_fill(b.wide, 3 * (int64_t)d, *cache, l, rg, (int)io.max_len, s));
+        GNNLM_TRY(causal_attn_varlen(b.wide, b.wide + d, b.wide + 2 * d, 3 * (int64_t)d, b.a, d, rg, m.H, dk, 0, s));
+        GNNLM_TRY(linear(b.a, d, w.wo, w.bo, b.x, n, d, d, b.x, ALPHA_UNSET, s));
         // feed-forward block: x += fc2(act(fc1(LN(x))))
         float* h2 = last && io.last_ffn_input ? io.last_ffn_input : b.h;
-        TRY(layernorm(b.x, d, w.ln2_g, w.ln2_b, h2, d, n, d, eps, nullptr, s));
-        TRY(linear(h2, w.w1, w.b1, b.wide, n, m.ffn, d, nullptr, s));
-        TRY(m.act == 0 ? relu(b.wide, n * m.ffn, s) : gelu(b.wide, n * m.ffn, s));
+        GNNLM_TRY(layernorm(b.x, d, w.ln2_g, w.ln2_b, h2, d, n, d, eps, nullptr, s));
+        GNNLM_TRY(linear(h2, d, w.w1, w.b1, b.wide, n, m.ffn, d, nullptr, ALPHA_UNSET, s));
+        GNNLM_TRY(m.act == 0 ? relu(b.wide, n * m.ffn, s) : gelu(b.wide, n * m.ffn, s));
         // the last layer's residual sum is inner_states[-1]: it lands where it is wanted
         float* dst = !last ? b.x : (io.last_inner ? io.last_inner : (m.ln_out_g ? b.x : io.out));
-        TRY(linear(b.wide, w.w2, w.b2, dst, n, d, m.ffn, b.x, s));
+        GNNLM_TRY(linear(b.wide, m.ffn, w.w2, w.b2, dst, n, d, m.ffn, b.x, ALPHA_UNSET, s));
         if (last) {
-            if (m.ln_out_g) TRY(layernorm(dst, d, m.ln_out_g, m.ln_out_b, io.out, d, n, d, eps, nullptr, s));
+            if (m.ln_out_g) GNNLM_TRY(layernorm(dst, d, m.ln_out_g, m.ln_out_b, io.out, d, n, d, eps, nullptr, s));
             else if (dst != io.out) GNNLM_HIP(hipMemcpyAsync(io.out, dst, (size_t)n * d * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
     }
-    if (cache) TRY(kv_len_set(*cache, rg.block_off, (int)io.max_len, s));
+    if (cache) GNNLM_TRY(kv_len_set(*cache, rg.block_off, (int)io.max_len, s));
     return OK;
 }
 
 size_t carve_step(const gnnlm_tlm_t& m, int B, int max_len, char* base, TlmBufs& b, float** attn_ws, size_t* attn_bytes) {
-    size_t off = carve_tlm(m, B, base, b) - 256;
-    off = (off + 255) & ~size_t(255);
+    Carver c(base);
+    take_tlm(m, B, c, b);
     const size_t n = decode_attn_workspace_bytes(B, m.H, m.H > 0 ? m.d / m.H : 0, max_len);
-    if (attn_ws) *attn_ws = base ? reinterpret_cast<float*>(base + off) : nullptr;
+    float* a = reinterpret_cast<float*>(c.take<char>((int64_t)n));
+    if (attn_ws) *attn_ws = a;
     if (attn_bytes) *attn_bytes = n;
-    return off + n + 256;
+    return c.off + 256;
 }
 
 // beam (gnnlm_transformer_lm_step_beam): every layer's attention reads its cached rows through the table src
 int tlm_step(const gnnlm_tlm_t& m, const gnnlm_kv_cache_t& c, const gnnlm_tlm_step_io_t& io, void* ws, size_t ws_bytes, hipStream_t s,
              bool beam = false, const int32_t* src = nullptr, int64_t ld_src = 0) {
-    TRY(check_tlm(m));
-    TRY(check_tlm_cache(m, c));
+    GNNLM_TRY(check_tlm(m));
+    GNNLM_TRY(check_tlm_cache(m, c));
     const int B = c.B, d = m.d, dk = m.d / m.H;
     const float eps = m.ln_eps == 0.f ? 1e-5f : m.ln_eps;
     GNNLM_REQUIRE(io.max_len >= 1 && io.max_len <= c.cap, "transformer_lm_step: max_len outside [1, cap] (the cache is full)");
@@ -305,7 +286,7 @@ int tlm_step(const gnnlm_tlm_t& m, const gnnlm_kv_cache_t& c, const gnnlm_tlm_st
         hipLaunchKernelGGL(lm_embed_step_kernel, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, s, p);
         GNNLM_LAUNCH_CHECK();
     }
-    if (m.ln_emb_g) TRY(layernorm(b.x, d, m.ln_emb_g, m.ln_emb_b, b.x, d, B, d, eps, nullptr, s));
+    if (m.ln_emb_g) GNNLM_TRY(layernorm(b.x, d, m.ln_emb_g, m.ln_emb_b, b.x, d, B, d, eps, nullptr, s));
     gnnlm_decode_attn_t a{};
     a.q = b.wide; a.k_new = b.wide + d; a.v_new = b.wide + 2 * d; a.ld = 3 * (int64_t)d;
     a.out = b.a; a.ldo = d;
@@ -314,24 +295,24 @@ int tlm_step(const gnnlm_tlm_t& m, const gnnlm_kv_cache_t& c, const gnnlm_tlm_st
     for (int l = 0; l < m.L; ++l) {
         const gnnlm_tlm_layer_t& w = m.layers[l];
         const bool last = l == m.L - 1;
-        TRY(layernorm(b.x, d, w.ln1_g, w.ln1_b, b.h, d, B, d, eps, nullptr, s));
-        TRY(linear(b.h, w.wqkv, w.bqkv, b.wide, B, 3 * d, d, nullptr, s));
+        GNNLM_TRY(layernorm(b.x, d, w.ln1_g, w.ln1_b, b.h, d, B, d, eps, nullptr, s));
+        GNNLM_TRY(linear(b.h, d, w.wqkv, w.bqkv, b.wide, B, 3 * d, d, nullptr, ALPHA_UNSET, s));
         a.layer = l;
         if (l > 0) a.cache.n_bad = nullptr;                 // a row out of range is counted once per step, not once per layer
-        TRY(beam ? beam_attn(a, src, ld_src, s) : decode_attn(a, s));
-        TRY(linear(b.a, w.wo, w.bo, b.x, B, d, d, b.x, s));
+        GNNLM_TRY(beam ? beam_attn(a, src, ld_src, s) : decode_attn(a, s));
+        GNNLM_TRY(linear(b.a, d, w.wo, w.bo, b.x, B, d, d, b.x, ALPHA_UNSET, s));
         float* h2 = last && io.last_ffn_input ? io.last_ffn_input : b.h;
-        TRY(layernorm(b.x, d, w.ln2_g, w.ln2_b, h2, d, B, d, eps, nullptr, s));
-        TRY(linear(h2, w.w1, w.b1, b.wide, B, m.ffn, d, nullptr, s));
-        TRY(m.act == 0 ? relu(b.wide, (int64_t)B * m.ffn, s) : gelu(b.wide, (int64_t)B * m.ffn, s));
+        GNNLM_TRY(layernorm(b.x, d, w.ln2_g, w.ln2_b, h2, d, B, d, eps, nullptr, s));
+        GNNLM_TRY(linear(h2, d, w.w1, w.b1, b.wide, B, m.ffn, d, nullptr, ALPHA_UNSET, s));
+        GNNLM_TRY(m.act == 0 ? relu(b.wide, (int64_t)B * m.ffn, s) : gelu(b.wide, (int64_t)B * m.ffn, s));
         float* dst = !last ? b.x : (io.last_inner ? io.last_inner : (m.ln_out_g ? b.x : io.out));
-        TRY(linear(b.wide, w.w2, w.b2, dst, B, d, m.ffn, b.x, s));
+        GNNLM_TRY(linear(b.wide, m.ffn, w.w2, w.b2, dst, B, d, m.ffn, b.x, ALPHA_UNSET, s));
         if (last) {
-            if (m.ln_out_g) TRY(layernorm(dst, d, m.ln_out_g, m.ln_out_b, io.out, d, B, d, eps, nullptr, s));
+            if (m.ln_out_g) GNNLM_TRY(layernorm(dst, d, m.ln_out_g, m.ln_out_b, io.out, d, B, d, eps, nullptr, s));
             else if (dst != io.out) GNNLM_HIP(hipMemcpyAsync(io.out, dst, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
     }
-    TRY(kv_len_advance(c, (int)io.max_len, s));
+    GNNLM_TRY(kv_len_advance(c, (int)io.max_len, s));
     return OK;
 }
 
@@ -356,12 +337,6 @@ int relu(float* x, int64_t n, hipStream_t stream) {
 }  // namespace gnnlm
 
 using namespace gnnlm;
-
-#define GNNLM_DESC(d)                                       \
-    if (!(d)) {                                             \
-        set_error("invalid argument: null descriptor");     \
-        return E_INVALID;                                   \
-    }
 
 extern "C" {
 

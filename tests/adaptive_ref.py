@@ -44,7 +44,7 @@ LSE_BAR = 2e-5
 BS_WAVES = 16                                    # rowops.hip: band_split_kernel takes rows in chunks of 64 * BS_WAVES
 CHUNK = 64 * BS_WAVES
 REDUCE4_MIN_PARTS = 1024                         # gemm_f32.hip: lse_reduce() launches the four-wave kernel from this many parts on
-HEAD_ORDER_MIN_N = 1024                          # api.hip: adaptive_impl sets tile_order = 2 + 4 on the head from this many rows on
+HEAD_ORDER_MIN_N = 1024                          # adaptive_logp.hip: adaptive_impl sets tile_order = 2 + 4 on the head from this many rows on
 HEAD_TILE_ORDER = 6
 INT64_MIN, INT64_MAX = -2 ** 63, 2 ** 63 - 1
 OOR_TARGETS = ("-1", "V", "V+1", 2 ** 31, 2 ** 32 + 3, INT64_MIN, INT64_MAX)

@@ -98,7 +98,7 @@ def test_outside_the_vocabulary_is_minus_infinity():
 def test_constants_are_the_sources():
     import test_gemm_ref_cpu
     test_gemm_ref_cpu.test_route_constants_are_the_sources()
-    api, rowops, main = src("api.hip"), src("rowops.hip"), src("gemm_f32.hip")
+    api, rowops, main = src("adaptive_logp.hip"), src("rowops.hip"), src("gemm_f32.hip")
     impl = body_of(api, "int adaptive_impl(", "\n}\n")
     assert "lse_reduce(b.head_part, 2 * (int)cdiv(head_n, 128), n, nullptr, b.head_lse, s)" in impl
     assert "lse_reduce(b.tail_part, 2 * (int)cdiv(size, 128), n, cnt, b.tail_lse, s)" in impl
