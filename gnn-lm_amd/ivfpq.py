@@ -22,21 +22,25 @@ candidates and scores are those of the one-pass float32 scan -- ``IVFPQIndex(...
 With ``attach_vals`` the index carries each key's label next to its id (one 8-byte payload per key), and the search
 returns ``vals[ids]`` with the neighbours: the label gather of knn/knn_model.py:198 disappears.
 
-``IVFPQIndex.build`` is the offline producer (the reference delegates it to faiss: index_builder.py:79-150): plain
-Lloyd k-means for the product quantizers, spherical k-means (unit-norm centroids, what faiss's index_factory sets for
-inner-product indexes) for the coarse one, a random orthonormal matrix for R (faiss alternates OPQ updates; any
-orthonormal R gives a valid index).  It runs on the GPU with torch ops -- offline tooling, not the hot path.
+Host path of one search ("The search's host path"): the constructor names the index's ROUTE once (``choose_route``:
+"int8" / "packed" / "rowmajor", with the L2 term in use); every call turns its numbers into one ``SearchPlan`` (``plan_search``:
+probes, capacities, block size, sampled rank, who splits the payloads); every query block fills one ``_Block`` of buffers and runs
+its route's rounds; the call's ``_Outcome`` waits in a ``_PendingSearch`` until ``_finish`` has looked at the survivor counts and
+repaired what overflowed.  One private function fills each kernel descriptor.  ``IVFPQIndex.build`` is the offline producer
+(``ivfpq_train.py``).
 
 PARITY UNPINNED against faiss itself (not in the image, no version pinned): the pin is the numpy restatement
 ``oracle/ivfpq.py`` over the SAME index arrays (tests/test_knn_search_gpu.py)."""
 import contextlib
 import ctypes
 import os
+from collections import namedtuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ivfpq_train, ops
 
 
 class _LazyStats(dict):
@@ -46,6 +50,10 @@ class _LazyStats(dict):
     def add(self, key, thunk):
         dict.setdefault(self, key, 0)
         self.__dict__.setdefault("_pending", {}).setdefault(key, []).append(thunk)
+
+    def set(self, key, value):
+        """a number the host knows already"""
+        dict.__setitem__(self, key, value)
 
     def _resolve(self, key):
         pend = self.__dict__.get("_pending", {}).pop(key, None)
@@ -63,117 +71,108 @@ class _LazyStats(dict):
         return [(k, self[k]) for k in list(self.keys())]
 
 
+def choose_route(M, ntotal, max_list, nlist, scan=None, metric="ip", list_term_bytes=4 << 30):
+    """The kernels an index is searched with, decided once from the constructor's numbers -> (route, L2 term | None).
+    route "int8": M = 64, the int8-MFMA filter + exact re-score over tiles of 16 code rows (csrc/ivfpq_mfma.hip);
+    "packed": M = 32 / 64, the float32 scan over its own image of the code rows (blocks of 64 rows, bytes in rotated order) and
+    tables in [half][code][sub-quantizer] order -- look-ups without LDS bank conflicts (csrc/ivfpq.hip); scan="f32" asks for it at
+    M = 64 too (tests compare the int8 search with it);  "rowmajor": one table per (query, list) task over the codes as stored.
+    L2 term (see ``IVFPQIndex.__init__``): "list_term", "key_term", or None (inner product, or an L2 index without keys)."""
+    term = None
+    if metric == "l2":
+        fits = nlist * M * 1024 <= list_term_bytes
+        if fits and (M != 64 or scan == "rowmajor"):
+            term = "list_term"
+        elif ntotal:
+            term = "key_term"
+        scan = "f32" if M == 64 and scan != "rowmajor" else "rowmajor"
+    if scan == "rowmajor":
+        return "rowmajor", term
+    # (a survivor record packs the row inside its list into 19 bits and the list into 18: longer / more lists take the float32 scan)
+    if M == 64 and ntotal and ntotal < (1 << 32) and scan != "f32" and max_list < (1 << 19) and nlist <= (1 << 18):
+        return "int8", term
+    return ("packed" if M in (32, 64) and ntotal else "rowmajor"), term
+
+
+# What a plan depends on besides the call's own arguments: the index's route and sizes (score_bytes: the budget of the dense round's
+# score rows per query block), its sampling settings as they are now (``_finish`` may have changed them), and the two switches of the
+# environment as they are now (select: GNNLM_IVF_SELECT != "0"; env_query_block: GNNLM_IVF_QUERY_BLOCK)
+SearchNumbers = namedtuple("SearchNumbers", "route nprobe nlist ntotal max_list score_bytes has_vals threshold_sample "
+                                            "sample_min_keys_per_k sample_sigmas select env_query_block")
+# Every per-call quantity of one pass over a batch of queries, by the rules of ``plan_search``: lists probed per query, of which the best
+# `dense` give the threshold; records per query the thresholded round may emit (int8: the filter's survivors) and candidate columns;
+# queries per block; the int8 threshold pass histograms every S-th tile of 16 keys and takes the bound of rank `rank` of that sample;
+# fold: the final selection stores (id, label) itself, no split pass over [n, k]
+SearchPlan = namedtuple("SearchPlan", "k nprobe dense cap ccap query_block qb S rank fold select")
+
+
+def plan_search(ix, k, dense_probes, cap, query_block=None, fold=None):
+    """Numbers in, numbers out (no tensors).  ``fold`` not None: decided by the caller (rows searched again come back in the state
+    of the pass they belong to, split once or not at all)."""
+    int8 = ix.route == "int8"
+    nprobe = min(ix.nprobe, ix.nlist)
+    dense = max(1, min(dense_probes, nprobe))
+    # (the int8 path: `cap` bounds a query's SURVIVORS of the filter; what scores above the refined threshold afterwards is a fraction of them
+    # and gets 16384 columns at most -- the width the one-chunk k-selection takes)
+    ccap = min(cap, 16384) if int8 else cap
+    if query_block is None:
+        # (the int8 filter groups 8 queries per list: the more queries a block holds, the fuller its groups and the longer a list's bytes
+        # stay in the XCD's L2 -- per 8192 queries 12.2 ms in blocks of 8192, 11.4 of 16384, 11.0 of 32768; ~18 GB of temporaries at 32768)
+        query_block = ix.env_query_block if int8 else 1024
+    # the dense round's score rows: query_block * dense * max_list floats, bounded (a skewed index has long lists)
+    qb = query_block if int8 else max(1, min(query_block, ix.score_bytes // max(1, 4 * dense * max(ix.max_list, 1))))
+    # The threshold pass histograms a SAMPLE of its lists' keys (every S-th tile of 16) when they hold plenty of them: tau is then the
+    # bound of rank k / S + 4.5 sigma of the sample (sigma = sqrt(k (S - 1)) / S: the k best land in the sample binomially), i.e. with
+    # probability ~1e-5 per query fewer than k keys score above it.  Nothing is taken on trust: a query with fewer than k candidates
+    # above its threshold is reported like an overflowing one and searched again with every probed list in an exact threshold pass.
+    S = ix.threshold_sample if (dense < nprobe and ix.ntotal / max(ix.nlist, 1) * dense >= ix.sample_min_keys_per_k * k) else 1
+    rank = k if S == 1 else max(1, min(k, -(-k // S) + int(np.ceil(ix.sample_sigmas * np.sqrt(k * (S - 1)) / S))))
+    if fold is None:
+        fold = bool(ix.has_vals and int8 and k <= 1024 and ix.select)
+    return SearchPlan(k, nprobe, dense, cap, ccap, query_block, qb, S, rank, fold, ix.select)
+
+
+# The buffers every route's rounds work on, for one block of queries (``IVFPQIndex._block_begin``): qr [nq, d] = R q; cs [nq, nlist] =
+# <q', c_l>; pv, pi [nq, nprobe] the probed lists' bias and ids, best first (-1: none); lut [nq, M * 256] the ADC tables and, on the int8
+# route, tables = (qlut [nq, 2, 256, 32] u8, qmeta [nq, 4] f32), their byte image; cv, ci [nq, ccap] the scores and payloads of the
+# thresholded round's candidates, cc [nq] how many (zeroed)
+_Block = namedtuple("_Block", "qr cs pv pi lut tables cv ci cc")
+
+
+class _Outcome(NamedTuple):
+    """What one pass over a batch (or a block of it: ``rows``) leaves behind."""
+    val: torch.Tensor                # [n, k] scores, descending
+    idx: torch.Tensor                # [n, k] payloads as the index carries them, or ids if `split`
+    labels: Optional[torch.Tensor]   # [n, k] int32 if `split` and the caller wants the labels
+    split: bool                      # the final selection has split the payloads already (``_deliver`` must not)
+    over: Optional[torch.Tensor] = None   # [n] survivor counts to hold against the capacity (None: no thresholded round ran)
+
+    def rows(self, lo, hi):
+        return self._replace(val=self.val[lo:hi], idx=self.idx[lo:hi], labels=None if self.labels is None else self.labels[lo:hi])
+
+
 class _PendingSearch:
     """Handle of ``IVFPQIndex.search_begin``."""
 
-    def __init__(self, index, q, k, query_block, return_vals, stats, val, idx, over, worst, ev, cap, split=None):
+    def __init__(self, index, q, k, query_block, return_vals):
         self.index, self.q, self.k, self.query_block, self.return_vals = index, q, k, query_block, return_vals
-        self.stats = stats                               # work counters of THIS search: index.stats once it has finished
-        self.val, self.idx, self.over, self.worst, self.ev = val, idx, over, worst, ev
-        self.cap = cap                                   # survivor capacity the buffers of THIS search were allocated with
-        self.split = split                               # (labels | None,) if the final selection has split the payloads already, else None
-        self._out = None
+        # of the latest pass over the whole call (``IVFPQIndex._run``): its work counters (index.stats once the search has finished),
+        # the survivor capacity its buffers were allocated with, its outcome
+        self.stats = self.cap = self.out = None
+        self.worst = self.ev = None                      # the first pass's worst survivor count on its way to pinned memory, the event behind it
+        self._result = None
 
     def result(self):
-        if self._out is None:
-            self._out = self.index._finish(self)
-        return self._out
-
-
-def _kmeans(x, k, iters, gen, spherical=False, init=None):
-    """Lloyd's algorithm (squared L2) on the device; empty clusters are re-seeded from random points.  ``spherical``: the
-    centroids are L2-normalised after every update (faiss ClusteringParameters.spherical, set by index_factory for
-    METRIC_INNER_PRODUCT coarse quantizers).  ``init``: centroids to start from (OPQ's inner PQ rounds)."""
-    n = x.shape[0]
-    if init is not None:
-        cen = init.clone()
-    else:
-        cen = x[torch.randperm(n, generator=gen, device=x.device)[:k]].clone()
-    if cen.shape[0] < k:
-        cen = torch.cat([cen, cen[torch.randint(0, cen.shape[0], (k - cen.shape[0],), generator=gen, device=x.device)]])
-    for _ in range(iters):
-        assign = torch.empty(n, dtype=torch.int64, device=x.device)
-        c2 = (cen ** 2).sum(1)
-        for s in range(0, n, 1 << 18):
-            xs = x[s:s + (1 << 18)]
-            assign[s:s + (1 << 18)] = (c2[None, :] - 2 * xs @ cen.t()).argmin(1)
-        cnt = torch.bincount(assign, minlength=k)
-        new = torch.zeros_like(cen).index_add_(0, assign, x)
-        live = cnt > 0
-        new[live] /= cnt[live, None].to(x.dtype)
-        dead = (~live).nonzero().reshape(-1)
-        if dead.numel():
-            new[dead] = x[torch.randint(0, n, (dead.numel(),), generator=gen, device=x.device)]
-        cen = new / new.norm(dim=1, keepdim=True).clamp_min(1e-20) if spherical else new
-    return cen
-
-
-def _pq_assign(x, cen):
-    """x [n, dsub], cen [256, dsub] -> nearest centroid per row (squared L2), in chunks."""
-    out = torch.empty(x.shape[0], dtype=torch.int64, device=x.device)
-    c2 = (cen ** 2).sum(1)
-    for s in range(0, x.shape[0], 1 << 18):
-        out[s:s + (1 << 18)] = (c2[None, :] - 2 * x[s:s + (1 << 18)] @ cen.t()).argmin(1)
-    return out
-
-
-def train_opq(x, M, R0, iters, gen, pq_iters=4):
-    """The OPQ rotation (Ge et al., "Optimized Product Quantization", the non-parametric solution; what faiss's OPQMatrix trains
-    for the ``OPQ64_1024`` block of the reference's index type, knn/index_builder.py:60-64): alternate (a) a product quantizer of
-    M x 256 centroids on the rotated vectors x R^T (k-means per sub-space, warm-started from the previous round) and (b) the
-    orthogonal Procrustes solution R^T = U V^T, U S V^T = x^T y, y = the quantizer's reconstruction of x R^T -- the rotation
-    under which the quantizer loses least.  x [n, d] f32 on the device, R0 [d_out, d] with orthonormal rows; -> R [d_out, d]."""
-    n, d = x.shape
-    dsub = R0.shape[0] // M                                                   # R0 [d_out, d]: d_out < d for an `OPQ<M>_<d_out>` block that reduces
-    R, cents = R0.clone(), [None] * M
-    for _ in range(iters):
-        xr = x @ R.t()
-        y = torch.empty_like(xr)
-        for m in range(M):
-            sub = xr[:, m * dsub:(m + 1) * dsub].contiguous()
-            cents[m] = _kmeans(sub, 256, pq_iters, gen, init=cents[m])
-            y[:, m * dsub:(m + 1) * dsub] = cents[m][_pq_assign(sub, cents[m])]
-        U, _, Vt = torch.linalg.svd((x.t() @ y).double(), full_matrices=False)
-        R = (U @ Vt).t().to(torch.float32).contiguous()
-    return R
-
-
-def build_groups(pl, nlist, seg=None):
-    """(query, probe) pairs of ``pl`` [nq, P] (list ids, -1 = none) -> groups of up to 8 queries that probe the same list,
-    sorted by list: grp_list [G] int32, grp_q [G, 8] int32 (-1 padded), the number of groups in use as a one-element int32
-    tensor on the device.  Torch ops on the tensor's device, no host round trip; G is the upper bound pairs / 8 + nlist + 1.
-    With ``seg``: also grp_out [G, 8] int64, the offset (query * P + probe slot) * seg of the pair's segment in a [nq, P, seg]
-    array (-1: none).  What gnnlm_ivfpq_scan8 takes as its task table (include/gnnlm.h)."""
-    nq, P = pl.shape
-    dev = pl.device
-    n = nq * P
-    key = torch.where(pl < 0, torch.full_like(pl, nlist), pl).reshape(-1)
-    skey, order = torch.sort(key, stable=True)
-    cnt = torch.zeros(nlist + 1, dtype=torch.int64, device=dev).scatter_add_(0, key, torch.ones_like(key))   # pairs per list (last bucket: no list); no host sync, unlike bincount
-    start = torch.cumsum(cnt, 0) - cnt
-    gcnt = (cnt + 7) // 8
-    goff = torch.cumsum(gcnt, 0) - gcnt                                       # first group of every list
-    pos = torch.arange(n, device=dev) - start[skey]                           # position inside the run of one list
-    gid = goff[skey] + pos // 8
-    G = n // 8 + nlist + 1
-    none = skey >= nlist                                                      # pairs without a list: their groups sort last and are
-    grp_list = torch.full((G,), -1, dtype=torch.int32, device=dev)            # cut off by n_groups, their entries stay -1
-    grp_list[gid] = torch.where(none, torch.full_like(skey, -1), skey).to(torch.int32)
-    grp_q = torch.full((G, 8), -1, dtype=torch.int32, device=dev)
-    grp_q[gid, pos % 8] = torch.where(none, torch.full_like(order, -1), torch.div(order, P, rounding_mode="floor")).to(torch.int32)
-    n_groups = gcnt[:nlist].sum().reshape(1).to(torch.int32)                  # (the groups of the "no list" bucket sort last: cut off)
-    if seg is None:
-        return grp_list, grp_q, n_groups, G
-    grp_out = torch.full((G, 8), -1, dtype=torch.int64, device=dev)
-    grp_out[gid, pos % 8] = torch.where(none, torch.full_like(order, -1), order * seg)   # order = query * P + slot
-    return grp_list, grp_q, n_groups, G, grp_out
+        if self._result is None:
+            self._result = self.index._finish(self)
+        return self._result
 
 
 class IVFPQIndex:
-    UNDERFLOW = 1 << 30      # "survivor count" of a query whose sampled threshold left fewer than k candidates: searched again like an overflow
-    COLUMNS = (1 << 30) - 1  # ... of a query with more candidates than the selection has columns (a larger survivor capacity would not help it)
     """faiss ``search`` contract: ``search(queries [n, d] f32, k) -> (scores [n, k] descending, ids [n, k], -1 padded)``."""
 
+    UNDERFLOW = 1 << 30      # "survivor count" of a query whose sampled threshold left fewer than k candidates: searched again like an overflow
+    COLUMNS = (1 << 30) - 1  # ... of a query with more candidates than the selection has columns (a larger survivor capacity would not help it)
     LABEL_BITS = 24                                                          # payload = id << 24 | label (ids < 2^39, labels < 2^24)
 
     def __init__(self, R, coarse, pq, list_off, list_ids, list_codes, nprobe=32, cosine=True, dense_probes=None, cand_cap=None,
@@ -181,7 +180,7 @@ class IVFPQIndex:
         self.R, self.coarse, self.pq = R, coarse, pq                         # [d, d], [nlist, d], [M, 256, dsub]  f32
         self.list_off, self.list_ids, self.list_codes = list_off, list_ids, list_codes   # i64 [nlist+1], i64 [N], u8 [N, M]
         self.nprobe, self.cosine, self.dense_probes, self.cand_cap = nprobe, cosine, dense_probes, cand_cap
-        self.threshold_sample = 4                # every S-th tile of the threshold lists is histogrammed (1: all of them -- see _search_block_mfma)
+        self.threshold_sample = 4                # every S-th tile of the threshold lists is histogrammed (1: all of them -- see plan_search)
         self.sample_min_keys_per_k = 64          # ... when the threshold lists hold at least this many keys per neighbour asked for
         self.sample_sigmas = 4.5                 # margin of the sample's rank (tests lower it to force the verification to fail)
         self.sample_fail_frac = 0.01             # more failing queries than this in a batch: the index stops sampling
@@ -194,13 +193,10 @@ class IVFPQIndex:
         self.d, self.nlist = coarse.shape[1], coarse.shape[0]
         self.M, _, self.dsub = pq.shape
         self.ntotal = list_ids.shape[0]
-        self.max_list = int((list_off[1:] - list_off[:-1]).max().item()) if self.nlist else 0
-        # M = 32 / 64: the scan runs on its own image of the code rows (blocks of 64 rows, bytes in rotated order) and on
-        # tables in [half][code][sub-quantizer] order -- look-ups without LDS bank conflicts (csrc/ivfpq.hip)
-        # M = 64: the int8-MFMA search's image of the code rows (tiles of 16 rows, rotated byte order; csrc/ivfpq_mfma.hip)
-        # scan="f32": the float32 scan at M = 64 too (tests compare the int8-MFMA search with it)
-        self.packed_codes = self.tiles = None
-        self.list_term = self.key_term = None
+        self.list_len = list_off[1:] - list_off[:-1]
+        self.max_list = int(self.list_len.max().item()) if self.nlist else 0
+        self.route, term = choose_route(self.M, self.ntotal, self.max_list, self.nlist, scan, metric, list_term_bytes)
+        self.packed_codes = self.tiles = self.list_term = self.key_term = None
         if metric == "l2":
             # squared distances with residual codes: |q' - c_l - r|^2 = |q' - c_l|^2 + sum_m (T[l][m][code] - 2 <q'_m, p_mc>) with the
             # per-list table T[l][m][c] = |p_mc|^2 + 2 <c_l,m, p_mc> (faiss IndexIVFPQ's precomputed table).  A key's M entries of T add up
@@ -210,31 +206,29 @@ class IVFPQIndex:
             #   T beyond list_term_bytes (nlist * M KiB: many lists): key_term + the row-major scan
             #   otherwise: T itself; the row-major scan adds it to the query's table while it fills LDS (gnnlm_ivfpq_scan, list_term)
             self.coarse_n2 = (coarse ** 2).sum(1).contiguous()
-            fits = self.nlist * self.M * 1024 <= list_term_bytes
-            if fits and (self.M != 64 or scan == "rowmajor"):
+            if term == "list_term":
                 cross = torch.einsum("lmd,mcd->lmc", coarse.reshape(self.nlist, self.M, self.dsub), pq)
                 self.list_term = ((pq ** 2).sum(2)[None] + 2.0 * cross).reshape(self.nlist, self.M * 256).contiguous()
-            elif self.ntotal:
+            elif term == "key_term":
                 self.key_term = ops.ivfpq_key_terms(list_codes, list_off, coarse, pq)
-            scan = "f32" if self.M == 64 and scan != "rowmajor" else "rowmajor"
-        if scan == "rowmajor":
-            pass                                                             # the row-major kernels (one table per (query, list) task)
-        elif self.M == 64 and self.ntotal and self.ntotal < (1 << 32) and scan != "f32" and self.max_list < (1 << 19) and self.nlist <= (1 << 18):
-            # (a survivor record packs the row inside its list into 19 bits and the list into 18: longer / more lists take the float32 scan)
+        if self.route == "int8":
             self.tiles = ops.ivfpq_pack_tiles(self.list_codes)
-        elif self.M in (32, 64) and self.ntotal:
+        elif self.route == "packed":
             self.packed_codes = torch.empty(-(-self.ntotal // 64) * 64 * self.M, dtype=torch.uint8, device=self.device)
             _lib.call("gnnlm_ivfpq_pack_codes", _lib.ptr(self.list_codes), self.ntotal, self.M, _lib.ptr(self.packed_codes), _lib.stream())
         # lists per query behind the threshold: the float32 dense round scores 2 in full; the int8 threshold pass is cheap and its
         # bound a little loose, 6 lists give the tighter threshold (fewer survivors to re-score) for less time
         if self.dense_probes is None:
-            self.dense_probes = 6 if self.tiles is not None else 2
+            self.dense_probes = 6 if self.route == "int8" else 2
         # records per query: the int8 filter's SURVIVORS (8 bytes each; a sampled threshold lets ~8 k of them through on average and twice that
         # where list lengths vary: 32768 keeps the re-searches of overflowing queries rare), the float32 scan's candidates
         if self.cand_cap is None:
-            self.cand_cap = 32768 if self.tiles is not None else 16384
+            self.cand_cap = 32768 if self.route == "int8" else 16384
         self.refine_tau = True                   # the threshold refinement inside the re-score's launch (False: the re-score alone, tests)
+        self.keep_candidates, self.last_candidates = False, None             # tests / debugging: (cv, ci, cc, tau) of the last block's thresholded round
+        self.keep_work_ctr, self.last_work_ctr = False, None                 # instrumented builds (GNNLM_IVF8_EXP & 512) leave phase times in the last scan8's counters
         self._side_streams = {}                                              # raw stream -> its side stream
+        self._worst_host, self._worst_next = None, 0                         # pinned landing slots (``_landing_slot``), pinned with the first search
         self.stats = {}                                                      # device-side work counters of the last search that finished (bench.py)
 
     def attach_vals(self, vals):
@@ -251,60 +245,16 @@ class IVFPQIndex:
         self.has_vals, self.val_last = True, int(v[-1].item())
         return self
 
-    # ------------------------------------------------------------------------------------------ offline producer
     @classmethod
     def build(cls, keys, nlist, M, device="cuda", cosine=True, nprobe=32, iters=10, train_size=262144, seed=0, chunk=1 << 18,
               opq_iters=0, metric="ip", **kw):
-        """Train (rotation, coarse centroids, residual product quantizer) on a sample and add every key.  ``opq_iters`` = 0: a
-        random orthonormal rotation (spreads the variance over the sub-spaces); > 0: that many rounds of OPQ training from it
-        (``train_opq``: what the reference's ``OPQ64_1024`` block asks faiss for)."""
-        device = torch.device(device)
-        gen = torch.Generator(device=device)
-        gen.manual_seed(seed)
-        N, d = keys.shape
-        assert d % M == 0 and (d // M) % 4 == 0 and M % 16 == 0, "need dsub % 4 == 0 and M % 16 == 0"
-        dsub = d // M
-
-        def rows(lo, hi):
-            x = torch.from_numpy(np.ascontiguousarray(keys[lo:hi]).astype(np.float32)).to(device) if not isinstance(keys, torch.Tensor) \
-                else keys[lo:hi].to(device, torch.float32)
-            return x / (x ** 2).sum(1, keepdim=True).sqrt() if cosine else x
-
-        cpu_gen = torch.Generator().manual_seed(seed)
-        R = torch.linalg.qr(torch.randn(d, d, generator=cpu_gen, dtype=torch.float64))[0].to(torch.float32).to(device)
-        pick = np.sort(np.random.RandomState(seed).choice(N, size=min(N, train_size), replace=False))
-        xt = torch.cat([rows(int(s), int(min(N, s + chunk)))[torch.from_numpy(pick[(pick >= s) & (pick < s + chunk)] - s).to(device)]
-                        for s in range(0, N, chunk)])
-        if opq_iters > 0:
-            R = train_opq(xt, M, R, opq_iters, gen)
-        xt = xt @ R.t()
-        l2 = metric == "l2"
-        assert not (l2 and cosine), "the L2 index takes the keys as they are"
-        coarse = _kmeans(xt, nlist, iters, gen, spherical=cosine)
-        # the list of a vector: the centroid with the largest inner product (IndexFlatIP quantizer) / the nearest one (IndexFlatL2)
-        nearest = lambda x: ((x @ coarse.t()) - (0.5 * (coarse ** 2).sum(1)[None, :] if l2 else 0.0)).argmax(1)
-        resid = xt - coarse[nearest(xt)]
-        pq = torch.stack([_kmeans(resid[:, m * dsub:(m + 1) * dsub].contiguous(), 256, iters, gen) for m in range(M)])
-        # add every key: list assignment + residual PQ codes (HIP argmin kernel of TorchPQCodec.encode)
-        assign = torch.empty(N, dtype=torch.int64, device=device)
-        codes = torch.empty(N, M, dtype=torch.uint8, device=device)
-        norm2 = (pq ** 2).sum(2).contiguous()
-        for s in range(0, N, chunk):
-            x = rows(s, min(N, s + chunk)) @ R.t()
-            a = nearest(x)
-            assign[s:s + chunk] = a
-            r = (x - coarse[a]).contiguous()
-            _lib.call("gnnlm_pq_encode", _lib.ptr(r), r.stride(0), _lib.ptr(pq), _lib.ptr(norm2), M, dsub, r.shape[0],
-                      _lib.ptr(codes[s:s + chunk]), _lib.stream())
-        order = torch.sort(assign, stable=True).indices
-        off = torch.zeros(nlist + 1, dtype=torch.int64, device=device)
-        off[1:] = torch.cumsum(torch.bincount(assign, minlength=nlist), 0)
-        return cls(R.contiguous(), coarse.contiguous(), pq.contiguous(), off, order.contiguous(), codes[order].contiguous(),
-                   nprobe=nprobe, cosine=cosine, metric=metric, **kw)
+        """The offline producer: train and add every key (``ivfpq_train.build_arrays``), then the index over those arrays."""
+        arrays = ivfpq_train.build_arrays(keys, nlist, M, device, cosine, iters, train_size, seed, chunk, opq_iters, metric)
+        return cls(*arrays, nprobe=nprobe, cosine=cosine, metric=metric, **kw)
 
     def save(self, path):
-        np.savez(path, **{k: getattr(self, k).cpu().numpy() for k in ("R", "coarse", "pq", "list_off", "list_ids", "list_codes")},
-                 meta=np.array([self.nprobe, int(self.cosine), int(self.metric == "l2")]))
+        arrays = dict(R=self.R, coarse=self.coarse, pq=self.pq, list_off=self.list_off, list_ids=self.list_ids, list_codes=self.list_codes)
+        np.savez(path, **{k: t.cpu().numpy() for k, t in arrays.items()}, meta=np.array([self.nprobe, int(self.cosine), int(self.metric == "l2")]))
 
     @classmethod
     def load(cls, path, device="cuda", **kw):
@@ -333,46 +283,10 @@ class IVFPQIndex:
         kw.setdefault("nprobe", z["nprobe"])
         return cls(t(R), t(z["coarse"]), t(z["pq"]), t(z["list_off"]), t(z["list_ids"]), t(z["list_codes"]), cosine=cosine, **kw)
 
-    # ------------------------------------------------------------------------------------------ search
-    def _scan(self, lut, probe_val, probe_id, p_lo, p_hi, out=None, tau=None, cand=None, cap=None):
-        n = lut.shape[0]
-        dev = self.device
-        pl = probe_id[:, p_lo:p_hi]
-        # tasks grouped by list (bookkeeping on the device, no host round trip): concurrent workgroups share code rows
-        order = torch.sort(pl.reshape(-1), stable=True).indices
-        task_q = torch.div(order, p_hi - p_lo, rounding_mode="floor").to(torch.int32)
-        task_p = (order % (p_hi - p_lo) + p_lo).to(torch.int32)
-        s = _lib.gnnlm_ivfpq_scan_t()
-        s.codes, s.ids, s.list_off, s.M = self.list_codes.data_ptr(), self.payload.data_ptr(), self.list_off.data_ptr(), self.M
-        if self.packed_codes is not None:
-            s.codes, s.packed = self.packed_codes.data_ptr(), 1                 # `lut` is then the packed table set
-        s.lut, s.ld_lut = lut.data_ptr(), lut.stride(0)
-        s.probe_list, s.probe_bias, s.ld_probe = probe_id.data_ptr(), probe_val.data_ptr(), probe_id.stride(0)
-        s.task_q, s.task_p, s.n_tasks = task_q.data_ptr(), task_p.data_ptr(), order.numel()
-        if self.list_term is not None:
-            s.list_term, s.ld_list_term = self.list_term.data_ptr(), self.list_term.stride(0)
-        if self.key_term is not None:
-            s.key_term = self.key_term.data_ptr()
-        if tau is None:
-            s.out_val, s.ld_out, s.p0, s.seg = out.data_ptr(), out.stride(0), p_lo, self.max_list       # scores only (out_id NULL)
-        else:
-            s.tau, s.cand_val, s.cand_id, s.cand_cnt, s.cap = tau.data_ptr(), cand[0].data_ptr(), cand[1].data_ptr(), cand[2].data_ptr(), cap
-        _lib.call_desc("gnnlm_ivfpq_scan", s)
-
-    def _groups(self, pl, seg=None):
-        """The scan's task table on the device (gnnlm_ivfpq_build_groups: histogram, prefix, scatter -- four small launches instead
-        of the ~25 of ``build_groups``, the torch reference of the same table); same tuple."""
-        nq, P = pl.shape
-        dev = pl.device
-        G = nq * P // 8 + self.nlist + 1
-        grp_list = torch.empty(G, dtype=torch.int32, device=dev)
-        grp_q = torch.empty(G, 8, dtype=torch.int32, device=dev)
-        grp_out = torch.empty(G, 8, dtype=torch.int64, device=dev) if seg is not None else None
-        n_groups = torch.empty(1, dtype=torch.int32, device=dev)
-        scratch = torch.empty(2 * (self.nlist + 1), dtype=torch.int32, device=dev)
-        _lib.call("gnnlm_ivfpq_build_groups", ctypes.c_void_p(pl.data_ptr()), pl.stride(0), nq, P, self.nlist, seg or 0, _lib.ptr(grp_list),
-                  _lib.ptr(grp_q), _lib.ptr(grp_out), _lib.ptr(n_groups), _lib.ptr(scratch), _lib.stream())
-        return (grp_list, grp_q, n_groups, G) if seg is None else (grp_list, grp_q, n_groups, G, grp_out)
+    # ------------------------------------------------------------------------------------------ a search: begin, finish, repair
+    def search(self, queries, k):
+        d, i = self.search_device(torch.as_tensor(np.asarray(queries)), k)
+        return d.cpu().numpy(), i.cpu().numpy()
 
     def search_device(self, q, k, query_block=None, return_vals=False):
         """The search, on device tensors: (scores [n, k] descending, ids [n, k], -1 padded[, vals [n, k] int32 with
@@ -387,111 +301,191 @@ class IVFPQIndex:
         worst survivor count on its way to pinned memory) and returns what ``search_device`` returns.  Work enqueued between the two
         calls (the language model's softmax, which does not depend on the neighbours) keeps the device busy while the host looks at
         the count and enqueues what follows: no pipeline bubble behind the search's one host round trip."""
-        q = q.to(self.device, torch.float32).contiguous()
-        stats = self._new_stats(q.shape[0])
-        cap = self.cand_cap                                                  # the capacity THIS search's buffers were allocated with
-        val, idx, over, split = self._search_once(q, k, query_block, self.dense_probes, cap, stats, return_vals)
-        worst = ev = None
-        if over is not None:
-            if getattr(self, "_worst_host", None) is None:                    # pinned landing slots, one per search in flight (a ring of 8)
-                self._worst_host, self._worst_next = torch.empty(8, dtype=torch.int32).pin_memory(), 0
-            worst = self._worst_host[self._worst_next:self._worst_next + 1]
-            self._worst_next = (self._worst_next + 1) % 8
-            worst.copy_(over.max().reshape(1), non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        return _PendingSearch(self, q, k, query_block, return_vals, stats, val, idx, over, worst, ev, cap, split)
+        h = _PendingSearch(self, q.to(self.device, torch.float32).contiguous(), k, query_block, return_vals)
+        self._run(h, self.cand_cap)
+        if h.out.over is not None:
+            h.worst = self._landing_slot()
+            h.worst.copy_(h.out.over.max().reshape(1), non_blocking=True)
+            h.ev = torch.cuda.Event()
+            h.ev.record()
+        return h
 
-    def _new_stats(self, n):
-        return _LazyStats(pairs=0, survivors=0, candidates=0, queries=n, M=self.M, requeried=0)
+    def _landing_slot(self):
+        """one of 8 pinned ints, one per search in flight (a ring)"""
+        if self._worst_host is None:
+            self._worst_host = torch.empty(8, dtype=torch.int32).pin_memory()
+        slot = self._worst_host[self._worst_next:self._worst_next + 1]
+        self._worst_next = (self._worst_next + 1) % 8
+        return slot
+
+    def _plan(self, k, dense_probes, cap, query_block=None, fold=None):
+        ix = SearchNumbers(self.route, self.nprobe, self.nlist, self.ntotal, self.max_list, self.score_bytes, self.has_vals,
+                           self.threshold_sample, self.sample_min_keys_per_k, self.sample_sigmas,
+                           # GNNLM_IVF_SELECT=0: the selections by gnnlm_topk_merge and the split pass of their own, as before csrc/ivfpq_select.hip (A/B runs)
+                           os.environ.get("GNNLM_IVF_SELECT", "1") != "0", int(os.environ.get("GNNLM_IVF_QUERY_BLOCK", "32768")))
+        return plan_search(ix, k, dense_probes, cap, query_block, fold)
+
+    def _run(self, h, cap):
+        """One pass over the whole call with `cap` records per query (not self.cand_cap: another search in flight may have raised it
+        since), under the index's settings as they are now; the handle's counters describe this pass alone."""
+        h.cap, h.stats = cap, _LazyStats(pairs=0, survivors=0, candidates=0, queries=h.q.shape[0], M=self.M, requeried=0)
+        h.out = self._search_once(h.q, self._plan(h.k, self.dense_probes, cap, h.query_block), h.stats, h.return_vals)
 
     def _finish(self, h):
-        q, k, query_block = h.q, h.k, h.query_block
-        val, idx, over, split = h.val, h.idx, h.over, h.split
-        cap = h.cap                                                           # (not self.cand_cap: another search in flight may have raised it since)
-        while over is not None:
+        n = h.q.shape[0]
+        while h.out.over is not None:
             if h.ev is not None:
                 h.ev.synchronize()
-                if int(h.worst[0]) <= cap:
+                if int(h.worst[0]) <= h.cap:
                     break
                 h.ev = None
-            bad = (over > cap).nonzero().reshape(-1)                          # host sync
+            over = h.out.over
+            bad = (over > h.cap).nonzero().reshape(-1)                        # host sync
             if bad.numel() == 0:
                 break
             n_under = int((over[bad] >= self.UNDERFLOW).sum().item())
             n_cols = int((over[bad] == self.COLUMNS).sum().item())            # too many CANDIDATES for the selection's columns: searched again one by one
-            if n_under > self.sample_fail_frac * q.shape[0] and self.threshold_sample > 1:   # the sample does not stand for its lists on this data: stop sampling
+            if n_under > self.sample_fail_frac * n and self.threshold_sample > 1:   # the sample does not stand for its lists on this data: stop sampling
                 self.threshold_sample = 1
-                h.stats = self._new_stats(q.shape[0])
-                val, idx, over, split = self._search_once(q, k, query_block, self.dense_probes, cap, h.stats, h.return_vals)
-                continue
-            if (bad.numel() - n_under - n_cols) * 8 > q.shape[0] and cap < (1 << 18):
-                cap *= 2
-                self.cand_cap = max(self.cand_cap, cap)
-                h.stats = self._new_stats(q.shape[0])
-                val, idx, over, split = self._search_once(q, k, query_block, self.dense_probes, cap, h.stats, h.return_vals)
-                continue
-            sub, cap2 = q[bad].contiguous(), cap
-            while True:                                                       # every probed list in the threshold / dense round
-                # (the counters describe the main pass: the re-search's go to a throw-away set)
-                # (`split` of the main pass decides for its rows: the re-searched ones come back in the same state, split once or not at all)
-                v2, i2, o2, s2 = self._search_once(sub, k, query_block, self.nprobe, cap2, _LazyStats(), h.return_vals, fold=split is not None)
-                if o2 is None or int(o2.max().item()) <= cap2:
-                    break
-                if cap2 >= (1 << 22):                                         # survivors beyond the capacity would be dropped silently
-                    raise _lib.GnnlmError(f"ivfpq search: {int(o2.max().item())} survivors of one query exceed the largest candidate "
-                                          f"capacity ({cap2}); lower k / nprobe or search this index with scan='f32'")
-                cap2 *= 2
-            val[bad], idx[bad] = v2, i2
-            if split is not None and split[0] is not None:
-                split[0][bad] = s2[0]
-            dict.__setitem__(h.stats, "requeried", int(bad.numel()))
-            break
+                self._run(h, h.cap)
+            elif (bad.numel() - n_under - n_cols) * 8 > n and h.cap < (1 << 18):
+                self.cand_cap = max(self.cand_cap, 2 * h.cap)
+                self._run(h, 2 * h.cap)
+            else:
+                self._search_rows_again(h, bad)
+                break
         self.stats = h.stats
+        return self._deliver(h)
+
+    def _search_rows_again(self, h, bad):
+        """Rows `bad` of the handle's outcome, searched on their own with every probed list in the threshold / dense round and written
+        over their rows (the counters describe the main pass: the re-search's go to a throw-away set)."""
+        out, sub, cap = h.out, h.q[bad].contiguous(), h.cap
+        while True:
+            again = self._search_once(sub, self._plan(h.k, self.nprobe, cap, h.query_block, fold=out.split), _LazyStats(), h.return_vals)
+            if again.over is None or int(again.over.max().item()) <= cap:
+                break
+            if cap >= (1 << 22):                                              # survivors beyond the capacity would be dropped silently
+                raise _lib.GnnlmError(f"ivfpq search: {int(again.over.max().item())} survivors of one query exceed the largest candidate "
+                                      f"capacity ({cap}); lower k / nprobe or search this index with scan='f32'")
+            cap *= 2
+        out.val[bad], out.idx[bad] = again.val, again.idx
+        if out.labels is not None:
+            out.labels[bad] = again.labels
+        h.stats.set("requeried", int(bad.numel()))
+
+    def _deliver(self, h):
+        """the outcome as ``search_device`` returns it: distances for L2, payloads split into (id, label) if nobody has yet"""
+        val, idx, rv = h.out.val, h.out.idx, h.return_vals
         if self.metric == "l2":
             val = -val                                                        # scores are -distance: squared distances, ascending, +inf padded
         if not self.has_vals:
-            return (val, idx, None) if h.return_vals else (val, idx)
-        if split is not None:                                                 # the final selection stored (id, label) itself: no pass over [n, k]
-            return (val, idx, split[0]) if h.return_vals else (val, idx)
+            return (val, idx, None) if rv else (val, idx)
+        if h.out.split:                                                       # the final selection stored (id, label) itself: no pass over [n, k]
+            return (val, idx, h.out.labels) if rv else (val, idx)
         # payload -> (id in place, label): one pass (gnnlm_ivfpq_split_payload) instead of five elementwise torch kernels over [n, k]
-        vals = torch.empty(idx.shape, dtype=torch.int32, device=idx.device) if h.return_vals else None
+        vals = torch.empty(idx.shape, dtype=torch.int32, device=idx.device) if rv else None
         _lib.call("gnnlm_ivfpq_split_payload", _lib.ptr(idx), idx.numel(), self.LABEL_BITS, self.val_last, _lib.ptr(vals), _lib.stream())
-        return (val, idx, vals) if h.return_vals else (val, idx)
+        return (val, idx, vals) if rv else (val, idx)
 
-    @staticmethod
-    def _select_on():
-        """GNNLM_IVF_SELECT=0: the selections by gnnlm_topk_merge and the split pass of their own, as before csrc/ivfpq_select.hip (A/B runs)"""
-        return os.environ.get("GNNLM_IVF_SELECT", "1") != "0"
-
-    def _search_once(self, q, k, query_block, dense_probes, cap, stats, return_vals=False, fold=None):
-        """-> (val, idx, over, split).  split: None = idx holds the payloads as the index carries them (``_finish`` splits them if they
-        have labels); (labels | None,) = the final selection has stored ids (and labels [n, k] int32 with ``return_vals``) already."""
+    # ------------------------------------------------------------------------------------------ one pass: blocks of queries
+    def _search_once(self, q, plan, stats, return_vals=False):
         n, dev = q.shape[0], self.device
-        nprobe = min(self.nprobe, self.nlist)
-        dense = max(1, min(dense_probes, nprobe))
-        val = torch.empty(n, k, device=dev, dtype=torch.float32)
-        idx = torch.empty(n, k, device=dev, dtype=torch.int64)
-        if fold is None:
-            fold = self.has_vals and self.tiles is not None and k <= 1024 and self._select_on()
-        split = ((torch.empty(n, k, dtype=torch.int32, device=dev) if return_vals else None),) if fold else None
-        if query_block is None:                                               # groups of 8 queries per list want many queries per block
-            # (the int8 filter groups 8 queries per list: the more queries a block holds, the fuller its groups and the longer a list's bytes
-            # stay in the XCD's L2 -- per 8192 queries 12.2 ms in blocks of 8192, 11.4 of 16384, 11.0 of 32768; ~18 GB of temporaries at 32768)
-            query_block = int(os.environ.get("GNNLM_IVF_QUERY_BLOCK", "32768")) if self.tiles is not None else 1024
-        # the dense round's score rows: query_block * dense * max_list floats, bounded (a skewed index has long lists)
-        qb = query_block if self.tiles is not None else max(1, min(query_block, self.score_bytes // max(1, 4 * dense * max(self.max_list, 1))))
-        over = None
-        for q0 in range(0, n, qb):
-            bl = None if split is None else (None if split[0] is None else split[0][q0:q0 + qb],)
-            o = self._search_block(q[q0:q0 + qb], k, val[q0:q0 + qb], idx[q0:q0 + qb], nprobe, dense, cap, stats, bl)
+        val = torch.empty(n, plan.k, device=dev, dtype=torch.float32)
+        idx = torch.empty(n, plan.k, device=dev, dtype=torch.int64)
+        labels = torch.empty(n, plan.k, dtype=torch.int32, device=dev) if plan.fold and return_vals else None
+        out, over = _Outcome(val, idx, labels, plan.fold), None
+        block = self._block_int8 if self.route == "int8" else self._block_f32
+        for q0 in range(0, n, plan.qb):
+            o = block(plan, self._block_begin(plan, q[q0:q0 + plan.qb], stats), out.rows(q0, q0 + plan.qb), stats)
             if o is not None:
                 over = o if over is None else torch.cat([over, o])
-        return val, idx, over, split
+        return out._replace(over=over)
 
-    def _select_probes(self, cs, pv, pi, col_bias=None):
+    def _block_begin(self, plan, qs, stats):
+        dev, nq = self.device, qs.shape[0]
+        qr = ops.gemm_nt(qs, self.R)                                            # q' = R q
+        # the ADC tables (a store-bound batched GEMM, 2 KB per query and sub-quantizer) and their 8-bit images depend on q' alone: they
+        # are built on a side stream beside the coarse scores / probe selection / task table of this stream
+        lut, tables, side = self._tables_begin(qr)
+        cs = ops.gemm_nt(qr, self.coarse)                                       # <q', c_l>
+        pv = torch.empty(nq, plan.nprobe, device=dev, dtype=torch.float32)
+        pi = torch.empty(nq, plan.nprobe, device=dev, dtype=torch.int64)
+        if self.metric == "l2":                                                 # the nprobe NEAREST lists: argmax <q', c> - |c|^2 / 2
+            self._select_probes(plan, cs, pv, pi, col_bias=-0.5 * self.coarse_n2)
+            pv = (2.0 * pv - (qr ** 2).sum(1, keepdim=True)).contiguous()      # the list's bias: -|q' - c_l|^2
+        else:
+            self._select_probes(plan, cs, pv, pi)                               # the nprobe best lists, best first
+        stats.add("pairs", lambda pi=pi: self.list_len[pi.clamp(min=0)].masked_fill(pi < 0, 0).sum().double())
+        if side is not None:
+            torch.cuda.current_stream().wait_stream(side)                       # (lut / tables were allocated on THIS stream: no record_stream needed)
+        cv = torch.empty(nq, plan.ccap, device=dev, dtype=torch.float32)
+        ci = torch.empty(nq, plan.ccap, device=dev, dtype=torch.int64)
+        cc = torch.zeros(nq, device=dev, dtype=torch.int32)
+        return _Block(qr, cs, pv, pi, lut, tables, cv, ci, cc)
+
+    def _block_f32(self, plan, blk, out, stats):
+        """The float32 scan ("packed" / "rowmajor"), two rounds; -> the candidate counts of round 2 (None: every list was dense)."""
+        dev, nq, k, dense = self.device, blk.pv.shape[0], plan.k, plan.dense
+        bv, bi, pi = out.val, out.idx, blk.pi
+        lut_s = blk.lut
+        if self.route == "packed":
+            lut_s = torch.empty_like(blk.lut)
+            _lib.call("gnnlm_ivfpq_pack_lut", _lib.ptr(blk.lut), blk.lut.stride(0), nq, self.M, _lib.ptr(lut_s), _lib.stream())
+        # round 1: the best `dense` lists of every query, every score
+        ov = torch.empty(nq, dense * self.max_list, device=dev, dtype=torch.float32)
+        self._scan(lut_s, blk, 0, dense, out=ov)
+        ops.topk_merge(ov, bv, bi, largest=True, init=True)                     # ids = columns of ov
+        # the columns kept -> payloads: column = probe slot * max_list + position in the list (-inf: beyond a list)
+        lst = torch.gather(pi, 1, torch.div(bi, self.max_list, rounding_mode="floor").clamp_(0, dense - 1))
+        pos = self.list_off[lst.clamp(min=0)] + bi % self.max_list
+        bi.copy_(torch.where(torch.isinf(bv) | (lst < 0), torch.full_like(bi, -1), self.payload[pos.clamp_(0, max(self.ntotal - 1, 0))]))
+        if plan.nprobe <= dense:
+            return None
+        # round 2: the other lists only emit scores above the query's k-th best so far
+        tau = torch.where(bi[:, k - 1] >= 0, bv[:, k - 1], torch.full_like(bv[:, k - 1], float("-inf"))).contiguous()
+        self._scan(lut_s, blk, dense, plan.nprobe, filt=(tau, plan.cap))
+        stats.add("candidates", lambda cc=blk.cc: cc.sum().double())
+        if self.keep_candidates:
+            self.last_candidates = (blk.cv, blk.ci, blk.cc, tau)
+        ops.topk_merge(blk.cv, bv, bi, ids=blk.ci, largest=True, init=False, row_ncols=blk.cc.clamp(max=plan.cap))
+        return blk.cc
+
+    def _block_int8(self, plan, blk, out, stats):
+        """M = 64: everything on the int8 matrix cores (csrc/ivfpq_mfma.hip).  (1) threshold pass: histograms of the integer sums of the
+        first `dense` lists (a sample of them: plan.S) -> a lower bound tau of the query's k-th best score (no per-key output, no
+        selection); (2) filter: every probed list, keys whose integer sum can reach tau; (3) exact float32 scores of the survivors,
+        score > tau -> candidates; (4) one k-selection over the candidates.  -> the survivor counts to hold against plan.cap."""
+        dev, nq, pi, cc = self.device, blk.pv.shape[0], blk.pi, blk.cc
+        hist = torch.empty(nq, plan.dense, 1024, device=dev, dtype=torch.int32)   # per (query, list): sum_u >> 4 counted on the device
+        self._scan8(blk.tables, blk.cs, self._groups(pi[:, :plan.dense], seg=1024), hist=hist, stride=plan.S)
+        tau = self._tau(plan, blk, hist)
+        surv = torch.empty(nq, plan.cap, 2, device=dev, dtype=torch.int32)
+        sc16 = torch.zeros(nq, 16, device=dev, dtype=torch.int32)              # one 64-byte line per counter (column 0)
+        g2 = self._groups(pi)
+        stats.add("groups", lambda g=g2[2]: g[0].double())
+        self._scan8(blk.tables, blk.cs, g2, filt=(tau, surv, sc16))
+        sc = sc16[:, 0]
+        self._rescore(plan, blk, (tau, surv, sc16), stats)
+        stats.add("survivors", lambda sc=sc: sc.sum().double())
+        stats.add("candidates", lambda cc=cc: cc.sum().double())
+        if self.keep_candidates:
+            self.last_candidates = (blk.cv, blk.ci, cc, tau)
+        self._select_final(plan, blk, out)
+        over = sc                                                             # every candidate is a survivor: sc >= cc
+        if plan.ccap < plan.cap:                                              # more candidates than columns: an overflow like any other
+            over = torch.where(cc > plan.ccap, torch.full_like(sc, self.COLUMNS), over)
+        if plan.S > 1:                                                        # the sampled threshold's proof: k candidates above it (or every key there is)
+            avail = self.list_len[pi.clamp(min=0)].masked_fill(pi < 0, 0).sum(1)
+            short = cc.to(torch.int64) < avail.clamp(max=plan.k)
+            stats.add("underflow", lambda short=short: short.sum().double())
+            over = torch.where(short, torch.full_like(sc, self.UNDERFLOW), over)
+        return over
+
+    # ------------------------------------------------------------------------------------------ one function per descriptor
+    def _select_probes(self, plan, cs, pv, pi, col_bias=None):
         """the nprobe best lists of every query, best first (csrc/ivfpq_select.hip); shapes it does not take go to gnnlm_topk_merge"""
-        if not self._select_on() or cs.shape[1] > 4096 or pv.shape[1] > 64:
+        if not plan.select or cs.shape[1] > 4096 or pv.shape[1] > 64:
             return ops.topk_merge(cs, pv, pi, largest=True, init=True, col_bias=col_bias)
         d = _lib.gnnlm_ivfpq_select_probes_t()
         d.scores, d.ld, d.n, d.ncols = cs.data_ptr(), cs.stride(0), cs.shape[0], cs.shape[1]
@@ -500,87 +494,20 @@ class IVFPQIndex:
         d.k, d.largest, d.out_val, d.out_id = pv.shape[1], 1, pv.data_ptr(), pi.data_ptr()
         _lib.call_desc("gnnlm_ivfpq_select_probes", d)
 
-    def _search_block(self, qs, k, bv, bi, nprobe, dense, cap, stats, split=None):
-        dev = self.device
-        nq = qs.shape[0]
-        qr = ops.gemm_nt(qs, self.R)                                            # q' = R q
-        # the ADC tables (a store-bound batched GEMM, 2 KB per query and sub-quantizer) and their 8-bit images depend on q' alone: they
-        # are built on a side stream beside the coarse scores / probe selection / task table of this stream
-        lut, tables, side = self._tables_begin(qr)
-        cs = ops.gemm_nt(qr, self.coarse)                                       # <q', c_l>
-        pv = torch.empty(nq, nprobe, device=dev, dtype=torch.float32)
-        pi = torch.empty(nq, nprobe, device=dev, dtype=torch.int64)
-        if self.metric == "l2":                                                 # the nprobe NEAREST lists: argmax <q', c> - |c|^2 / 2
-            self._select_probes(cs, pv, pi, col_bias=-0.5 * self.coarse_n2)
-            pv = (2.0 * pv - (qr ** 2).sum(1, keepdim=True)).contiguous()      # the list's bias: -|q' - c_l|^2
-        else:
-            self._select_probes(cs, pv, pi)                                     # the nprobe best lists, best first
-        stats.add("pairs", lambda pi=pi: (self.list_off[1:] - self.list_off[:-1])[pi.clamp(min=0)].masked_fill(pi < 0, 0).sum().double())
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)                       # (lut / tables were allocated on THIS stream: no record_stream needed)
-        # (the int8 path: `cap` bounds a query's SURVIVORS of the filter; what scores above the refined threshold afterwards is a fraction of them
-        # and gets 16384 columns at most -- the width the one-chunk k-selection takes)
-        ccap = min(cap, 16384) if self.tiles is not None else cap
-        cv = torch.empty(nq, ccap, device=dev, dtype=torch.float32)
-        ci = torch.empty(nq, ccap, device=dev, dtype=torch.int64)
-        cc = torch.zeros(nq, device=dev, dtype=torch.int32)
-        if self.tiles is not None:
-            return self._search_block_mfma(k, bv, bi, nprobe, dense, cs, pv, pi, lut, tables, cv, ci, cc, cap, stats, split)
-        lut_s = lut
-        if self.packed_codes is not None:
-            lut_s = torch.empty_like(lut)
-            _lib.call("gnnlm_ivfpq_pack_lut", _lib.ptr(lut), lut.stride(0), nq, self.M, _lib.ptr(lut_s), _lib.stream())
-        # round 1: the best `dense` lists of every query, every score
-        ov = torch.empty(nq, dense * self.max_list, device=dev, dtype=torch.float32)
-        self._scan(lut_s, pv, pi, 0, dense, out=ov)
-        ops.topk_merge(ov, bv, bi, largest=True, init=True)                     # ids = columns of ov
-        # the columns kept -> payloads: column = probe slot * max_list + position in the list (-inf: beyond a list)
-        lst = torch.gather(pi, 1, torch.div(bi, self.max_list, rounding_mode="floor").clamp_(0, dense - 1))
-        pos = self.list_off[lst.clamp(min=0)] + bi % self.max_list
-        bi.copy_(torch.where(torch.isinf(bv) | (lst < 0), torch.full_like(bi, -1), self.payload[pos.clamp_(0, max(self.ntotal - 1, 0))]))
-        if nprobe <= dense:
-            return None
-        # round 2: the other lists only emit scores above the query's k-th best so far
-        tau = torch.where(bi[:, k - 1] >= 0, bv[:, k - 1], torch.full_like(bv[:, k - 1], float("-inf"))).contiguous()
-        self._scan(lut_s, pv, pi, dense, nprobe, tau=tau, cand=(cv, ci, cc), cap=cap)
-        stats.add("candidates", lambda cc=cc: cc.sum().double())
-        if getattr(self, "keep_candidates", False):                          # tests / debugging: the round-2 candidates of the last block
-            self.last_candidates = (cv, ci, cc, tau)
-        ops.topk_merge(cv, bv, bi, ids=ci, largest=True, init=False, row_ncols=cc.clamp(max=cap))
-        return cc
-
-    def _scan8(self, qlut, qmeta, cs, groups, tau=None, surv=None, hist=None, stride=1):
-        d = _lib.gnnlm_ivfpq_scan8_t()
-        d.sums_stride = stride
-        d.tiles, d.list_off, d.M = self.tiles.data_ptr(), self.list_off.data_ptr(), self.M
-        d.nlist, d.max_list = self.nlist, self.max_list
-        d.qlut, d.qmeta, d.coarse, d.ld_coarse = qlut.data_ptr(), qmeta.data_ptr(), cs.data_ptr(), cs.stride(0)
-        d.grp_list, d.grp_q, d.n_groups, d.max_groups = groups[0].data_ptr(), groups[1].data_ptr(), groups[2].data_ptr(), groups[3]
-        ctr = torch.zeros(8, 16, device=self.device, dtype=torch.int32)          # the persistent workgroups' work counters (one per XCD)
-        d.work_ctr = ctr.data_ptr()
-        if getattr(self, "keep_work_ctr", False):                              # instrumented builds (GNNLM_IVF8_EXP & 512) leave phase times here
-            self.last_work_ctr = ctr
-        if hist is not None:
-            d.out_hist, d.grp_out = hist.data_ptr(), groups[4].data_ptr()
-        else:
-            d.tau, d.surv, d.surv_cnt, d.cap = tau.data_ptr(), surv[0].data_ptr(), surv[1].data_ptr(), surv[0].shape[1]
-        _lib.call_desc("gnnlm_ivfpq_scan8", d)
-
     def _tables_begin(self, qr):
         """lut[q][m][c] = <q'_m, p_mc> (M small GEMMs) and, for the int8 filter, its byte image: enqueued on a side stream of the
         current one when the filter will run (the caller joins before the first consumer).  -> (lut, (qlut, qmeta) | None, side | None)"""
         nq, dev = qr.shape[0], self.device
         lut = torch.empty(nq, self.M * 256, device=dev, dtype=torch.float32)
-        tables = None
-        if self.tiles is not None:
+        tables = side = None
+        if self.route == "int8":
             tables = (torch.empty(nq, 2, 256, 32, dtype=torch.uint8, device=dev), torch.empty(nq, 4, dtype=torch.float32, device=dev))
-        side = None
-        if self.tiles is not None and not torch.cuda.is_current_stream_capturing():
-            cur = torch.cuda.current_stream()
-            side = self._side_streams.get(cur.cuda_stream)
-            if side is None:
-                side = self._side_streams[cur.cuda_stream] = torch.cuda.Stream(device=dev)
-            side.wait_stream(cur)
+            if not torch.cuda.is_current_stream_capturing():
+                cur = torch.cuda.current_stream()
+                side = self._side_streams.get(cur.cuda_stream)
+                if side is None:
+                    side = self._side_streams[cur.cuda_stream] = torch.cuda.Stream(device=dev)
+                side.wait_stream(cur)
         with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
             if tables is not None and self.dsub in (4, 8, 16, 32):
                 t = _lib.gnnlm_ivfpq_tables_t()
@@ -597,73 +524,104 @@ class IVFPQIndex:
                 _lib.call("gnnlm_ivfpq_quantize_lut", _lib.ptr(lut), lut.stride(0), nq, self.M, _lib.ptr(tables[0]), _lib.ptr(tables[1]), _lib.stream())
         return lut, tables, side
 
-    def _search_block_mfma(self, k, bv, bi, nprobe, dense, cs, pv, pi, lut, tables, cv, ci, cc, cap, stats, split=None):
-        """M = 64: everything on the int8 matrix cores (csrc/ivfpq_mfma.hip).  (1) threshold pass: histograms of the integer sums of the
-        first `dense` lists -> a lower bound tau of the query's k-th best score (no per-key output, no selection); (2) filter: every probed
-        list, keys whose integer sum can reach tau; (3) exact float32 scores of the survivors, score > tau -> candidates;
-        (4) one k-selection over the candidates."""
-        dev = self.device
-        nq, ccap = pv.shape[0], cv.shape[1]
-        qlut, qmeta = tables
-        hist = torch.empty(nq, dense, 1024, device=dev, dtype=torch.int32)      # per (query, list): sum_u >> 4 counted on the device
-        # The threshold pass histograms a SAMPLE of its lists' keys (every S-th tile of 16) when they hold plenty of them: tau is then the
-        # bound of rank k / S + 4.5 sigma of the sample (sigma = sqrt(k (S - 1)) / S: the k best land in the sample binomially), i.e. with
-        # probability ~1e-5 per query fewer than k keys score above it.  Nothing is taken on trust: a query with fewer than k candidates
-        # above its threshold is reported like an overflowing one and searched again with every probed list in an exact threshold pass.
-        S = self.threshold_sample if (dense < nprobe and self.ntotal / max(self.nlist, 1) * dense >= self.sample_min_keys_per_k * k) else 1
-        rank = k if S == 1 else max(1, min(k, -(-k // S) + int(np.ceil(self.sample_sigmas * np.sqrt(k * (S - 1)) / S))))
-        self._scan8(qlut, qmeta, cs, self._groups(pi[:, :dense], seg=1024), hist=hist, stride=S)
-        tau = torch.empty(nq, device=dev, dtype=torch.float32)
+    def _scan(self, lut, blk, p_lo, p_hi, out=None, filt=None):
+        """gnnlm_ivfpq_scan over probe slots p_lo..p_hi of a block.  ``out``: every score, [nq, (p_hi - p_lo) * max_list];
+        ``filt`` = (tau, cap): scores above tau into the block's candidate buffers."""
+        pl = blk.pi[:, p_lo:p_hi]
+        # tasks grouped by list (bookkeeping on the device, no host round trip): concurrent workgroups share code rows
+        order = torch.sort(pl.reshape(-1), stable=True).indices
+        task_q = torch.div(order, p_hi - p_lo, rounding_mode="floor").to(torch.int32)
+        task_p = (order % (p_hi - p_lo) + p_lo).to(torch.int32)
+        s = _lib.gnnlm_ivfpq_scan_t()
+        s.codes, s.ids, s.list_off, s.M = self.list_codes.data_ptr(), self.payload.data_ptr(), self.list_off.data_ptr(), self.M
+        if self.route == "packed":
+            s.codes, s.packed = self.packed_codes.data_ptr(), 1                 # `lut` is then the packed table set
+        s.lut, s.ld_lut = lut.data_ptr(), lut.stride(0)
+        s.probe_list, s.probe_bias, s.ld_probe = blk.pi.data_ptr(), blk.pv.data_ptr(), blk.pi.stride(0)
+        s.task_q, s.task_p, s.n_tasks = task_q.data_ptr(), task_p.data_ptr(), order.numel()
+        if self.list_term is not None:
+            s.list_term, s.ld_list_term = self.list_term.data_ptr(), self.list_term.stride(0)
+        if self.key_term is not None:
+            s.key_term = self.key_term.data_ptr()
+        if filt is None:
+            s.out_val, s.ld_out, s.p0, s.seg = out.data_ptr(), out.stride(0), p_lo, self.max_list       # scores only (out_id NULL)
+        else:
+            s.tau, s.cand_val, s.cand_id, s.cand_cnt, s.cap = filt[0].data_ptr(), blk.cv.data_ptr(), blk.ci.data_ptr(), blk.cc.data_ptr(), filt[1]
+        _lib.call_desc("gnnlm_ivfpq_scan", s)
+
+    def _groups(self, pl, seg=None):
+        """The scan's task table on the device (gnnlm_ivfpq_build_groups: histogram, prefix, scatter -- four small launches instead
+        of the ~25 of ``tests/ivfpq_groups_ref.py``, the torch reference of the same table); same tuple."""
+        nq, P = pl.shape
+        dev = pl.device
+        G = nq * P // 8 + self.nlist + 1
+        grp_list = torch.empty(G, dtype=torch.int32, device=dev)
+        grp_q = torch.empty(G, 8, dtype=torch.int32, device=dev)
+        grp_out = torch.empty(G, 8, dtype=torch.int64, device=dev) if seg is not None else None
+        n_groups = torch.empty(1, dtype=torch.int32, device=dev)
+        scratch = torch.empty(2 * (self.nlist + 1), dtype=torch.int32, device=dev)
+        _lib.call("gnnlm_ivfpq_build_groups", ctypes.c_void_p(pl.data_ptr()), pl.stride(0), nq, P, self.nlist, seg or 0, _lib.ptr(grp_list),
+                  _lib.ptr(grp_q), _lib.ptr(grp_out), _lib.ptr(n_groups), _lib.ptr(scratch), _lib.stream())
+        return (grp_list, grp_q, n_groups, G) if seg is None else (grp_list, grp_q, n_groups, G, grp_out)
+
+    def _scan8(self, tables, cs, groups, hist=None, stride=1, filt=None):
+        """gnnlm_ivfpq_scan8 over a task table (``_groups``).  ``hist`` (groups with segment offsets): the threshold pass, every
+        `stride`-th tile; ``filt`` = (tau, surv, counters): the filter."""
+        d = _lib.gnnlm_ivfpq_scan8_t()
+        d.sums_stride = stride
+        d.tiles, d.list_off, d.M = self.tiles.data_ptr(), self.list_off.data_ptr(), self.M
+        d.nlist, d.max_list = self.nlist, self.max_list
+        d.qlut, d.qmeta, d.coarse, d.ld_coarse = tables[0].data_ptr(), tables[1].data_ptr(), cs.data_ptr(), cs.stride(0)
+        d.grp_list, d.grp_q, d.n_groups, d.max_groups = groups[0].data_ptr(), groups[1].data_ptr(), groups[2].data_ptr(), groups[3]
+        ctr = torch.zeros(8, 16, device=self.device, dtype=torch.int32)          # the persistent workgroups' work counters (one per XCD)
+        d.work_ctr = ctr.data_ptr()
+        if self.keep_work_ctr:
+            self.last_work_ctr = ctr
+        if hist is not None:
+            d.out_hist, d.grp_out = hist.data_ptr(), groups[4].data_ptr()
+        else:
+            tau, surv, cnt = filt
+            d.tau, d.surv, d.surv_cnt, d.cap = tau.data_ptr(), surv.data_ptr(), cnt.data_ptr(), surv.shape[1]
+        _lib.call_desc("gnnlm_ivfpq_scan8", d)
+
+    def _tau(self, plan, blk, hist):
+        """histograms of the threshold lists -> tau [nq], the bound of rank plan.rank among the keys counted"""
+        tau = torch.empty(hist.shape[0], device=self.device, dtype=torch.float32)
         t = _lib.gnnlm_ivfpq_tau_t()
-        t.hist, t.D = hist.data_ptr(), dense
-        t.probe_list, t.probe_bias, t.ld_probe = pi.data_ptr(), pv.data_ptr(), pi.stride(0)
-        t.qmeta, t.n, t.k, t.tau = qmeta.data_ptr(), nq, rank, tau.data_ptr()
+        t.hist, t.D = hist.data_ptr(), plan.dense
+        t.probe_list, t.probe_bias, t.ld_probe = blk.pi.data_ptr(), blk.pv.data_ptr(), blk.pi.stride(0)
+        t.qmeta, t.n, t.k, t.tau = blk.tables[1].data_ptr(), hist.shape[0], plan.rank, tau.data_ptr()
         _lib.call_desc("gnnlm_ivfpq_tau", t)
-        surv = torch.empty(nq, cap, 2, device=dev, dtype=torch.int32)
-        sc16 = torch.zeros(nq, 16, device=dev, dtype=torch.int32)              # one 64-byte line per counter (column 0)
-        g2 = self._groups(pi)
-        stats.add("groups", lambda g=g2[2]: g[0].double())
-        self._scan8(qlut, qmeta, cs, g2, tau=tau, surv=(surv, sc16))
-        sc = sc16[:, 0]
+        return tau
+
+    def _rescore(self, plan, blk, filt, stats):
+        """exact float32 scores of the filter's survivors; those above tau become the block's candidates"""
+        tau, surv, sc16 = filt
         r = _lib.gnnlm_ivfpq_rescore_t()
         r.codes, r.payload, r.M = self.list_codes.data_ptr(), self.payload.data_ptr(), self.M
-        r.lut, r.ld_lut, r.coarse, r.ld_coarse, r.tau = lut.data_ptr(), lut.stride(0), cs.data_ptr(), cs.stride(0), tau.data_ptr()
-        r.surv, r.surv_cnt, r.cap, r.n = surv.data_ptr(), sc16.data_ptr(), cap, nq
-        r.cand_val, r.cand_id, r.cand_cnt, r.cand_cap = cv.data_ptr(), ci.data_ptr(), cc.data_ptr(), ccap
+        r.lut, r.ld_lut, r.coarse, r.ld_coarse, r.tau = blk.lut.data_ptr(), blk.lut.stride(0), blk.cs.data_ptr(), blk.cs.stride(0), tau.data_ptr()
+        r.surv, r.surv_cnt, r.cap, r.n = surv.data_ptr(), sc16.data_ptr(), plan.cap, sc16.shape[0]
+        r.cand_val, r.cand_id, r.cand_cnt, r.cand_cap = blk.cv.data_ptr(), blk.ci.data_ptr(), blk.cc.data_ptr(), plan.ccap
         if self.refine_tau:
             # inside the re-score's launch: a tighter threshold from the survivors' own integer sums (all lists, un-binned), and only
             # the survivors that can beat it are re-scored
             rc16 = torch.empty_like(sc16)
-            r.qmeta, r.k, r.out_cnt = qmeta.data_ptr(), k, rc16.data_ptr()
+            r.qmeta, r.k, r.out_cnt = blk.tables[1].data_ptr(), plan.k, rc16.data_ptr()
             stats.add("rescored", lambda rc=rc16: rc[:, 0].sum().double())
         _lib.call_desc("gnnlm_ivfpq_rescore", r)
-        stats.add("survivors", lambda sc=sc: sc.sum().double())
-        stats.add("candidates", lambda cc=cc: cc.sum().double())
-        if getattr(self, "keep_candidates", False):
-            self.last_candidates = (cv, ci, cc, tau)
-        if k <= 1024 and (split is not None or self._select_on()):
-            # the k best candidates, ranked inside value bins (csrc/ivfpq_select.hip); with `split` the payloads leave as (id, label)
-            rn = cc.clamp(max=ccap)
-            f = _lib.gnnlm_ivfpq_select_final_t()
-            f.cand_val, f.ld_val, f.cand_id, f.ld_id = cv.data_ptr(), cv.stride(0), ci.data_ptr(), ci.stride(0)
-            f.row_ncols, f.n, f.cap, f.k, f.out_val, f.out_id = rn.data_ptr(), nq, ccap, k, bv.data_ptr(), bi.data_ptr()
-            if split is not None:
-                f.label_bits, f.val_last = self.LABEL_BITS, self.val_last
-                if split[0] is not None:
-                    f.out_vals = split[0].data_ptr()
-            _lib.call_desc("gnnlm_ivfpq_select_final", f)
-        else:
-            ops.topk_merge(cv, bv, bi, ids=ci, largest=True, init=True, row_ncols=cc.clamp(max=ccap))
-        over = sc                                                             # every candidate is a survivor: sc >= cc
-        if ccap < cap:                                                         # more candidates than columns: an overflow like any other
-            over = torch.where(cc > ccap, torch.full_like(sc, self.COLUMNS), over)
-        if S > 1:                                                              # the sampled threshold's proof: k candidates above it (or every key there is)
-            avail = (self.list_off[1:] - self.list_off[:-1])[pi.clamp(min=0)].masked_fill(pi < 0, 0).sum(1)
-            short = cc.to(torch.int64) < avail.clamp(max=k)
-            stats.add("underflow", lambda short=short: short.sum().double())
-            over = torch.where(short, torch.full_like(sc, self.UNDERFLOW), over)
-        return over
 
-    def search(self, queries, k):
-        d, i = self.search_device(torch.as_tensor(np.asarray(queries)), k)
-        return d.cpu().numpy(), i.cpu().numpy()
+    def _select_final(self, plan, blk, out):
+        """the k best candidates of every query into the outcome's rows: ranked inside value bins (csrc/ivfpq_select.hip), with
+        ``out.split`` the payloads leave as (id, label); k beyond 1024 and GNNLM_IVF_SELECT=0 go to gnnlm_topk_merge"""
+        cv, ci, ccap = blk.cv, blk.ci, plan.ccap
+        if not (plan.k <= 1024 and (out.split or plan.select)):
+            return ops.topk_merge(cv, out.val, out.idx, ids=ci, largest=True, init=True, row_ncols=blk.cc.clamp(max=ccap))
+        rn = blk.cc.clamp(max=ccap)
+        f = _lib.gnnlm_ivfpq_select_final_t()
+        f.cand_val, f.ld_val, f.cand_id, f.ld_id = cv.data_ptr(), cv.stride(0), ci.data_ptr(), ci.stride(0)
+        f.row_ncols, f.n, f.cap, f.k, f.out_val, f.out_id = rn.data_ptr(), cv.shape[0], ccap, plan.k, out.val.data_ptr(), out.idx.data_ptr()
+        if out.split:
+            f.label_bits, f.val_last = self.LABEL_BITS, self.val_last
+            if out.labels is not None:
+                f.out_vals = out.labels.data_ptr()
+        _lib.call_desc("gnnlm_ivfpq_select_final", f)

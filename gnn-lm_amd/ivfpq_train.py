@@ -1,0 +1,117 @@
+"""The offline producer of an IVF-PQ index (``IVFPQIndex.build`` delegates here; the reference delegates it to faiss:
+knn/index_builder.py:79-150): plain Lloyd k-means for the product quantizers, spherical k-means (unit-norm centroids, what faiss's
+index_factory sets for inner-product indexes) for the coarse one, a random orthonormal matrix for R or OPQ rounds from it (faiss
+alternates OPQ updates; any orthonormal R gives a valid index).  It runs on the GPU with torch ops -- offline tooling, not the
+hot path; ``quantize_features.py`` trains its feature quantizer with the same ``kmeans`` / ``train_opq``."""
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def kmeans(x, k, iters, gen, spherical=False, init=None):
+    """Lloyd's algorithm (squared L2) on the device; empty clusters are re-seeded from random points.  ``spherical``: the
+    centroids are L2-normalised after every update (faiss ClusteringParameters.spherical, set by index_factory for
+    METRIC_INNER_PRODUCT coarse quantizers).  ``init``: centroids to start from (OPQ's inner PQ rounds)."""
+    n = x.shape[0]
+    if init is not None:
+        cen = init.clone()
+    else:
+        cen = x[torch.randperm(n, generator=gen, device=x.device)[:k]].clone()
+    if cen.shape[0] < k:
+        cen = torch.cat([cen, cen[torch.randint(0, cen.shape[0], (k - cen.shape[0],), generator=gen, device=x.device)]])
+    for _ in range(iters):
+        assign = torch.empty(n, dtype=torch.int64, device=x.device)
+        c2 = (cen ** 2).sum(1)
+        for s in range(0, n, 1 << 18):
+            xs = x[s:s + (1 << 18)]
+            assign[s:s + (1 << 18)] = (c2[None, :] - 2 * xs @ cen.t()).argmin(1)
+        cnt = torch.bincount(assign, minlength=k)
+        new = torch.zeros_like(cen).index_add_(0, assign, x)
+        live = cnt > 0
+        new[live] /= cnt[live, None].to(x.dtype)
+        dead = (~live).nonzero().reshape(-1)
+        if dead.numel():
+            new[dead] = x[torch.randint(0, n, (dead.numel(),), generator=gen, device=x.device)]
+        cen = new / new.norm(dim=1, keepdim=True).clamp_min(1e-20) if spherical else new
+    return cen
+
+
+def pq_assign(x, cen):
+    """x [n, dsub], cen [256, dsub] -> nearest centroid per row (squared L2), in chunks."""
+    out = torch.empty(x.shape[0], dtype=torch.int64, device=x.device)
+    c2 = (cen ** 2).sum(1)
+    for s in range(0, x.shape[0], 1 << 18):
+        out[s:s + (1 << 18)] = (c2[None, :] - 2 * x[s:s + (1 << 18)] @ cen.t()).argmin(1)
+    return out
+
+
+def train_opq(x, M, R0, iters, gen, pq_iters=4):
+    """The OPQ rotation (Ge et al., "Optimized Product Quantization", the non-parametric solution; what faiss's OPQMatrix trains
+    for the ``OPQ64_1024`` block of the reference's index type, knn/index_builder.py:60-64): alternate (a) a product quantizer of
+    M x 256 centroids on the rotated vectors x R^T (k-means per sub-space, warm-started from the previous round) and (b) the
+    orthogonal Procrustes solution R^T = U V^T, U S V^T = x^T y, y = the quantizer's reconstruction of x R^T -- the rotation
+    under which the quantizer loses least.  x [n, d] f32 on the device, R0 [d_out, d] with orthonormal rows; -> R [d_out, d]."""
+    n, d = x.shape
+    dsub = R0.shape[0] // M                                                   # R0 [d_out, d]: d_out < d for an `OPQ<M>_<d_out>` block that reduces
+    R, cents = R0.clone(), [None] * M
+    for _ in range(iters):
+        xr = x @ R.t()
+        y = torch.empty_like(xr)
+        for m in range(M):
+            sub = xr[:, m * dsub:(m + 1) * dsub].contiguous()
+            cents[m] = kmeans(sub, 256, pq_iters, gen, init=cents[m])
+            y[:, m * dsub:(m + 1) * dsub] = cents[m][pq_assign(sub, cents[m])]
+        U, _, Vt = torch.linalg.svd((x.t() @ y).double(), full_matrices=False)
+        R = (U @ Vt).t().to(torch.float32).contiguous()
+    return R
+
+
+def build_arrays(keys, nlist, M, device="cuda", cosine=True, iters=10, train_size=262144, seed=0, chunk=1 << 18, opq_iters=0,
+                 metric="ip"):
+    """Train (rotation, coarse centroids, residual product quantizer) on a sample and add every key.  ``opq_iters`` = 0: a
+    random orthonormal rotation (spreads the variance over the sub-spaces); > 0: that many rounds of OPQ training from it
+    (``train_opq``: what the reference's ``OPQ64_1024`` block asks faiss for).
+    -> (R, coarse, pq, list_off, list_ids, list_codes), the constructor arguments of ``IVFPQIndex``."""
+    device = torch.device(device)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed)
+    N, d = keys.shape
+    assert d % M == 0 and (d // M) % 4 == 0 and M % 16 == 0, "need dsub % 4 == 0 and M % 16 == 0"
+    dsub = d // M
+
+    def rows(lo, hi):
+        x = torch.from_numpy(np.ascontiguousarray(keys[lo:hi]).astype(np.float32)).to(device) if not isinstance(keys, torch.Tensor) \
+            else keys[lo:hi].to(device, torch.float32)
+        return x / (x ** 2).sum(1, keepdim=True).sqrt() if cosine else x
+
+    cpu_gen = torch.Generator().manual_seed(seed)
+    R = torch.linalg.qr(torch.randn(d, d, generator=cpu_gen, dtype=torch.float64))[0].to(torch.float32).to(device)
+    pick = np.sort(np.random.RandomState(seed).choice(N, size=min(N, train_size), replace=False))
+    xt = torch.cat([rows(int(s), int(min(N, s + chunk)))[torch.from_numpy(pick[(pick >= s) & (pick < s + chunk)] - s).to(device)]
+                    for s in range(0, N, chunk)])
+    if opq_iters > 0:
+        R = train_opq(xt, M, R, opq_iters, gen)
+    xt = xt @ R.t()
+    l2 = metric == "l2"
+    assert not (l2 and cosine), "the L2 index takes the keys as they are"
+    coarse = kmeans(xt, nlist, iters, gen, spherical=cosine)
+    # the list of a vector: the centroid with the largest inner product (IndexFlatIP quantizer) / the nearest one (IndexFlatL2)
+    nearest = lambda x: ((x @ coarse.t()) - (0.5 * (coarse ** 2).sum(1)[None, :] if l2 else 0.0)).argmax(1)
+    resid = xt - coarse[nearest(xt)]
+    pq = torch.stack([kmeans(resid[:, m * dsub:(m + 1) * dsub].contiguous(), 256, iters, gen) for m in range(M)])
+    # add every key: list assignment + residual PQ codes (HIP argmin kernel of TorchPQCodec.encode)
+    assign = torch.empty(N, dtype=torch.int64, device=device)
+    codes = torch.empty(N, M, dtype=torch.uint8, device=device)
+    norm2 = (pq ** 2).sum(2).contiguous()
+    for s in range(0, N, chunk):
+        x = rows(s, min(N, s + chunk)) @ R.t()
+        a = nearest(x)
+        assign[s:s + chunk] = a
+        r = (x - coarse[a]).contiguous()
+        _lib.call("gnnlm_pq_encode", _lib.ptr(r), r.stride(0), _lib.ptr(pq), _lib.ptr(norm2), M, dsub, r.shape[0],
+                  _lib.ptr(codes[s:s + chunk]), _lib.stream())
+    order = torch.sort(assign, stable=True).indices
+    off = torch.zeros(nlist + 1, dtype=torch.int64, device=device)
+    off[1:] = torch.cumsum(torch.bincount(assign, minlength=nlist), 0)
+    return R.contiguous(), coarse.contiguous(), pq.contiguous(), off, order.contiguous(), codes[order].contiguous()

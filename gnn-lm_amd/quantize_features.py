@@ -6,7 +6,7 @@
 
   1. gathers the reference's training sample (``--chunk-size`` rows taken as the FIRST rows of each of 100 equal parts of the
      key table, quantize_features.py:79-90; ``--norm`` L2-normalises them, :92-94),
-  2. trains the quantizer the index string names -- ``OPQ<M>_<d_out>`` = an OPQ rotation ``A [d_out, d_in]`` (``ivfpq.train_opq``:
+  2. trains the quantizer the index string names -- ``OPQ<M>_<d_out>`` = an OPQ rotation ``A [d_out, d_in]`` (``ivfpq_train.train_opq``:
      alternating product-quantizer rounds and orthogonal Procrustes, what faiss's ``OPQMatrix`` does for the reference at :96,107),
      ``PQ<M>`` = M x 256 centroids by k-means on the rotated sample -- on the GPU,
   3. writes ``<data-dir>/quantizer[-norm]`` in faiss's own ``IndexPreTransform(OPQMatrix -> IndexPQ)`` serialisation
@@ -32,7 +32,7 @@ import torch
 from . import ops
 from .data_store import DataStore
 from .faiss_io import write_pq_quantizer
-from .ivfpq import _kmeans, train_opq
+from .ivfpq_train import kmeans, train_opq
 from .path_utils import dstore_path, quantized_feature_path, quantizer_path
 from .pq_wrapper import TorchPQCodec
 
@@ -122,7 +122,7 @@ def train_quantizer(xt, opq, d_out, M, opq_iters, pq_iters, opq_train, seed):
     else:
         xr = xt
     dsub = d_out // M
-    cen = torch.stack([_kmeans(xr[:, m * dsub:(m + 1) * dsub].contiguous(), 256, pq_iters, gen) for m in range(M)])
+    cen = torch.stack([kmeans(xr[:, m * dsub:(m + 1) * dsub].contiguous(), 256, pq_iters, gen) for m in range(M)])
     return cen.cpu().numpy(), (A.cpu().numpy() if A is not None else None), (np.zeros(0, np.float32) if A is not None else None)
 
 

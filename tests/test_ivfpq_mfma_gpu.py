@@ -75,7 +75,7 @@ def test_quantize_lut_bound(dev):
 
 
 def _prepare(index, q, dev):
-    """The pieces of IVFPQIndex._search_block a direct call of the scan needs."""
+    """The pieces of IVFPQIndex._block_begin a direct call of the scan needs."""
     from gnnlm_amd import _lib, ops
     qr = ops.gemm_nt(q, index.R)
     cs = ops.gemm_nt(qr, index.coarse)
@@ -145,7 +145,7 @@ def test_groups(dev, small_index):
         assert ((rows >= 0).sum(1)[:-1] == 8).all()
     # the device builder (gnnlm_ivfpq_build_groups) against the torch reference of the table: same lists, same group counts, same
     # queries per list (which queries share a group is left open), the segment offsets of the threshold pass, a strided probe table
-    from gnnlm_amd.ivfpq import build_groups
+    from ivfpq_groups_ref import build_groups
     big = torch.from_numpy(np.stack([rs.permutation(index.nlist)[:9] for _ in range(300)])).to(dev)
     big[5, 1] = -1
     for tab, seg in ((pl, None), (big[:, :4], 1024), (big, 16)):
@@ -241,7 +241,7 @@ def test_threshold_pass_is_a_lower_bound(dev, small_index):
     u = (qlut.cpu().numpy().astype(np.int64) ^ 0x80)                           # [nq, 2, 256, 32]: the byte tables
     for D, k in ((3, 1024), (2, 64), (1, 9000)):
         hist = torch.zeros(nq, D, 1024, device=dev, dtype=torch.int32)
-        index._scan8(qlut, qmeta, cs, index._groups(pi[:, :D], seg=1024), hist=hist)
+        index._scan8((qlut, qmeta), cs, index._groups(pi[:, :D], seg=1024), hist=hist)
         tau = torch.empty(nq, device=dev)
         t = _lib.gnnlm_ivfpq_tau_t()
         t.hist, t.D = hist.data_ptr(), D
@@ -436,7 +436,7 @@ def test_search_result_does_not_depend_on_the_grouping(dev, small_index, monkeyp
     """Which queries of a list share a workgroup, and in which order survivors and candidates are appended, is decided by
     atomics (gnnlm_ivfpq_build_groups, the survivor counters): the RESULT must not depend on it -- repeated searches, the torch
     reference of the task table and a shuffled query order all give the same scores and ids, bit for bit."""
-    from gnnlm_amd.ivfpq import build_groups
+    from ivfpq_groups_ref import build_groups
     index, q = small_index
     qd = torch.from_numpy(np.concatenate([q, q[::-1], q[5:25]])).to(dev)
     v0, i0 = index.search_device(qd, 1024)

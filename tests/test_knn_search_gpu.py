@@ -210,7 +210,7 @@ def test_ivfpq_packed_scan_matches_oracle(dev, M):
     assert np.mean([len(set(a) & set(b)) / 1024 for a, b in zip(jf, i3)]) > 0.998
     # the same index searched by the row-major kernels gives the same neighbours
     plain = IVFPQIndex(index.R, index.coarse, index.pq, index.list_off, index.list_ids, index.list_codes, nprobe=9, scan="f32")
-    plain.packed_codes = None
+    plain.packed_codes, plain.route = None, "rowmajor"
     v2, i2 = plain.search(qn, 64)
     np.testing.assert_allclose(v2, v, rtol=1e-5, atol=1e-5)
     assert np.mean([len(set(a) & set(b)) / 64 for a, b in zip(i, i2)]) > 0.998

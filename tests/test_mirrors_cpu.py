@@ -190,7 +190,7 @@ def test_ivfpq_group_table():
     most 8 queries that probe the same list, sorted by list; every pair exactly once, full groups except the last of a list,
     -1 probes dropped, the output offsets of the threshold pass -- pure torch, device-agnostic (here on the CPU)."""
     import torch
-    from gnnlm_amd.ivfpq import build_groups
+    from ivfpq_groups_ref import build_groups
     rs = np.random.RandomState(5)
     nlist, nq, P, seg = 24, 61, 7, 1024
     pl = torch.from_numpy(np.stack([rs.permutation(nlist)[:P] for _ in range(nq)]))
