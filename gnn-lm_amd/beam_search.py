@@ -30,15 +30,13 @@ ignored hypotheses; here the slots without a survivor are dead (``pad``, -inf). 
 ``--score-prompt`` with ``--knnlm``.
 """
 import logging
-import os
 import sys
 
 import numpy as np
 import torch
 
-from . import ops
-from .generate import DONE_EVERY, EOS, PAD, UNK, Generator
-from . import generate as _gen
+from . import gen_common, ops
+from .generate import DONE_EVERY, EOS, PAD, UNK, Generator, read_prompts
 
 logger = logging.getLogger("gnnlm_amd.beam_search")
 
@@ -89,10 +87,7 @@ def finish(fin_n, fin_tok, fin_cum, fin_len, fin_score, score0, len0, lenpen=1.0
 class BeamGenerator(Generator):
     @staticmethod
     def check_beam(max_new, beam, nbest, temperature, V):
-        if max_new < 1:
-            raise ValueError("max_new (--max-len-b) must be at least 1")
-        if not temperature > 0:
-            raise ValueError("--temperature must be greater than 0")
+        gen_common.check_decode(max_new, temperature)
         if beam < 1 or beam > MAX_BEAM:
             raise ValueError(f"--beam {beam}: between 1 and {MAX_BEAM} (gnnlm_beam_select)")
         if 2 * beam > V - 1:
@@ -103,22 +98,14 @@ class BeamGenerator(Generator):
     def start(self, prompts, max_new, beam, temperature=1.0, unk_penalty=0.0, score0=None, len0=None, score_prompt=False):
         """Prefill the prompts once per sentence into a cache of ``B * beam`` slots -> dict(cache, state, table, x, extra, len0, score0,
         want_ffn): everything :meth:`advance` needs; ``x`` / ``extra`` are the B rows the first selection is made from."""
-        lm, dev = self.lm, self.lm.device
-        if not prompts or any(len(p) < 1 for p in prompts):
-            raise ValueError("generate: every prompt needs at least one token")
-        B, lens = len(prompts), np.asarray([len(p) for p in prompts], dtype=np.int64)
-        off = np.concatenate([[0], np.cumsum(lens)])
-        tokens = torch.tensor([t for p in prompts for t in p], dtype=torch.int64, device=dev)
-        cache = lm.new_cache(B * beam, int(lens.max()) + max_new)
-        view = cache.prompt_view(beam)
-        want_ffn = self.knn is not None and self.knn_keytype == "last_ffn_input"
-        x, extra = lm.prefill(tokens, torch.from_numpy(off.astype(np.int32)), view, want_ffn_input=want_ffn, check=False)
-        cache.spread(view)
+        dev, B = self.lm.device, len(prompts)
+        cache, tokens, lens, x, extra, last, want_ffn = self.prefill(prompts, max_new, beam)
         len0 = np.zeros(B, np.int64) if len0 is None else np.asarray(len0, np.int64)
         score0 = np.zeros(B, np.float32) if score0 is None else np.asarray(score0, np.float32)
         if score_prompt:                                     # log p(prompt[1:] | its own past), as the reference's forced prefix steps score it
             if self.knn is not None and self.lmbda > 0.0:
                 raise ValueError("--score-prompt with --knnlm is not built (the prompt's rows are not searched)")
+            off = np.concatenate([[0], np.cumsum(lens)])
             rows = np.concatenate([np.arange(off[b], off[b + 1] - 1) for b in range(B)]).astype(np.int64)
             tgt = np.concatenate([np.arange(off[b] + 1, off[b + 1]) for b in range(B)]).astype(np.int64)
             score0, len0 = np.zeros(B, np.float32), lens - 1
@@ -127,9 +114,7 @@ class BeamGenerator(Generator):
                 lp = self._head(temperature).target_log_prob(xr if temperature == 1.0 else xr / temperature, tokens[torch.from_numpy(tgt).to(dev)])
                 lp = lp.double().cpu().numpy() - unk_penalty * (tokens.cpu().numpy()[tgt] == UNK)
                 score0 = np.asarray([lp[off[b] - b:off[b + 1] - b - 1].sum() for b in range(B)], np.float32)
-        last = torch.from_numpy(off[1:] - 1).to(dev)
-        x = x[last]
-        extra = {k_: ([v[0][last]] if isinstance(v, list) else v[last]) for k_, v in extra.items()}
+        x, extra = gen_common.last_rows(x, extra, last)
         state = BeamState(B, beam, max_new, cache.len, cache.done, dev, score0)
         table = torch.zeros(B * beam, cache.cap, device=dev, dtype=torch.int32)
         cand = (torch.empty(B * beam, 2 * beam, device=dev, dtype=torch.float32), torch.empty(B * beam, 2 * beam, device=dev, dtype=torch.int64))
@@ -186,41 +171,12 @@ class BeamGenerator(Generator):
 def get_parser():
     import argparse
     p = argparse.ArgumentParser(prog="python -m gnnlm_amd.beam_search", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("data", help="the data directory (DATA/<split>.bin/.idx, optionally dict.txt)")
-    p.add_argument("--path", required=True, help="the --arch transformer_lm* checkpoint")
-    p.add_argument("--model-overrides", default="{}")
-    p.add_argument("--device", default="cuda:0")
-    p.add_argument("--gen-subset", default="test")
-    p.add_argument("--n-prompts", type=int, default=8)
-    p.add_argument("--prompt-len", type=int, default=32)
-    p.add_argument("--prompt-ids", default=None, help="one prompt as comma-separated token ids (instead of cutting prompts from the split)")
-    p.add_argument("--max-len-b", type=int, default=64, help="new tokens per hypothesis before the forced eos")
-    p.add_argument("--beam", type=int, default=5)
+    gen_common.add_common_args(p, beam=5, max_len_help="new tokens per hypothesis before the forced eos",
+                               out_help="write tokens / scores / positional scores / lengths / prompts to this .npz")
     p.add_argument("--nbest", type=int, default=1)
     p.add_argument("--lenpen", type=float, default=1.0)
     p.add_argument("--unnormalized", action="store_true")
-    p.add_argument("--min-len", type=int, default=1, help="eos is forbidden while the hypothesis (the scored prompt included) is shorter")
     p.add_argument("--score-prompt", action="store_true", help="score and count the prompt as the reference's prefix_tokens run does")
-    p.add_argument("--temperature", type=float, default=1.0, help="the GENERATION temperature; the kNN one is --knn-temperature")
-    p.add_argument("--knn-temperature", type=float, default=1.0)
-    p.add_argument("--unkpen", type=float, default=0.0)
-    p.add_argument("--fp16", action="store_true")
-    p.add_argument("--sampling", action="store_true", help="belongs to gnnlm_amd.generate: refused")
-    p.add_argument("--sampling-topk", type=int, default=-1)
-    p.add_argument("--sampling-topp", type=float, default=-1.0, help="not built: refused")
-    p.add_argument("--no-repeat-ngram-size", type=int, default=0, help="not built: refused")
-    p.add_argument("--graph", action="store_true", help="not built (HGTLayer.infer): refused")
-    for name in ("--sweep-lmbda", "--sweep-temperature", "--sweep-k"):
-        p.add_argument(name, default=None, help="belongs to eval_lm: refused")
-    p.add_argument("--knnlm", action="store_true")
-    p.add_argument("--k", type=int, default=1024)
-    p.add_argument("--lmbda", type=float, default=0.25)
-    p.add_argument("--probe", type=int, default=32)
-    p.add_argument("--dstore-dir", default=None)
-    p.add_argument("--index-file", default=None)
-    p.add_argument("--knn-sim-func", default="do_not_recomp_ip")
-    p.add_argument("--knn-keytype", default=None)
-    p.add_argument("--out", default=None, help="write tokens / scores / positional scores / lengths / prompts to this .npz")
     return p
 
 
@@ -228,17 +184,7 @@ def check_args(args):
     """Host only, before any device work: what this build does not compute is refused with the flag's name."""
     if args.sampling or args.sampling_topk > 0:
         raise ValueError("--sampling: beam search does not sample (python -m gnnlm_amd.generate does, at beam 1)")
-    if args.sampling_topp > 0:
-        raise ValueError("--sampling-topp is not built")
-    if args.no_repeat_ngram_size:
-        raise ValueError("--no-repeat-ngram-size is not built")
-    if args.graph:
-        raise ValueError("--graph: generation through the GNN (HGTLayer.infer) is not built")
-    for name in ("sweep_lmbda", "sweep_temperature", "sweep_k"):
-        if getattr(args, name) is not None:
-            raise ValueError(f"--{name.replace('_', '-')} belongs to eval_lm: generation runs one setting")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise NotImplementedError("generation runs in one process (WORLD_SIZE > 1 is not built)")
+    gen_common.check_unbuilt(args)
     if args.beam > MAX_BEAM or args.beam < 1:
         raise ValueError(f"--beam {args.beam}: between 1 and {MAX_BEAM}")
     if not 1 <= args.nbest <= args.beam:
@@ -249,46 +195,24 @@ def check_args(args):
         raise ValueError("--temperature must be greater than 0")
     if args.score_prompt and args.knnlm:
         raise ValueError("--score-prompt with --knnlm is not built (the prompt's rows are not searched)")
-    if args.knnlm and getattr(args, "knn_model", None) is None and not (args.dstore_dir and args.index_file):
-        raise ValueError("--knnlm needs --dstore-dir and --index-file")
-    if args.knnlm and not 0.0 < args.lmbda < 1.0:
-        raise ValueError(f"--lmbda {args.lmbda} with --knnlm: the mixture needs 0 < lmbda < 1 (without kNN: drop --knnlm)")
-    if args.knnlm and args.knn_sim_func not in ("do_not_recomp_ip", "do_not_recomp_l2", "ip", "l2"):
-        raise ValueError("Invalid knn similarity function!")
-    if args.prompt_ids is None and (args.n_prompts < 1 or args.prompt_len < 1):
-        raise ValueError("--n-prompts and --prompt-len must be at least 1")
+    gen_common.check_knn_and_prompts(args)
 
 
 def main(args, model=None, file=None):
     """-> dict(hypotheses (per prompt, best first), prompts).  Prints fairseq's ``S-i`` / ``H-i`` / ``P-i`` lines to ``file`` (stdout)."""
-    import ast
-    from .eval_lm import load_symbols
-    from .transformer_lm import TransformerLM
     check_args(args)
     file = sys.stdout if file is None else file
     device = torch.device(args.device)
     torch.cuda.set_device(device)
-    prompts = _gen.read_prompts(args)
-    if model is None:
-        model, _ = TransformerLM.from_checkpoint(args.path, device, ast.literal_eval(args.model_overrides), precision="fp16" if args.fp16 else None)
-    elif args.fp16:
-        model.precision = "fp16"
+    prompts = read_prompts(args)
+    model = gen_common.load_model(args, device, model)
     logger.info("%d prompt(s), beam %d, up to %d new tokens each, precision %s", len(prompts), args.beam, args.max_len_b, model.precision)
-    knn = None
-    if args.knnlm:
-        from .knn_model import KNNModel
-        knn = getattr(args, "knn_model", None) or KNNModel(
-            index_file=args.index_file, dstore_dir=args.dstore_dir, probe=args.probe, cuda=-1, k=args.k,
-            no_load_keys=("do_not_recomp" in args.knn_sim_func), use_memory=True, metric_type=args.knn_sim_func, device=device)
-        width = getattr(knn, "hidden_size", None)
-        if width is not None and int(width) != model.d:
-            raise ValueError(f"--knnlm: the queries have width {model.d}, the datastore {args.dstore_dir} holds keys of hidden_size {int(width)}")
+    knn = gen_common.load_knn(args, model, device)
     g = BeamGenerator(model, knn, args.knn_keytype, k=args.k if args.knnlm else 0, lmbda=args.lmbda if args.knnlm else 0.0,
                       knn_temperature=args.knn_temperature)
     hyps = g.generate(prompts, args.max_len_b, beam=args.beam, nbest=args.nbest, lenpen=args.lenpen, unnormalized=args.unnormalized,
                       min_len=args.min_len, temperature=args.temperature, unk_penalty=args.unkpen, score_prompt=args.score_prompt)
-    symbols = load_symbols(args.data)
-    word = lambda t: symbols[t] if symbols is not None and 0 <= t < len(symbols) else str(t)
+    word = gen_common.word_of(args.data)
     for i, p in enumerate(prompts):
         print(f"S-{i}\t" + " ".join(word(t) for t in p[1:]), file=file)
         for h in hyps[i]:
@@ -305,19 +229,13 @@ def main(args, model=None, file=None):
             for f, h in enumerate(hs):
                 m = len(h["tokens"])
                 tok[i, f, :m], pos[i, f, :m], score[i, f], raw[i, f], lengths[i, f] = h["tokens"], h["positional_scores"], h["score"], h["raw"], m
-        width = max(len(p) for p in prompts)
-        pr = np.full((len(prompts), width), PAD, dtype=np.int64)
-        for i, p in enumerate(prompts):
-            pr[i, :len(p)] = p
-        np.savez(args.out, tokens=tok, positional_scores=pos, scores=score, raw=raw, lengths=lengths, prompts=pr,
-                 prompt_lengths=np.asarray([len(p) for p in prompts]))
+        pr, pr_len = gen_common.padded_prompts(prompts)
+        np.savez(args.out, tokens=tok, positional_scores=pos, scores=score, raw=raw, lengths=lengths, prompts=pr, prompt_lengths=pr_len)
     return res
 
 
 def cli_main(argv=None):
-    logging.basicConfig(format="%(asctime)s | %(levelname)s | %(name)s | %(message)s", level=os.environ.get("LOGLEVEL", "INFO").upper(),
-                        stream=sys.stderr)
-    main(get_parser().parse_args(argv))
+    gen_common.cli_main(main, get_parser, argv)
 
 
 if __name__ == "__main__":

@@ -76,6 +76,17 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
     return base + idx;
 }
 
+// The last b in [0, n) with off[b] - base <= r, by bisection of an ascending offset table (repeated offsets: the last one wins).
+// base: off[0] of a table that need not start at 0 (gnnlm_ragged_t.block_off).  Wave-uniform when r is.
+__device__ __forceinline__ int last_block(const int32_t* off, int n, int64_t r, int64_t base = 0) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)off[mid] - base <= r) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 // Cross-lane reductions on the VALU (DPP + the gfx950 permlane swaps): no LDS round trips, unlike
 // __shfl_xor (ds_bpermute_b32).  Fixed combination order, every lane ends up with the result.
 //   row16_*: over the 16 lanes of a DPP row;  half32_*: over lanes 0..31 / 32..63;  wave_*: all 64.

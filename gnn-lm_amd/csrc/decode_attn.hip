@@ -26,7 +26,7 @@ struct DecParams {
     float* out; int64_t ldo;
     int B, H, n_chunk;
     int32_t* keys_out;                     // profiling only (else nullptr): the keys the launch really attends, summed over b
-    const int32_t* src; int64_t ld_src;    // IND only (gnnlm_beam_attn): key row u < len of b is row u of cache sequence src[b][u]
+    SlotTable tab;                         // IND only (gnnlm_beam_attn): key row u < len of b is row u of cache sequence src[b][u]
 };
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void decode_attn_chunk_kernel(DecParams p) {
         st4(vb + (int64_t)len * p.ld_row, ld4(vnp));
     }
     const float4 q4 = ld4(qp);
-    [[maybe_unused]] const int32_t* tab = IND ? p.src + b * p.ld_src : nullptr;
+    [[maybe_unused]] const int32_t* tab = IND ? p.tab.src + b * p.tab.ld : nullptr;
     [[maybe_unused]] bool bad = false;
     float m = -INFINITY, s = 0.f;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -209,11 +209,7 @@ __global__ __launch_bounds__(256) void kv_cache_fill_kernel(FillParams p) {
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= p.n_tok) return;
     const int64_t base = p.block_off[0];
-    int lo = 0, hi = p.n_blocks;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((int64_t)p.block_off[mid] - base <= r) lo = mid; else hi = mid;
-    }
+    const int lo = last_block(p.block_off, p.n_blocks, r, base);
     const int64_t t = r - ((int64_t)p.block_off[lo] - base);
     if (t < 0 || t >= p.max_rows) return;                  // (the host refused a block longer than the cache: memory safety only)
     const float4* ks = reinterpret_cast<const float4*>(p.src + r * p.ld_src) + p.d4;
@@ -258,8 +254,20 @@ size_t decode_attn_workspace_bytes(int B, int H, int dk, int max_len) {
 }
 
 namespace {
-// src == nullptr: gnnlm_decode_attn, its two launches as they always were; else gnnlm_beam_attn
-int decode_attn_launch(const gnnlm_decode_attn_t& d, const int32_t* src, int64_t ld_src, bool beam, hipStream_t stream) {
+template <bool IND>
+void launch_dec(int dk, dim3 g1, dim3 g2, hipStream_t stream, const DecParams& p) {
+#define GNNLM_DEC(DK)                                                                                  \
+    case DK:                                                                                           \
+        hipLaunchKernelGGL((decode_attn_chunk_kernel<DK, IND>), g1, dim3(256), 0, stream, p);          \
+        hipLaunchKernelGGL((decode_attn_combine_kernel<DK, IND>), g2, dim3(64), 0, stream, p);         \
+        break;
+    switch (dk) { GNNLM_DEC(16) GNNLM_DEC(32) GNNLM_DEC(64) GNNLM_DEC(128) }
+#undef GNNLM_DEC
+}
+}  // namespace
+
+// tab == nullptr: gnnlm_decode_attn, its two launches as they always were; else gnnlm_beam_attn
+int decode_attn(const gnnlm_decode_attn_t& d, const SlotTable* tab, hipStream_t stream) {
     const gnnlm_kv_cache_t& c = d.cache;
     GNNLM_REQUIRE(decode_attn_ok(d.dk), "decode_attn: d_k must be 16, 32, 64 or 128");
     int rc = check_kv_cache(c);
@@ -268,9 +276,9 @@ int decode_attn_launch(const gnnlm_decode_attn_t& d, const int32_t* src, int64_t
     GNNLM_REQUIRE(d.layer >= 0 && d.layer < c.L, "decode_attn: layer outside [0, L)");
     GNNLM_REQUIRE(d.max_len >= 0 && d.max_len <= c.cap, "decode_attn: max_len outside [0, cap]");
     GNNLM_REQUIRE(d.ld >= c.d && d.ld % 4 == 0 && d.ldo >= c.d && d.ldo % 4 == 0, "decode_attn: ld / ldo must be multiples of 4 and >= H * d_k");
-    if (beam) GNNLM_REQUIRE(ld_src >= c.cap, "beam_attn: ld_src < cache.cap");
+    if (tab) GNNLM_REQUIRE(tab->ld >= c.cap, "beam_attn: ld_src < cache.cap");
     if (c.B == 0) return OK;
-    if (beam) GNNLM_REQUIRE(src && (uintptr_t)src % 4 == 0, "beam_attn: src missing or misaligned");
+    if (tab) GNNLM_REQUIRE(tab->src && (uintptr_t)tab->src % 4 == 0, "beam_attn: src missing or misaligned");
     GNNLM_REQUIRE(d.q && d.k_new && d.v_new && d.out, "decode_attn: q / k_new / v_new / out missing");
     GNNLM_REQUIRE(((uintptr_t)d.q | (uintptr_t)d.k_new | (uintptr_t)d.v_new | (uintptr_t)d.out) % 16 == 0, "decode_attn: q / k_new / v_new / out must be 16-byte aligned");
     const int bound = d.max_len ? d.max_len : c.cap;
@@ -278,39 +286,21 @@ int decode_attn_launch(const gnnlm_decode_attn_t& d, const int32_t* src, int64_t
     GNNLM_REQUIRE(d.workspace && (uintptr_t)d.workspace % 16 == 0 && d.workspace_bytes >= need, "decode_attn: workspace missing, misaligned or too small");
     DecParams p{d.q, d.k_new, d.v_new, d.ld, c.k + d.layer * c.ld_layer, c.v + d.layer * c.ld_layer, c.ld_row, c.ld_seq, bound,
                 c.len, c.done, c.n_bad, reinterpret_cast<float*>(d.workspace), d.out, d.ldo, c.B, d.H, (int)cdiv(bound, CHUNK), nullptr,
-                src, ld_src};
+                tab ? *tab : SlotTable{}};
     const int64_t items = (int64_t)c.B * d.H * p.n_chunk;
     GNNLM_REQUIRE(cdiv(items, 4) < (1ll << 31), "decode_attn: too many chunks for one launch");
     // work: K and V read once, the partials written and read once -- stated for B * bound keys, which is all the host knows, and
     // scaled by the keys the rows really hold (sum of len[b] + 1), which the combine kernel reports when a profile is open
     ProfScope prof(K_CAUSAL, stream, 4.0 * c.B * bound * c.d,
-                   8.0 * c.B * bound * c.d + 8.0 * items * (d.dk + 4) + 16.0 * c.B * c.d + (beam ? 4.0 * d.H * c.B * bound : 0.0),
+                   8.0 * c.B * bound * c.d + 8.0 * items * (d.dk + 4) + 16.0 * c.B * c.d + (tab ? 4.0 * d.H * c.B * bound : 0.0),
                    c.len, (double)c.B * bound, true);
     if (!prof.slot) prof.sd = nullptr;                        // (no slot to be had: the bound stands, unscaled)
     p.keys_out = prof.slot;
     const dim3 g1((unsigned)cdiv(items, 4)), g2((unsigned)cdiv((int64_t)c.B * d.H, 256 / d.dk));
-#define GNNLM_DEC(DK)                                                                                  \
-    case DK:                                                                                           \
-        hipLaunchKernelGGL(decode_attn_chunk_kernel<DK>, g1, dim3(256), 0, stream, p);                 \
-        hipLaunchKernelGGL(decode_attn_combine_kernel<DK>, g2, dim3(64), 0, stream, p);                \
-        break;
-#define GNNLM_DEC_IND(DK)                                                                              \
-    case DK:                                                                                           \
-        hipLaunchKernelGGL((decode_attn_chunk_kernel<DK, true>), g1, dim3(256), 0, stream, p);         \
-        hipLaunchKernelGGL((decode_attn_combine_kernel<DK, true>), g2, dim3(64), 0, stream, p);        \
-        break;
-    if (!beam) switch (d.dk) { GNNLM_DEC(16) GNNLM_DEC(32) GNNLM_DEC(64) GNNLM_DEC(128) }
-    else switch (d.dk) { GNNLM_DEC_IND(16) GNNLM_DEC_IND(32) GNNLM_DEC_IND(64) GNNLM_DEC_IND(128) }
-#undef GNNLM_DEC
-#undef GNNLM_DEC_IND
+    if (tab) launch_dec<true>(d.dk, g1, g2, stream, p);
+    else launch_dec<false>(d.dk, g1, g2, stream, p);
     GNNLM_LAUNCH_CHECK();
     return OK;
-}
-}  // namespace
-
-int decode_attn(const gnnlm_decode_attn_t& d, hipStream_t stream) { return decode_attn_launch(d, nullptr, 0, false, stream); }
-int beam_attn(const gnnlm_decode_attn_t& d, const int32_t* src, int64_t ld_src, hipStream_t stream) {
-    return decode_attn_launch(d, src, ld_src, true, stream);
 }
 
 int kv_cache_fill(const float* qkv, int64_t ld_src, const gnnlm_kv_cache_t& c, int layer, const gnnlm_ragged_t& rg, int max_rows,
@@ -349,11 +339,12 @@ size_t gnnlm_decode_attn_workspace_bytes(int32_t B, int32_t H, int32_t dk, int32
 }
 int gnnlm_decode_attn(const gnnlm_decode_attn_t* d, void* stream) {
     GNNLM_DESC(d);
-    return decode_attn(*d, (hipStream_t)stream);
+    return decode_attn(*d, nullptr, (hipStream_t)stream);
 }
 int gnnlm_beam_attn(const gnnlm_beam_attn_t* d, void* stream) {
     GNNLM_DESC(d);
-    return beam_attn(d->a, d->src, d->ld_src, (hipStream_t)stream);
+    const SlotTable tab{d->src, d->ld_src};
+    return decode_attn(d->a, &tab, (hipStream_t)stream);
 }
 
 }  // extern "C"

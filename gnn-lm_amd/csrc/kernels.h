@@ -126,9 +126,10 @@ int causal_attn_varlen(const float* Q, const float* K, const float* V, int64_t l
 bool decode_attn_ok(int dk);
 int check_kv_cache(const gnnlm_kv_cache_t& c);
 size_t decode_attn_workspace_bytes(int B, int H, int dk, int max_len);
-int decode_attn(const gnnlm_decode_attn_t& d, hipStream_t stream);
-// the same through a table of cache slots (gnnlm_beam_attn): key row u < len of sequence b is row u of sequence src[b][u]
-int beam_attn(const gnnlm_decode_attn_t& d, const int32_t* src, int64_t ld_src, hipStream_t stream);
+// a table of cache slots (gnnlm_beam_attn): key row u < len of sequence b is row u of sequence src[b * ld + u]
+struct SlotTable { const int32_t* src; int64_t ld; };
+// tab == nullptr: every sequence reads its own rows (gnnlm_decode_attn); else through the table
+int decode_attn(const gnnlm_decode_attn_t& d, const SlotTable* tab, hipStream_t stream);
 // one beam-search step of every sentence (beam.hip)
 int beam_select(const gnnlm_beam_select_t& d, hipStream_t stream);
 // K' | V' of the packed q | k | v rows [n_tok, ld_src] -> cache rows [0, min(len_b, max_rows)) of sequence b = block b of `layer`

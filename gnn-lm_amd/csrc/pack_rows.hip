@@ -34,11 +34,7 @@ __global__ __launch_bounds__(256) void pack_check_kernel(PackParams p, int32_t* 
 
 // -> the source row of output row r, or -1 when the tables do not describe one inside [0, n_tok) (wave-uniform).
 __device__ __forceinline__ int64_t source_row(const PackParams& p, int64_t r) {
-    int lo = 0, hi = p.n_blocks;                      // the last b with out_off[b] <= r (empty blocks repeat an offset: the last one wins)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((int64_t)p.out_off[mid] <= r) lo = mid; else hi = mid;
-    }
+    const int lo = last_block(p.out_off, p.n_blocks, r);    // (empty blocks repeat an offset: the last one wins)
     const int64_t j = r - p.out_off[lo];
     const int64_t b0 = (int64_t)p.block_off[lo] - p.block_off[0], b1 = (int64_t)p.block_off[lo + 1] - p.block_off[0];
     const int64_t sk = p.skip ? p.skip[lo] : 0;

@@ -35,7 +35,7 @@ import time
 import numpy as np
 import torch
 
-from . import ops
+from . import gen_common, ops
 
 logger = logging.getLogger("gnnlm_amd.eval_lm")
 
@@ -70,8 +70,7 @@ def check_args(args):
     """Host only, before any device work -> ``(sweep, topk)``: the tuning grid ``(ks, temperatures, lmbdas)`` of --sweep-* or None, and
     N of --output-topk (0: off), both as the --graph driver reads them (``eval_lm.parse_sweep`` / ``check_output_topk``)."""
     from .eval_lm import check_output_topk, parse_sweep
-    if args.knnlm and getattr(args, "knn_model", None) is None and not (args.dstore_dir and args.index_file):
-        raise ValueError("--knnlm needs --dstore-dir and --index-file")
+    gen_common.check_knn_store(args)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise NotImplementedError("the base LM path runs in one process (WORLD_SIZE > 1 is not built)")
     if getattr(args, "graph_capture", False):
@@ -84,8 +83,7 @@ def check_args(args):
     topk = check_output_topk(args)                               # (not with --sweep-*, --save-knnlm-dstore)
     if args.output_knn_recall and not args.knnlm:
         raise ValueError("--output-knn-recall needs --knnlm")
-    if args.knnlm and args.knn_sim_func not in ("do_not_recomp_ip", "do_not_recomp_l2", "ip", "l2"):
-        raise ValueError("Invalid knn similarity function!")
+    gen_common.check_knn_sim_func(args)
     if getattr(args, "reinit_nfeat", False):
         raise ValueError("--reinit-nfeat belongs to the --graph path")
     if args.add_bos_token:
@@ -102,8 +100,6 @@ def main(args, model=None):
     from .eval_lm import (DstoreWriter, budget_batches, check_break_mode, fairseq_token_stream, report_result, report_sweep, report_topk,
                           sample_blocks, word_output_setup, word_outputs, write_result_json)
     from .ragged import BlockTable, packed_rows
-    from .transformer_lm import TransformerLM
-    import ast
     sweep, topk = check_args(args)
     break_mode = check_break_mode(args)
     w = int(args.context_window)
@@ -120,10 +116,7 @@ def main(args, model=None):
     n_tok = int(stream_np.shape[0])
     if n_tok == 0:
         raise ValueError("the split is empty")
-    if model is None:
-        model, _ = TransformerLM.from_checkpoint(args.path, device, ast.literal_eval(args.model_overrides), precision="fp16" if args.fp16 else None)
-    elif args.fp16:
-        model.precision = "fp16"
+    model = gen_common.load_model(args, device, model)
     if args.fp16:
         logger.info("--fp16: float16 matrix-core GEMMs with float32 accumulation (transformer layers and output layer); embedding, "
                     "attention and LayerNorm stay float32")
@@ -155,16 +148,10 @@ def main(args, model=None):
     keytype = args.knn_keytype or None
     # ---- kNN-LM (sequence_scorer.py:102-136): the store, and the split's tables of ops.pack_rows -- how many rows in front of every
     # sample are context, and where its scored rows start among the batch's (offsets relative to the batch: n + 1 entries per batch)
-    knn, search, pack = None, False, None
-    if args.knnlm:
-        from .knn_model import KNNModel
-        knn = getattr(args, "knn_model", None) or KNNModel(
-            index_file=args.index_file, dstore_dir=args.dstore_dir, probe=args.probe, cuda=-1, k=args.k,
-            no_load_keys=("do_not_recomp" in args.knn_sim_func), use_memory=True, metric_type=args.knn_sim_func, device=device)
-        width = getattr(knn, "hidden_size", None)
-        if width is not None and int(width) != model.d:
-            raise ValueError(f"--knnlm: the queries are the base LM's {'last_ffn_input' if keytype == 'last_ffn_input' else 'inner_states[-1]'} "
-                             f"rows of width {model.d}, the datastore {args.dstore_dir} holds keys of hidden_size {int(width)}")
+    search, pack = False, None
+    knn = gen_common.load_knn(args, model, device,
+                              f"are the base LM's {'last_ffn_input' if keytype == 'last_ffn_input' else 'inner_states[-1]'} rows of")
+    if knn is not None:
         search = args.lmbda > 0.0 or sweep is not None                  # :102 -- `--lmbda 0` scores the LM alone; a sweep always searches
         if search and args.knn_sim_func in ("ip", "l2") and hasattr(knn, "keys_home"):
             logger.info(knn.keys_home())

@@ -30,12 +30,12 @@ import sys
 import numpy as np
 import torch
 
-from . import ops
+from . import gen_common, ops
+from .gen_common import EOS, PAD, UNK
 from .predict import MAX_TOPK, head_vocab
 
 logger = logging.getLogger("gnnlm_amd.generate")
 
-PAD, EOS, UNK = 1, 2, 3         # fairseq Dictionary
 DONE_EVERY = 16                 # steps between two looks at `done`
 
 
@@ -79,15 +79,26 @@ class Generator:
 
     @staticmethod
     def check(max_new, sampling, sampling_topk, temperature, V):
-        if max_new < 1:
-            raise ValueError("max_new (--max-len-b) must be at least 1")
-        if not temperature > 0:
-            raise ValueError("--temperature must be greater than 0")
+        gen_common.check_decode(max_new, temperature)
         if sampling and sampling_topk < 1:
             raise ValueError("--sampling without --sampling-topk (pure sampling over the vocabulary) is not built")
         if sampling and sampling_topk > MAX_TOPK:
             raise ValueError(f"--sampling-topk {sampling_topk}: at most {MAX_TOPK} (gnnlm_topk_merge's k)")
         return min(sampling_topk, V) if sampling else 1
+
+    def prefill(self, prompts, room, beam=None):
+        """Pack the prompts and prefill them into a new cache with ``room`` rows behind the longest -> ``(cache, tokens, lens, x, extra,
+        last, want_ffn)``: ``x`` / ``extra`` over ALL packed rows, ``last`` the rows the first pick is made from
+        (``gen_common.last_rows``).  ``beam``: the cache has ``beam`` slots per prompt, the prompt stored once, in the first."""
+        lm = self.lm
+        tokens, off, lens, last = gen_common.pack_prompts(prompts, lm.device)
+        cache = lm.new_cache(len(prompts) * (beam or 1), int(lens.max()) + room)
+        into = cache if beam is None else cache.prompt_view(beam)
+        want_ffn = self.knn is not None and self.knn_keytype == "last_ffn_input"
+        x, extra = lm.prefill(tokens, off, into, want_ffn_input=want_ffn, check=False)
+        if beam is not None:
+            cache.spread(into)
+        return cache, tokens, lens, x, extra, last, want_ffn
 
     def generate(self, prompts, max_new, sampling=False, sampling_topk=-1, temperature=1.0, unk_penalty=0.0, seed=None):
         """prompts: a list of non-empty lists of token ids, fed as they are -> ``(tokens int64 [B, max_new], logp f32 [B, max_new],
@@ -95,17 +106,9 @@ class Generator:
         behind it; ``logp`` the picks' own log-probabilities."""
         lm, dev = self.lm, self.lm.device
         k = self.check(max_new, sampling, sampling_topk, float(temperature), self.vocab)
-        if not prompts or any(len(p) < 1 for p in prompts):
-            raise ValueError("generate: every prompt needs at least one token")
-        B, lens = len(prompts), np.asarray([len(p) for p in prompts], dtype=np.int64)
-        off = np.concatenate([[0], np.cumsum(lens)])
-        tokens = torch.tensor([t for p in prompts for t in p], dtype=torch.int64, device=dev)
-        cache = lm.new_cache(B, int(lens.max()) + max_new - 1)
-        want_ffn = self.knn is not None and self.knn_keytype == "last_ffn_input"
-        x, extra = lm.prefill(tokens, torch.from_numpy(off.astype(np.int32)), cache, want_ffn_input=want_ffn, check=False)
-        last = torch.from_numpy(off[1:] - 1).to(dev)
-        x = x[last]
-        extra = {k_: ([v[0][last]] if isinstance(v, list) else v[last]) for k_, v in extra.items()}
+        cache, _, _, x, extra, last, want_ffn = self.prefill(prompts, max_new - 1)
+        x, extra = gen_common.last_rows(x, extra, last)
+        B = len(prompts)
         out = torch.full((B, max_new), PAD, dtype=torch.int64, device=dev)
         out_lp = torch.zeros(B, max_new, dtype=torch.float32, device=dev)
         best_val = torch.empty(B, k, dtype=torch.float32, device=dev)
@@ -139,41 +142,9 @@ class Generator:
 # ------------------------------------------------------------------------------------------------ the driver
 def get_parser():
     p = argparse.ArgumentParser(prog="python -m gnnlm_amd.generate", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("data", help="the data directory (DATA/<split>.bin/.idx, optionally dict.txt)")
-    p.add_argument("--path", required=True, help="the --arch transformer_lm* checkpoint")
-    p.add_argument("--model-overrides", default="{}")
-    p.add_argument("--device", default="cuda:0")
-    p.add_argument("--gen-subset", default="test")
-    p.add_argument("--n-prompts", type=int, default=8)
-    p.add_argument("--prompt-len", type=int, default=32)
-    p.add_argument("--prompt-ids", default=None, help="one prompt as comma-separated token ids (instead of cutting prompts from the split)")
-    p.add_argument("--max-len-b", type=int, default=64, help="tokens to generate per prompt (fairseq: max_len = a * src_len + b with a = 0)")
-    p.add_argument("--sampling", action="store_true")
-    p.add_argument("--sampling-topk", type=int, default=-1)
-    p.add_argument("--sampling-topp", type=float, default=-1.0, help="not built: refused")
-    p.add_argument("--temperature", type=float, default=1.0,
-                   help="the GENERATION temperature (fairseq/options.py:548): the decoder output is divided by it.  The kNN temperature, "
-                        "which eval_lm calls --temperature (options.py:496), is --knn-temperature here")
-    p.add_argument("--knn-temperature", type=float, default=1.0, help="the temperature of the kNN distribution (eval_lm's --temperature)")
-    p.add_argument("--unkpen", type=float, default=0.0)
+    gen_common.add_common_args(p, beam=1, max_len_help="tokens to generate per prompt (fairseq: max_len = a * src_len + b with a = 0)",
+                               out_help="write tokens / logp / lengths / prompts to this .npz")
     p.add_argument("--seed", type=int, default=1)
-    p.add_argument("--fp16", action="store_true")
-    p.add_argument("--beam", type=int, default=1, help="beam search is not built: anything but 1 is refused")
-    p.add_argument("--no-repeat-ngram-size", type=int, default=0, help="not built: refused")
-    p.add_argument("--min-len", type=int, default=1, help="not built: anything but 1 is refused")
-    p.add_argument("--graph", action="store_true", help="not built (HGTLayer.infer): refused")
-    for name in ("--sweep-lmbda", "--sweep-temperature", "--sweep-k"):
-        p.add_argument(name, default=None, help="belongs to eval_lm: refused")
-    p.add_argument("--knnlm", action="store_true")
-    p.add_argument("--k", type=int, default=1024)
-    p.add_argument("--lmbda", type=float, default=0.25, help="weight of the kNN distribution with --knnlm; 0 is refused (it would load the "
-                   "datastore and generate from the base LM alone: drop --knnlm for that)")
-    p.add_argument("--probe", type=int, default=32)
-    p.add_argument("--dstore-dir", default=None)
-    p.add_argument("--index-file", default=None)
-    p.add_argument("--knn-sim-func", default="do_not_recomp_ip")
-    p.add_argument("--knn-keytype", default=None)
-    p.add_argument("--out", default=None, help="write tokens / logp / lengths / prompts to this .npz")
     return p
 
 
@@ -181,28 +152,11 @@ def check_args(args):
     """Host only, before any device work: what this build does not compute is refused with the flag's name."""
     if args.beam != 1:
         raise ValueError(f"--beam {args.beam}: this driver decodes at --beam 1 only; beam search is python -m gnnlm_amd.beam_search")
-    if args.sampling_topp > 0:
-        raise ValueError("--sampling-topp is not built")
-    if args.no_repeat_ngram_size:
-        raise ValueError("--no-repeat-ngram-size is not built")
     if args.min_len != 1:
         raise ValueError(f"--min-len {args.min_len} is not built (only --min-len 1)")
-    if args.graph:
-        raise ValueError("--graph: generation through the GNN (HGTLayer.infer) is not built")
-    for name in ("sweep_lmbda", "sweep_temperature", "sweep_k"):
-        if getattr(args, name) is not None:
-            raise ValueError(f"--{name.replace('_', '-')} belongs to eval_lm: generation runs one setting")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise NotImplementedError("generation runs in one process (WORLD_SIZE > 1 is not built)")
+    gen_common.check_unbuilt(args)
     Generator.check(args.max_len_b, args.sampling, args.sampling_topk, args.temperature, MAX_TOPK)
-    if args.knnlm and getattr(args, "knn_model", None) is None and not (args.dstore_dir and args.index_file):
-        raise ValueError("--knnlm needs --dstore-dir and --index-file")
-    if args.knnlm and not 0.0 < args.lmbda < 1.0:
-        raise ValueError(f"--lmbda {args.lmbda} with --knnlm: the mixture needs 0 < lmbda < 1 (without kNN: drop --knnlm)")
-    if args.knnlm and args.knn_sim_func not in ("do_not_recomp_ip", "do_not_recomp_l2", "ip", "l2"):
-        raise ValueError("Invalid knn similarity function!")
-    if args.prompt_ids is None and (args.n_prompts < 1 or args.prompt_len < 1):
-        raise ValueError("--n-prompts and --prompt-len must be at least 1")
+    gen_common.check_knn_and_prompts(args)
 
 
 def read_prompts(args):
@@ -227,54 +181,34 @@ def read_prompts(args):
 
 def main(args, model=None, file=None):
     """-> dict(tokens, logp, lengths (numpy), prompts).  Prints fairseq's ``S-i`` / ``H-i`` lines to ``file`` (stdout)."""
-    import ast
-    from .eval_lm import load_symbols
-    from .transformer_lm import TransformerLM
     check_args(args)
     file = sys.stdout if file is None else file
     device = torch.device(args.device)
     torch.cuda.set_device(device)
     prompts = read_prompts(args)
-    if model is None:
-        model, _ = TransformerLM.from_checkpoint(args.path, device, ast.literal_eval(args.model_overrides), precision="fp16" if args.fp16 else None)
-    elif args.fp16:
-        model.precision = "fp16"
+    model = gen_common.load_model(args, device, model)
     logger.info("%d prompt(s), up to %d new tokens each, %s, precision %s", len(prompts), args.max_len_b,
                 f"top-{args.sampling_topk} sampling at temperature {args.temperature}" if args.sampling else "greedy", model.precision)
-    knn = None
-    if args.knnlm:
-        from .knn_model import KNNModel
-        knn = getattr(args, "knn_model", None) or KNNModel(
-            index_file=args.index_file, dstore_dir=args.dstore_dir, probe=args.probe, cuda=-1, k=args.k,
-            no_load_keys=("do_not_recomp" in args.knn_sim_func), use_memory=True, metric_type=args.knn_sim_func, device=device)
-        width = getattr(knn, "hidden_size", None)
-        if width is not None and int(width) != model.d:
-            raise ValueError(f"--knnlm: the queries have width {model.d}, the datastore {args.dstore_dir} holds keys of hidden_size {int(width)}")
+    knn = gen_common.load_knn(args, model, device)
     g = Generator(model, knn, args.knn_keytype, k=args.k if args.knnlm else 0, lmbda=args.lmbda if args.knnlm else 0.0,
                   knn_temperature=args.knn_temperature)
     tokens, logp, lengths = g.generate(prompts, args.max_len_b, sampling=args.sampling, sampling_topk=args.sampling_topk,
                                        temperature=args.temperature, unk_penalty=args.unkpen, seed=args.seed)
     tokens, logp, lengths = tokens.cpu().numpy(), logp.cpu().numpy(), lengths.cpu().numpy()
-    symbols = load_symbols(args.data)
-    word = lambda t: symbols[t] if symbols is not None and 0 <= t < len(symbols) else str(t)
+    word = gen_common.word_of(args.data)
     for i, p in enumerate(prompts):
         n = int(lengths[i])
         print(f"S-{i}\t" + " ".join(word(t) for t in p[1:]), file=file)
         print(f"H-{i}\t{float(logp[i, :n].astype(np.float64).sum())}\t" + " ".join(word(int(t)) for t in tokens[i, :n]), file=file)
     res = {"tokens": tokens, "logp": logp, "lengths": lengths, "prompts": prompts}
     if args.out:
-        width = max(len(p) for p in prompts)
-        pr = np.full((len(prompts), width), PAD, dtype=np.int64)
-        for i, p in enumerate(prompts):
-            pr[i, :len(p)] = p
-        np.savez(args.out, tokens=tokens, logp=logp, lengths=lengths, prompts=pr, prompt_lengths=np.asarray([len(p) for p in prompts]))
+        pr, pr_len = gen_common.padded_prompts(prompts)
+        np.savez(args.out, tokens=tokens, logp=logp, lengths=lengths, prompts=pr, prompt_lengths=pr_len)
     return res
 
 
 def cli_main(argv=None):
-    logging.basicConfig(format="%(asctime)s | %(levelname)s | %(name)s | %(message)s", level=os.environ.get("LOGLEVEL", "INFO").upper(),
-                        stream=sys.stderr)
-    main(get_parser().parse_args(argv))
+    gen_common.cli_main(main, get_parser, argv)
 
 
 if __name__ == "__main__":

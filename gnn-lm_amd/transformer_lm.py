@@ -245,22 +245,14 @@ class TransformerLM:
         if tokens.dtype != torch.int64 or tokens.shape != (cache.B,):
             raise TypeError("step: tokens must be int64 [B]")
         ld_src = ops._src_table(src, cache.B, cache.cap, "step") if src is not None else 0
-        if not tokens.is_cuda or not tokens.is_contiguous():
-            raise _lib.GnnlmError("gnnlm_amd kernels need contiguous device (HIP) tensors; there is no CPU fallback")
+        self._need_device(tokens)
         bound = cache.steps + 1 if max_len is None else int(max_len)
         # the table of new_cache: cache.cap positions, whatever the bound (a cache made by hand is served here, once)
         m = self._desc(self._positions(cache.cap))
         c = cache.desc()
         io = _lib.gnnlm_tlm_step_io_t()
         io.tokens, io.max_len = tokens.data_ptr(), bound
-        new = lambda: torch.empty(cache.B, self.d, device=tokens.device, dtype=torch.float32)
-        x = new()
-        inner = new() if want_inner else None
-        ffn_in = new() if want_ffn_input else None
-        io.out = x.data_ptr()
-        io.last_inner = inner.data_ptr() if inner is not None else None
-        io.last_ffn_input = ffn_in.data_ptr() if ffn_in is not None else None
-        io.n_bad = self.n_bad.data_ptr()
+        x, extra = self._outputs(io, cache.B, tokens.device, want_inner, want_ffn_input)
         L = _lib.lib()
         need = L.gnnlm_transformer_lm_step_workspace_bytes(ctypes.byref(m), ctypes.byref(c), ctypes.byref(io))
         ws = self._workspace(need, tokens.device)
@@ -271,6 +263,24 @@ class TransformerLM:
             _lib.check(L.gnnlm_transformer_lm_step_beam(ctypes.byref(m), ctypes.byref(c), ctypes.byref(io), ctypes.c_void_p(src.data_ptr()),
                                                         ld_src, _lib.ptr(ws), ws.numel(), _lib.stream()), "gnnlm_transformer_lm_step_beam")
         cache.steps += 1                                        # (replays of a captured step: the caller adds them)
+        return x, extra
+
+    @staticmethod
+    def _need_device(tokens):
+        if not tokens.is_cuda or not tokens.is_contiguous():
+            raise _lib.GnnlmError("gnnlm_amd kernels need contiguous device (HIP) tensors; there is no CPU fallback")
+
+    def _outputs(self, io, n, device, want_inner, want_ffn_input):
+        """Allocate ``x`` [n, d] and the wanted ones of ``inner_states[-1]`` / ``last_ffn_input``, point ``io`` (either io descriptor) at
+        them and at ``n_bad`` -> ``(x, extra)`` as :meth:`extract_features` returns them."""
+        new = lambda: torch.empty(n, self.d, device=device, dtype=torch.float32)
+        x = new()
+        inner = new() if want_inner else None
+        ffn_in = new() if want_ffn_input else None
+        io.out = x.data_ptr()
+        io.last_inner = inner.data_ptr() if inner is not None else None
+        io.last_ffn_input = ffn_in.data_ptr() if ffn_in is not None else None
+        io.n_bad = self.n_bad.data_ptr()
         extra = {"inner_states": [inner]}
         if ffn_in is not None:
             extra["last_ffn_input"] = ffn_in
@@ -287,8 +297,7 @@ class TransformerLM:
         from .ragged import as_ragged
         if tokens.dtype != torch.int64 or tokens.dim() != 1:
             raise TypeError("extract_features: tokens must be int64 [n_tok]")
-        if not tokens.is_cuda or not tokens.is_contiguous():
-            raise _lib.GnnlmError("gnnlm_amd kernels need contiguous device (HIP) tensors; there is no CPU fallback")
+        self._need_device(tokens)
         rg = as_ragged(block_off, tokens.device)
         n = rg.n_tok
         if n != tokens.shape[0]:
@@ -297,14 +306,7 @@ class TransformerLM:
         m = self._desc(self._positions(max_len))
         io = _lib.gnnlm_tlm_io_t()
         io.tokens, io.blocks, io.max_len = tokens.data_ptr(), rg.desc(), max_len
-        new = lambda: torch.empty(n, self.d, device=tokens.device, dtype=torch.float32)
-        x = new()
-        inner = new() if want_inner else None
-        ffn_in = new() if want_ffn_input else None
-        io.out = x.data_ptr()
-        io.last_inner = inner.data_ptr() if inner is not None else None
-        io.last_ffn_input = ffn_in.data_ptr() if ffn_in is not None else None
-        io.n_bad = self.n_bad.data_ptr()
+        x, extra = self._outputs(io, n, tokens.device, want_inner, want_ffn_input)
         L = _lib.lib()
         need = L.gnnlm_transformer_lm_workspace_bytes(ctypes.byref(m), ctypes.byref(io))
         ws = self._workspace(need, tokens.device)
@@ -318,9 +320,6 @@ class TransformerLM:
             cache.steps = max_len
         if check:
             self.check_tokens()
-        extra = {"inner_states": [inner if inner is not None else None]}
-        if ffn_in is not None:
-            extra["last_ffn_input"] = ffn_in
         return x, extra
 
     def check_tokens(self):
