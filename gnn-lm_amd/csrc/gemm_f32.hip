@@ -16,9 +16,9 @@
 // halves (half h of a float4 read covers k = 8s+4h..+3); the MFMA sums over k, so A and W only have
 // to agree on the permutation.  Global->LDS staging goes through registers with the next k-tile's loads
 // in flight under the current tile's MFMAs; ONE LDS buffer and two barriers per k-tile at 3 waves per SIMD
-// measured faster than two buffers at 2 waves per SIMD.  (Problems with K % 32 == 0 on 128x128 tiles
-// take gemm_f32_dma.hip instead: same tile, LDS-DMA staging; this kernel keeps the ragged-K, short-K and
-// 64x64 cases and the in-kernel split-bf16 modes.)
+// measured faster than two buffers at 2 waves per SIMD.  (gemm_route.h says which problems take this
+// kernel: the ragged-K, short-K and 64x64 cases and the in-kernel split-bf16 modes; the others go to the
+// kernels of gemm_f32_sched.hip, gemm_f32_dma.hip, gemm_f32_skinny.hip and gemm_split.hip.)
 //
 // Work list: the grid is a pool of resident workgroups walking the list of (batch, tile) pairs; list
 // position -> pool slot through xcd_remap, so every XCD (block b runs on XCD b % 8, speed only) walks a
@@ -31,6 +31,7 @@
 // tile and a token's 64 logits of a wave's slab sit in registers of two lanes; (max, sum exp) per
 // (row, 64-column slab) goes to part[row][slab] -- the logits matrix (164 MB per 2048-token step for the
 // WikiText-103 head) is never materialised.  Details in gemm_epilogue.inc.
+#include "gemm_route.h"
 #include "kernels.h"
 
 namespace gnnlm {
@@ -41,10 +42,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 constexpr int BK = 32, LDS_LD = BK + 4;
-#ifndef GNNLM_GEMM_NBUF
-#define GNNLM_GEMM_NBUF 1
-#endif
-constexpr int NBUF = GNNLM_GEMM_NBUF;
 enum { EPI_STORE = 0, EPI_LSE = 1 };
 
 // round-to-nearest-even f32 -> bf16 (bit pattern in the low 16 bits)
@@ -69,7 +66,7 @@ __global__ __launch_bounds__(256, 3) void gemm_nt_f32_kernel(const GemmParams p)
     constexpr int STAGE = (BM + BN) * LDS_LD;
     constexpr int SPLIT_LD = 20;                         // floats (80 B) per bf16 row of 32 k: conflict-free b128 reads
     constexpr int PLANE = (BM + BN) * SPLIT_LD;          // floats per bf16 plane
-    constexpr int LDS_FLOATS = NS == 0 ? NBUF * STAGE : NS * PLANE;
+    constexpr int LDS_FLOATS = NS == 0 ? STAGE : NS * PLANE;
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -111,16 +108,7 @@ __global__ __launch_bounds__(256, 3) void gemm_nt_f32_kernel(const GemmParams p)
         const unsigned by_ = (w_) / n_tiles, t = (w_) - by_ * n_tiles;                       \
         b1x = by_ / p.batch2; b2x = by_ % p.batch2;                                          \
         int tm, tn;                                                                          \
-        if (p.tile_order == 1) { tm = t / tiles_n; tn = t % tiles_n; }                       \
-        else if (p.tile_order == 2) { tn = t / tiles_m; tm = t % tiles_m; }                  \
-        else {   /* bands of GM m-tiles; inside a band n is the slow index */                \
-            const int GM = p.tile_order - 2;                                                 \
-            const int band = t / (GM * tiles_n);                                             \
-            const int m_in = min(GM, tiles_m - band * GM);                                   \
-            const int r = t - band * GM * tiles_n;                                           \
-            tn = r / m_in;                                                                   \
-            tm = band * GM + r % m_in;                                                       \
-        }                                                                                    \
+        GNNLM_TILE_WALK(p.tile_order, t, tiles_m, tiles_n, tm, tn)  /* in place: gemm_route.h */ \
         m0x = tm * BM; n0x = tn * BN;                                                        \
         const float* A_ = p.A + b1x * p.sA1 + b2x * p.sA2;                                   \
         const float* W_ = p.W + b1x * p.sW1 + b2x * p.sW2;                                   \
@@ -251,18 +239,7 @@ __global__ __launch_bounds__(256, 3) void gemm_nt_f32_kernel(const GemmParams p)
                 b[j] = *reinterpret_cast<const float4*>(w_base + 32 * j * LDS_LD + 8 * s_);  \
             _Pragma("unroll") for (int i = 0; i < TM; ++i)                                   \
                 _Pragma("unroll") for (int j = 0; j < TN; ++j) {                             \
-                    /* LSE epilogue: operands swapped = transposed accumulator tile (gemm_epilogue.inc) */ \
-                    if constexpr (EPI == EPI_LSE) {                                          \
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j].x, a[i].x, acc[i][j], 0, 0, 0); \
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j].y, a[i].y, acc[i][j], 0, 0, 0); \
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j].z, a[i].z, acc[i][j], 0, 0, 0); \
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j].w, a[i].w, acc[i][j], 0, 0, 0); \
-                    } else {                                                                 \
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, b[j].x, acc[i][j], 0, 0, 0); \
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b[j].y, acc[i][j], 0, 0, 0); \
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, b[j].z, acc[i][j], 0, 0, 0); \
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b[j].w, acc[i][j], 0, 0, 0); \
-                    }                                                                        \
+                    gemm_mfma4<EPI == EPI_LSE>(acc[i][j], a[i], b[j]);                       \
                 }                                                                            \
         }                                                                                    \
     }
@@ -286,12 +263,10 @@ __global__ __launch_bounds__(256, 3) void gemm_nt_f32_kernel(const GemmParams p)
         __syncthreads();
         if (nk_full > 0) {
             for (int kt = 0; kt < nk_full; ++kt) {
-                constexpr bool ONE_BUF = NBUF == 1 || NS != 0;
-                const int buf = ONE_BUF ? 0 : (kt & 1);
                 if (kt + 1 < nk_full) GNNLM_LOAD_TILE(kt + 1);
-                GNNLM_COMPUTE(buf);
-                if (ONE_BUF) __syncthreads();
-                if (kt + 1 < nk_full) { GNNLM_STORE_TILE(ONE_BUF ? 0 : (buf ^ 1)); }
+                GNNLM_COMPUTE(0);
+                __syncthreads();
+                if (kt + 1 < nk_full) { GNNLM_STORE_TILE(0); }
                 __syncthreads();
             }
             if (k_tail) {
@@ -380,51 +355,10 @@ void launch(const GemmParams& p, dim3 grid, hipStream_t stream) {
 }
 }  // namespace
 
-thread_local int g_default_gemm_precision = 0;
-
-int gemm_nt(const GemmParams& desc, hipStream_t stream) {
-    GemmParams p = desc;
-    if (p.precision == 0) p.precision = g_default_gemm_precision;
-    if (p.alpha == 0.f) p.alpha = 1.f;
-    if (p.batch1 == 0) p.batch1 = 1;
-    if (p.batch2 == 0) p.batch2 = 1;
-    GNNLM_REQUIRE(p.A && p.W && (p.C || p.lse_part), "gemm: null operand");
-    GNNLM_REQUIRE(p.M >= 0 && p.N > 0 && p.K > 0, "gemm: bad shape");
-    GNNLM_REQUIRE(p.K % 4 == 0 && p.lda % 4 == 0 && p.ldw % 4 == 0, "gemm: K, lda, ldw must be multiples of 4");
-    GNNLM_REQUIRE(((uintptr_t)p.A % 16 == 0) && ((uintptr_t)p.W % 16 == 0), "gemm: operands must be 16-byte aligned");
-    GNNLM_REQUIRE(p.sA1 % 4 == 0 && p.sA2 % 4 == 0 && p.sW1 % 4 == 0 && p.sW2 % 4 == 0, "gemm: batch strides must be multiples of 4");
-    GNNLM_REQUIRE(p.batch1 >= 1 && p.batch2 >= 1, "gemm: bad batch");
-    GNNLM_REQUIRE(p.precision >= 0 && p.precision <= 3, "gemm: precision must be 0 (f32 MFMA), 1 (bf16x3), 2 (bf16x6) or 3 (fp16)");
-    GNNLM_REQUIRE(!p.lse_part || p.batch1 * p.batch2 == 1, "gemm: the LSE epilogue does not support batches");
-    GNNLM_REQUIRE(!p.lse_part || p.alpha > 0.f, "gemm: the LSE epilogue needs alpha > 0");
-    // the LSE epilogue reduces alpha * A.W^T and nothing else (gemm_epilogue.inc): operands it would drop are refused, not ignored
-    GNNLM_REQUIRE(!p.lse_part || (!p.bias && !p.gate && !p.R && !p.c_rows), "gemm: the LSE epilogue takes no bias, gate, R or c_rows");
-    GNNLM_REQUIRE(p.tile_order >= 0 && p.tile_order <= 66, "gemm: tile_order must be 0 (auto), 1 (n fastest), 2 (m fastest) or 2+GM (bands of GM m-tiles)");
-    if (p.M == 0) return OK;
-    if (p.tile_order == 0)      // share the larger operand's panel between consecutive tiles
-        p.tile_order = (!p.m_dev && (double)p.M > (double)p.N) ? 1 : 2;
-    if (gemm_split_eligible(p)) return gemm_nt_split(p, stream);      // pre-split planes + LDS-DMA (gemm_split.hip)
-    if (gemm_skinny_eligible(p)) return gemm_nt_skinny(p, stream);    // narrow outputs: 32x32 tiles, k split over the waves (chosen from N, K only)
-    const int64_t nb = (int64_t)p.batch1 * p.batch2;
-    // 128x128 tiles unless they would leave CUs without a workgroup (256 CUs)
-    const int64_t tiles128 = cdiv(p.M, 128) * cdiv(p.N, 128) * nb;
-    const bool small = !p.lse_part && tiles128 < 256;
-    if (!small && gemm_sched_eligible(p)) return gemm_nt_sched(p, stream);   // hand-placed main loop (gemm_f32_sched.hip)
-    if (!small && gemm_dma_eligible(p)) return gemm_nt_dma(p, stream);   // LDS-DMA staged main loop (gemm_f32_dma.hip)
-    const int BMN = small ? 64 : 128;
-    const int64_t tiles = cdiv(p.M, BMN) * cdiv(p.N, BMN) * nb;
-    GNNLM_REQUIRE(tiles < (1ll << 31), "gemm: grid too large");
-    // pool of resident workgroups: 256 CUs x the kernel variant's workgroups per CU (a multiple of 8 = XCDs)
-    const int64_t pool = 256 * (small ? 4 : (p.precision == 2 ? 2 : 3));
-    dim3 grid((unsigned)std::min<int64_t>(tiles, pool));
-    const double work = 2.0 * p.M * (double)p.N * p.K * nb;
-    ProfScope prof(K_GEMM, stream, work, 4.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N) * nb,
-                   p.m_dev, (double)p.M, true);
-    if (prof.slot) p.m_out = prof.slot;
-    if (small) launch<64, 64>(p, grid, stream);
+// reg64 / reg128: the register-staged kernel on 64x64 or 128x128 tiles
+void gemm_launch_reg(GemmRoute route, const GemmParams& p, dim3 grid, hipStream_t stream) {
+    if (route == GemmRoute::REG64) launch<64, 64>(p, grid, stream);
     else launch<128, 128>(p, grid, stream);
-    GNNLM_LAUNCH_CHECK();
-    return OK;
 }
 
 int lse_reduce(const float* part, int n_parts, int64_t rows, const int32_t* m_dev, float* lse, hipStream_t stream) {

@@ -1,5 +1,6 @@
 // f32 "NT" GEMM on the f32 matrix cores with LDS-DMA staging (global_load_lds_dwordx4): the variant of
-// gemm_f32.hip's kernel taken for K % BK == 0 problems on 128x128 tiles.  Same contract, same epilogues
+// gemm_f32.hip's kernel for K % BK == 0 problems on 128x128 or 256x256 tiles, and an A-stationary kernel for short-K
+// log-sum-exp problems (gemm_route.h: dma128, dma256, astat128).  Same contract, same epilogues
 // (gemm_epilogue.inc), same numerics (v_mfma_f32_32x32x2_f32 fmaf chains; the k order inside a stage is
 // permuted, which the MFMA sums over).
 //
@@ -7,7 +8,8 @@
 // VGPRs, no ds_write pass, no second barrier per k-tile) and the LDS image is double-buffered with ONE barrier
 // per stage.
 //
-// Measured (tools/gemm_bench.py, TFLOP/s; GNNLM_DMA_EXP ablations built with tools/build_variant.sh):
+// Measured (tools/gemm_bench.py, TFLOP/s; the two ablation rows came from build-time switches that computed wrong results and
+// are gone: no DMA after the prologue, and the DMA re-reading stage 0):
 //   register-staged kernel      head 8192x20002x1024 124.7   4096^3 129.5   163840x1024x1024 127.7
 //   this kernel, BK = 16 (4 WG/CU)                   124.0          126.8                    127.1
 //   this kernel, BK = 32 (2 WG/CU, the default)      124.5          136.3                    123.4   (step: -1.7 %)
@@ -29,6 +31,7 @@
 // that free, and the fragment read applies the same involution.  f(r) = (r >> 2) & 3 for 64-B rows (BK = 16):
 // the 16 lanes of a ds_read_b128 group (16 consecutive rows, one chunk) then cover all 16 slots of a 256-B
 // bank window.
+#include "gemm_route.h"
 #include "kernels.h"
 
 namespace gnnlm {
@@ -40,9 +43,6 @@ typedef __attribute__((address_space(1))) const void glb_void_t;
 namespace {
 enum { EPI_STORE = 0, EPI_LSE = 1 };
 
-#ifndef GNNLM_DMA_EXP
-#define GNNLM_DMA_EXP 0      // ablations (timing only, wrong results): 1 no DMA after the prologue, 2 + no LDS reads, 3 + no barriers
-#endif
 // BT = 128: 128x128 tile, 4 waves (2x2) of 64x64.  BT = 256: 256x256 tile, 8 waves (2x4) of 128x64 -- half the
 // load instructions and 3/4 of the LDS reads per MFMA, one workgroup (2 waves per SIMD) per CU, 128 KiB of LDS.
 template <int EPI, int BK, int BT>
@@ -80,16 +80,7 @@ __global__ __launch_bounds__(BT == 256 ? 512 : 256, BT == 256 ? 1 : (BK == 16 ? 
         const unsigned by = w_ / n_tiles, t = w_ - by * n_tiles;
         const int b1 = by / p.batch2, b2 = by % p.batch2;
         int tm, tn;
-        if (p.tile_order == 1) { tm = t / tiles_n; tn = t % tiles_n; }
-        else if (p.tile_order == 2) { tn = t / tiles_m; tm = t % tiles_m; }
-        else {
-            const int GM = p.tile_order - 2;
-            const int band = t / (GM * tiles_n);
-            const int m_in = min(GM, tiles_m - band * GM);
-            const int r = t - band * GM * tiles_n;
-            tn = r / m_in;
-            tm = band * GM + r % m_in;
-        }
+        gemm_tile_walk(p.tile_order, t, tiles_m, tiles_n, tm, tn);
         const int m0 = tm * BM, n0 = tn * BN;
         // log-sum-exp problems: the tile's pick columns are requested now and staged in LDS behind the k-loop -- loaded in the
         // epilogue they cost the whole workgroup a memory round trip per tile
@@ -130,7 +121,7 @@ __global__ __launch_bounds__(BT == 256 ? 512 : 256, BT == 256 ? 1 : (BK == 16 ? 
         __syncthreads();
         const int arow = wm * WROWS + l32, wrow = BM + wn * WCOLS + l32;
         for (int ks = 0; ks < nk; ++ks) {
-            const float* sb = lds + (((GNNLM_DMA_EXP == 2 || GNNLM_DMA_EXP == 3) ? 0 : ks) & 1) * STAGE;
+            const float* sb = lds + (ks & 1) * STAGE;
 #pragma unroll
             for (int s = 0; s < BK / 8; ++s) {
                 float4 a[TM], b[TN];
@@ -144,25 +135,15 @@ __global__ __launch_bounds__(BT == 256 ? 512 : 256, BT == 256 ? 1 : (BK == 16 ? 
                     const int r = wrow + 32 * j;
                     b[j] = *reinterpret_cast<const float4*>(sb + r * BK + 4 * ((2 * s + half) ^ GNNLM_SWZ(r)));
                 }
-                if (s == 0 && ks + 1 < nk && (GNNLM_DMA_EXP == 0 || GNNLM_DMA_EXP >= 4)) GNNLM_ISSUE((GNNLM_DMA_EXP == 4 ? 0 : GNNLM_DMA_EXP == 5 ? (ks & 7) : ks + 1), (ks + 1) & 1)
+                if (s == 0 && ks + 1 < nk) GNNLM_ISSUE(ks + 1, (ks + 1) & 1)
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
-                        if constexpr (EPI == EPI_LSE) {     // transposed accumulators (gemm_epilogue.inc)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j].x, a[i].x, acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j].y, a[i].y, acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j].z, a[i].z, acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j].w, a[i].w, acc[i][j], 0, 0, 0);
-                        } else {
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, b[j].x, acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b[j].y, acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, b[j].z, acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b[j].w, acc[i][j], 0, 0, 0);
-                        }
+                        gemm_mfma4<EPI == EPI_LSE>(acc[i][j], a[i], b[j]);
                     }
             }
-            if (GNNLM_DMA_EXP != 3) __syncthreads();            // stage ks+1 landed (the barrier carries the DMA's vmcnt(0)); buffer ks&1 is free
+            __syncthreads();            // stage ks+1 landed (the barrier carries the DMA's vmcnt(0)); buffer ks&1 is free
         }
 #undef GNNLM_ISSUE
 
@@ -261,12 +242,7 @@ __global__ __launch_bounds__(256, 3) void gemm_lse_astationary_kernel(const Gemm
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {      // operands swapped: transposed accumulators (gemm_epilogue.inc)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j].x, areg[i][s].x, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j].y, areg[i][s].y, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j].z, areg[i][s].z, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j].w, areg[i][s].w, acc[i][j], 0, 0, 0);
-                }
+                for (int j = 0; j < TN; ++j) gemm_mfma4<true>(acc[i][j], areg[i][s], b[j]);      // transposed accumulators
         }
         __syncthreads();            // every wave has read the tile
         if (nt + nslots < tiles_n) GNNLM_ISSUE_W(nt + nslots)
@@ -279,37 +255,6 @@ __global__ __launch_bounds__(256, 3) void gemm_lse_astationary_kernel(const Gemm
 }
 }  // namespace
 
-#ifndef GNNLM_DMA_BK
-#define GNNLM_DMA_BK 32
-#endif
-#ifndef GNNLM_DMA_BIG_TILES
-#define GNNLM_DMA_BIG_TILES 2048     // 256x256 tiles from this many of them on (8 per CU); 1 << 30 disables
-#endif
-#ifndef GNNLM_DMA_MIN_K
-#define GNNLM_DMA_MIN_K 128
-#endif
-
-bool gemm_dma_eligible(const GemmParams& p) {
-#ifdef GNNLM_NO_DMA_GEMM
-    return false;
-#endif
-    // Where it pays, measured per launch inside the step (rocprofv3 trace, us; register-staged -> this kernel):
-    // LSE head 8192x20002x1024 2689 -> 2571, tail band 1 147 -> 147; store epilogue: projections 146 -> 145,
-    // absorbed queries (K = 128) 191 -> 209, 163840x1024x1024 of the 3-layer path 127.7 -> 123.4 TFLOP/s.  So the
-    // LSE problems take this kernel and the store-epilogue problems stay on the register-staged one
-    // (GNNLM_DMA_STORE=1 at build time sends them here too, for A/B runs).
-#ifndef GNNLM_DMA_STORE
-    // ... except the head-sized ones, which get the 256x256 tiles: 655360x1024x1024 (3-layer path) 123 -> 128 TFLOP/s
-    // ... and, round 2 (tools/gemm_bench.py step8k, us: register-staged -> this kernel, 128x128 tiles): the step's K = 1024
-    // problems 8192x1024x1024 169 -> 157, 8192x3072x1024 (Q, K, V in one) 464 -> 436, Z Wvz (batch 8, N = 128) 150 -> 142;
-    // K = 128 (absorbed queries) stays where it is (200 -> 218)
-    if (!p.lse_part && (p.m_dev || (p.K < 512 && cdiv(p.M, 256) * cdiv(p.N, 256) * p.batch1 * p.batch2 < GNNLM_DMA_BIG_TILES))) return false;
-#endif
-    if (p.precision == 0 && p.K == 64 && p.lse_part && p.batch1 * p.batch2 == 1 && p.M <= 128 * 768) return true;   // A-stationary kernel
-    return p.precision == 0 && p.K % GNNLM_DMA_BK == 0 && p.K >= GNNLM_DMA_MIN_K;
-}
-
-// p is normalised by gemm_nt (the caller checked the problem fills the chip with 128x128 tiles)
 template <int EPI, int BK, int BT>
 int launch_dma(const GemmParams& p, dim3 grid, hipStream_t stream) {
     constexpr size_t lds_bytes = 2 * (size_t)(2 * BT * BK) * sizeof(float);
@@ -318,37 +263,17 @@ int launch_dma(const GemmParams& p, dim3 grid, hipStream_t stream) {
     return OK;
 }
 
-int gemm_nt_dma(const GemmParams& p_in, hipStream_t stream) {
-    GemmParams p = p_in;
-    constexpr int BK = GNNLM_DMA_BK;
-    if (p.K == 64 && p.lse_part) {      // short-K log-sum-exp: A stays in registers, workgroups walk the n-tiles
-        constexpr size_t lds_bytes = (128 * 64 + 128) * sizeof(float);
-        GNNLM_LDS_OPT_IN(&gemm_lse_astationary_kernel<64>, lds_bytes);
-        const double work = 2.0 * p.M * (double)p.N * p.K;
-        ProfScope prof(K_GEMM, stream, work, 4.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N),
-                       p.m_dev, (double)p.M, true);
-        if (prof.slot) p.m_out = prof.slot;
-        hipLaunchKernelGGL((gemm_lse_astationary_kernel<64>), dim3(768), dim3(256), lds_bytes, stream, p);
-        GNNLM_LAUNCH_CHECK();
+// dma128 / dma256: the LDS-DMA kernel on that tile; astat128: A stays in registers, the workgroups walk the n-tiles
+int gemm_launch_dma(GemmRoute route, const GemmParams& p, dim3 grid, hipStream_t stream) {
+    if (route == GemmRoute::ASTAT128) {
+        constexpr size_t lds_bytes = (128 * ASTAT_K + 128) * sizeof(float);
+        GNNLM_LDS_OPT_IN(&gemm_lse_astationary_kernel<ASTAT_K>, lds_bytes);
+        hipLaunchKernelGGL((gemm_lse_astationary_kernel<ASTAT_K>), grid, dim3(256), lds_bytes, stream, p);
         return OK;
     }
-    const int64_t nb = (int64_t)p.batch1 * p.batch2;
-    const bool big = !p.m_dev && cdiv(p.M, 256) * cdiv(p.N, 256) * nb >= GNNLM_DMA_BIG_TILES;
-    const int BT = big ? 256 : 128;
-    const int64_t tiles = cdiv(p.M, BT) * cdiv(p.N, BT) * nb;
-    GNNLM_REQUIRE(tiles < (1ll << 31), "gemm: grid too large");
-    const int64_t pool = 256 * (big ? 1 : (BK == 16 ? 4 : 2));
-    dim3 grid((unsigned)std::min<int64_t>(tiles, pool));
-    const double work = 2.0 * p.M * (double)p.N * p.K * nb;
-    ProfScope prof(K_GEMM, stream, work, 4.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N) * nb,
-                   p.m_dev, (double)p.M, true);
-    if (prof.slot) p.m_out = prof.slot;
-    int rc;
-    if (big) rc = p.lse_part ? launch_dma<EPI_LSE, BK, 256>(p, grid, stream) : launch_dma<EPI_STORE, BK, 256>(p, grid, stream);
-    else rc = p.lse_part ? launch_dma<EPI_LSE, BK, 128>(p, grid, stream) : launch_dma<EPI_STORE, BK, 128>(p, grid, stream);
-    if (rc != OK) return rc;
-    GNNLM_LAUNCH_CHECK();
-    return OK;
+    if (route == GemmRoute::DMA256)
+        return p.lse_part ? launch_dma<EPI_LSE, DMA_BK, 256>(p, grid, stream) : launch_dma<EPI_STORE, DMA_BK, 256>(p, grid, stream);
+    return p.lse_part ? launch_dma<EPI_LSE, DMA_BK, 128>(p, grid, stream) : launch_dma<EPI_STORE, DMA_BK, 128>(p, grid, stream);
 }
 
 }  // namespace gnnlm

@@ -10,6 +10,7 @@
 //
 // LDS image of a stage (32 KiB, two of them): [256 rows (A 128 + W 128)][32 floats], slot s (16 B) of row r holds
 // k-chunk s ^ ((r >> 1) & 7): the 16 lanes of a ds_read_b128 group (16 consecutive rows, one chunk) cover all banks.
+#include "gemm_route.h"
 #include "kernels.h"
 
 namespace gnnlm {
@@ -60,16 +61,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f32_sched_kernel(const GemmPar
         const unsigned by = w_ / n_tiles, t = w_ - by * n_tiles;
         t_.b1 = by / p.batch2; t_.b2 = by % p.batch2;
         int tm, tn;
-        if (p.tile_order == 1) { tm = t / tiles_n; tn = t % tiles_n; }
-        else if (p.tile_order == 2) { tn = t / tiles_m; tm = t % tiles_m; }
-        else {
-            const int GM = p.tile_order - 2;
-            const int band = t / (GM * tiles_n);
-            const int m_in = min(GM, tiles_m - band * GM);
-            const int r = t - band * GM * tiles_n;
-            tn = r / m_in;
-            tm = band * GM + r % m_in;
-        }
+        gemm_tile_walk(p.tile_order, t, tiles_m, tiles_n, tm, tn);
         t_.m0 = tm * BM; t_.n0 = tn * BN;
         t_.A = p.A + t_.b1 * p.sA1 + t_.b2 * p.sA2;
         t_.W = p.W + t_.b1 * p.sW1 + t_.b2 * p.sW2;
@@ -148,13 +140,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f32_sched_kernel(const GemmPar
         int cnt = nk >> 1;
         int koff = nk > 1 ? BK * 4 : 0;
         const int inc = BK * 4;
-#ifdef GNNLM_SCHED_AGPR
-#define GNNLM_ACC_RC "+a"
-#else
-#define GNNLM_ACC_RC "+v"
-#endif
+        // the accumulators are VGPR operands ("+v": in AGPRs the loop measured 3 % slower at best); the loop's MFMA lines take
+        // their two sources through GNNLM_MFMA_AB(a, w)
 #define GNNLM_SCHED_OPERANDS                                                                                                    \
-            : [c00] GNNLM_ACC_RC(acc[0][0]), [c01] GNNLM_ACC_RC(acc[0][1]), [c10] GNNLM_ACC_RC(acc[1][0]), [c11] GNNLM_ACC_RC(acc[1][1]), [cnt] "+s"(cnt), [koff] "+s"(koff) \
+            : [c00] "+v"(acc[0][0]), [c01] "+v"(acc[0][1]), [c10] "+v"(acc[1][0]), [c11] "+v"(acc[1][1]), [cnt] "+s"(cnt), [koff] "+s"(koff) \
             : [sa] "s"(sa), [sw] "s"(sw), [inc] "s"(inc),                                                                             \
               [oa0] "v"(cur.oa[0]), [oa1] "v"(cur.oa[1]), [oa2] "v"(cur.oa[2]), [oa3] "v"(cur.oa[3]),                                                  \
               [ow0] "v"(cur.ow[0]), [ow1] "v"(cur.ow[1]), [ow2] "v"(cur.ow[2]), [ow3] "v"(cur.ow[3]), [lw] "v"(lw),                                    \
@@ -162,17 +151,21 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f32_sched_kernel(const GemmPar
               [rb0] "v"(rb[0]), [rb1] "v"(rb[1]), [rb2] "v"(rb[2]), [rb3] "v"(rb[3])                                                   \
             : "memory", "vcc", "scc",
         if constexpr (EPI == EPI_LSE) {          // operands swapped: transposed accumulators (gemm_epilogue.inc)
-            asm volatile(
-#include "gemm_sched_loop_t.inc"
-                GNNLM_SCHED_OPERANDS
-#include "gemm_sched_clobbers.inc"
-            );
-        } else {
+#define GNNLM_MFMA_AB(a_, w_) w_ ", " a_
             asm volatile(
 #include "gemm_sched_loop.inc"
                 GNNLM_SCHED_OPERANDS
 #include "gemm_sched_clobbers.inc"
             );
+#undef GNNLM_MFMA_AB
+        } else {
+#define GNNLM_MFMA_AB(a_, w_) a_ ", " w_
+            asm volatile(
+#include "gemm_sched_loop.inc"
+                GNNLM_SCHED_OPERANDS
+#include "gemm_sched_clobbers.inc"
+            );
+#undef GNNLM_MFMA_AB
         }
 #undef GNNLM_SCHED_OPERANDS
         __syncthreads();                                               // every wave left the loop: the LDS image is free
@@ -215,28 +208,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f32_sched_kernel(const GemmPar
 }
 }  // namespace
 
-// Where the scheduled kernel is taken: exact f32, K a multiple of 64 (the loop runs stage pairs), 128x128 tiles filling the
-// chip, rows addressed with 32-bit byte offsets inside the panel.  GNNLM_GEMM_SCHED=0 sends everything to the other kernels.
-bool gemm_sched_eligible(const GemmParams& p) {
-    // GNNLM_GEMM_SCHED (A/B runs): 0 = never, 1 = store-epilogue problems only, 3 (default) = log-sum-exp problems too, 7 = the head as well
-    static const int on = [] { const char* e = getenv("GNNLM_GEMM_SCHED"); return e ? atoi(e) : 3; }();
-    if (!on) return false;
-    if (p.precision != 0) return false;
-    if (p.lse_part && !(on & 2)) return false;
-    // the softmax head (>= 2048 tiles of 256x256) runs in the same time here as on the 256x256 LDS-DMA kernel (2.47 ms), but
-    // with 128-wide W panels it pulls the A panel through the fabric twice as often (PMC FETCH_SIZE 2.9 vs 1.4 GB): stays there
-    if (p.lse_part && !p.m_dev && !(on & 4) && cdiv(p.M, 256) * cdiv(p.N, 256) >= 2048) return false;
-    static const int min_k = [] { const char* e = getenv("GNNLM_GEMM_SCHED_MINK"); return e ? atoi(e) : 256; }();
-    if (p.K % 64 != 0 || p.K < min_k) return false;                       // K = 128 (absorbed queries): 191 us on the register-staged kernel, 206 here
-    const int64_t nb = (int64_t)p.batch1 * p.batch2;
-    if (cdiv(p.M, 128) * cdiv(p.N, 128) * nb < 256) return false;
-    // rows are addressed by 32-bit byte offsets from the panel base of the tile's batch
-    if ((int64_t)p.N * p.ldw * 4 >= (1ll << 32)) return false;
-    const int64_t a_rows = p.a_rows ? p.a_rows_bound : (int64_t)p.M;    // gathered rows index [0, a_rows_bound)
-    if (a_rows <= 0 || a_rows * p.lda * 4 >= (1ll << 32)) return false;
-    return true;
-}
-
 template <int EPI>
 static int launch_sched(const GemmParams& p, dim3 grid, hipStream_t stream) {
     constexpr size_t lds_bytes = 2 * 256 * 32 * sizeof(float);
@@ -245,20 +216,9 @@ static int launch_sched(const GemmParams& p, dim3 grid, hipStream_t stream) {
     return OK;
 }
 
-int gemm_nt_sched(const GemmParams& p_in, hipStream_t stream) {
-    GemmParams p = p_in;
-    const int64_t nb = (int64_t)p.batch1 * p.batch2;
-    const int64_t tiles = cdiv(p.M, 128) * cdiv(p.N, 128) * nb;
-    GNNLM_REQUIRE(tiles < (1ll << 31), "gemm: grid too large");
-    dim3 grid((unsigned)std::min<int64_t>(tiles, 512));
-    const double work = 2.0 * p.M * (double)p.N * p.K * nb;
-    ProfScope prof(K_GEMM, stream, work, 4.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N) * nb,
-                   p.m_dev, (double)p.M, true);
-    if (prof.slot) p.m_out = prof.slot;
-    const int rc = p.lse_part ? launch_sched<EPI_LSE>(p, grid, stream) : launch_sched<EPI_STORE>(p, grid, stream);
-    if (rc != OK) return rc;
-    GNNLM_LAUNCH_CHECK();
-    return OK;
+// sched128 (gemm_route.h: exact f32, K a multiple of 64, rows within 32-bit byte offsets of the panel base)
+int gemm_launch_sched(const GemmParams& p, dim3 grid, hipStream_t stream) {
+    return p.lse_part ? launch_sched<EPI_LSE>(p, grid, stream) : launch_sched<EPI_STORE>(p, grid, stream);
 }
 
 }  // namespace gnnlm

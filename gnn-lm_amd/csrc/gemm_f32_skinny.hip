@@ -8,7 +8,7 @@
 // a fixed order and stored by the whole workgroup with the store epilogue of gemm_epilogue.inc restated per element.
 //
 // The split changes the summation order of an output element, so WHICH problems take this kernel may not depend on the row
-// count: the choice is made from N, K and the batch alone (gemm_skinny_eligible), and a row's result is the same bits whether
+// count: the choice is made from N, K and the batch alone (gemm_route.h: skinny32), and a row's result is the same bits whether
 // its launch carries one block or thirty-two, a row subset or all rows.
 #include "kernels.h"
 
@@ -87,24 +87,9 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_skinny_kernel(const GemmParam
 }
 }  // namespace
 
-// Decided from N, K and the batch only -- never from the row count (see the header).  GNNLM_GEMM_SKINNY=0 switches it off.
-bool gemm_skinny_eligible(const GemmParams& p) {
-    static const int on = [] { const char* e = getenv("GNNLM_GEMM_SKINNY"); return e ? atoi(e) : 1; }();
-    if (!on || p.precision != 0 || p.lse_part) return false;
-    if (p.batch1 * p.batch2 != 1 || p.N > 256) return false;
-    return p.K % 32 == 0 && p.K >= 512;
-}
-
-int gemm_nt_skinny(const GemmParams& p_in, hipStream_t stream) {
-    GemmParams p = p_in;
-    const int64_t tiles = cdiv(p.M, 32) * cdiv(p.N, 32);
-    GNNLM_REQUIRE(tiles < (1ll << 31), "gemm: grid too large");
-    const double work = 2.0 * p.M * (double)p.N * p.K;
-    ProfScope prof(K_GEMM, stream, work, 4.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N), p.m_dev, (double)p.M, true);
-    if (prof.slot) p.m_out = prof.slot;
-    hipLaunchKernelGGL(gemm_nt_f32_skinny_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, p);
-    GNNLM_LAUNCH_CHECK();
-    return OK;
+// skinny32: one workgroup per 32x32 tile
+void gemm_launch_skinny(const GemmParams& p, dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL(gemm_nt_f32_skinny_kernel, grid, dim3(256), 0, stream, p);
 }
 
 }  // namespace gnnlm

@@ -30,6 +30,7 @@
 #include <mutex>
 #include <unordered_map>
 
+#include "gemm_route.h"
 #include "kernels.h"
 
 namespace gnnlm {
@@ -135,16 +136,7 @@ void gemm_planes_kernel(const GemmParams p, const uint4* __restrict__ Ap, const 
     const unsigned t_step = p.m_dev ? gridDim.x : n_tiles;
     for (unsigned t = p.m_dev ? blockIdx.x : xcd_remap(blockIdx.x, n_tiles); t < n_tiles; t += t_step) {
     int tm, tn;
-    if (p.tile_order == 1) { tm = t / tiles_n; tn = t % tiles_n; }
-    else if (p.tile_order == 2) { tn = t / tiles_m; tm = t % tiles_m; }
-    else {
-        const int GM = p.tile_order - 2;
-        const int band = t / (GM * tiles_n);
-        const int m_in = min(GM, tiles_m - band * GM);
-        const int r = t - band * GM * tiles_n;
-        tn = r / m_in;
-        tm = band * GM + r % m_in;
-    }
+    gemm_tile_walk(p.tile_order, t, tiles_m, tiles_n, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
 
     // this wave's share of every stage: the PH slabs of one 64-row block of one operand (PH KiB, contiguous)
@@ -154,11 +146,8 @@ void gemm_planes_kernel(const GemmParams p, const uint4* __restrict__ Ap, const 
     const int s_dst = s_op * OPU + s_rb * 64;
 
     // two of this wave's PH slabs of 16-k step ks_ -> LDS buffer buf_, step slot st_ (slabs q_, q_+1)
-#ifndef GNNLM_EXP
-#define GNNLM_EXP 0
-#endif
 #define GNNLM_ISSUE2(ks_, buf_, st_, q_)                                                     \
-    if ((ks_) < KS && !(GNNLM_EXP == 2 && (ks_) > 1)) {                                                                        \
+    if ((ks_) < KS) {                                                                        \
         const uint4* g_ = gsrc + (int64_t)(ks_) * (PH * 64) + (q_) * 64;                     \
         __builtin_amdgcn_global_load_lds((glb_void_t*)(g_), (lds_void_t*)(&lds[buf_][(st_) * 2 * OPU + s_dst + (q_) * T]), 16, 0, 0);            \
         __builtin_amdgcn_global_load_lds((glb_void_t*)(g_ + 64), (lds_void_t*)(&lds[buf_][(st_) * 2 * OPU + s_dst + ((q_) + 1) * T]), 16, 0, 0); \
@@ -296,21 +285,11 @@ void launch_planes(const GemmParams& p, const uint4* Ap, const uint4* Wp, int KS
 }
 }  // namespace
 
-bool gemm_split_eligible(const GemmParams& p) {
-    return p.precision != 0 && p.batch1 * p.batch2 == 1 && p.K >= 256 &&
-           cdiv(p.M, 128) * cdiv(p.N, 128) >= 256;
-}
-
-// p is normalised by gemm_nt (alpha, batch, tile_order resolved)
-int gemm_nt_split(const GemmParams& p_in, hipStream_t stream) {
-    GemmParams p = p_in;
+// Pass 1 of split128 / split256 (p normalised by gemm_nt): the plane images of A and W, zero-padded to whole tiles and stages, in
+// the stream's scratch
+int gemm_split_planes(GemmRoute route, const GemmParams& p, hipStream_t stream, GemmPlanes* out) {
     const int NS = p.precision == 3 ? 1 : p.precision == 1 ? 2 : 3;      // planes: fp16 one (the rounded value), bf16x3 two, bf16x6 three
-    // 256x256 tiles when they still give every CU >= 2 workgroups over the launch.  A device-side M is a small fraction of its bound
-    // where the bound is a token count (the softmax tails: 128-tiles), and of the order of the bound where it counts the slot rows
-    // of a batch's context groups (ABI 9: the ntgt projections of a multi-layer step, M >= 2^17 -- merged groups are a good
-    // third of all groups or more): those keep the big tiles (round 5: 22.2 k -> 25 k tokens/s on the 3-layer recipe under bf16x3)
-    const bool big = (!p.m_dev || p.M >= (1 << 17)) && cdiv(p.M, 256) * cdiv(p.N, 256) >= 512;
-    const int T = big ? 256 : 128;
+    const int T = gemm_geometry(route).tile;
     const int KPAD = NS == 1 ? 4 : 2;                    // 16-k steps per stage of the widest kernel variant of this precision
     const int KS = (int)cdiv(p.K, SK * KPAD) * KPAD;     // 16-k steps, zero-padded to a whole number of stages
     const int64_t rbA = cdiv(p.M, T) * (T / 64), rbW = cdiv(p.N, T) * (T / 64);
@@ -320,30 +299,36 @@ int gemm_nt_split(const GemmParams& p_in, hipStream_t stream) {
     if (rc != OK) return rc;
     uint4* Ap = reinterpret_cast<uint4*>(ws);
     uint4* Wp = Ap + (size_t)rbA * per_rb / unit_bytes;
-    {
-        ProfScope prof(K_SPLIT, stream, 0.0, (4.0 + 2.0 * NS) * ((double)p.M + (double)p.N) * p.K);
-        if (NS == 1) {
-            launch_split<1>(p.A, p.lda, p.a_rows, p.M, p.m_dev, p.K, KS, (int)rbA, Ap, stream);
-            launch_split<1>(p.W, p.ldw, nullptr, p.N, nullptr, p.K, KS, (int)rbW, Wp, stream);
-        } else if (NS == 2) {
-            launch_split<2>(p.A, p.lda, p.a_rows, p.M, p.m_dev, p.K, KS, (int)rbA, Ap, stream);
-            launch_split<2>(p.W, p.ldw, nullptr, p.N, nullptr, p.K, KS, (int)rbW, Wp, stream);
-        } else {
-            launch_split<3>(p.A, p.lda, p.a_rows, p.M, p.m_dev, p.K, KS, (int)rbA, Ap, stream);
-            launch_split<3>(p.W, p.ldw, nullptr, p.N, nullptr, p.K, KS, (int)rbW, Wp, stream);
-        }
-        GNNLM_LAUNCH_CHECK();
+    ProfScope prof(K_SPLIT, stream, 0.0, (4.0 + 2.0 * NS) * ((double)p.M + (double)p.N) * p.K);
+    if (NS == 1) {
+        launch_split<1>(p.A, p.lda, p.a_rows, p.M, p.m_dev, p.K, KS, (int)rbA, Ap, stream);
+        launch_split<1>(p.W, p.ldw, nullptr, p.N, nullptr, p.K, KS, (int)rbW, Wp, stream);
+    } else if (NS == 2) {
+        launch_split<2>(p.A, p.lda, p.a_rows, p.M, p.m_dev, p.K, KS, (int)rbA, Ap, stream);
+        launch_split<2>(p.W, p.ldw, nullptr, p.N, nullptr, p.K, KS, (int)rbW, Wp, stream);
+    } else {
+        launch_split<3>(p.A, p.lda, p.a_rows, p.M, p.m_dev, p.K, KS, (int)rbA, Ap, stream);
+        launch_split<3>(p.W, p.ldw, nullptr, p.N, nullptr, p.K, KS, (int)rbW, Wp, stream);
     }
-    const int64_t tiles = cdiv(p.M, T) * cdiv(p.N, T);
-    GNNLM_REQUIRE(tiles < (1ll << 31), "gemm: grid too large");
-    dim3 grid((unsigned)(p.m_dev ? std::min<int64_t>(tiles, 512) : tiles));
-    const double work = 2.0 * p.M * (double)p.N * p.K;
-    ProfScope prof(K_GEMM, stream, work, 4.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N), p.m_dev, (double)p.M, true);
-    if (prof.slot) p.m_out = prof.slot;
-    if (big) { if (NS == 1) launch_planes<256, 1>(p, Ap, Wp, KS, grid, stream); else if (NS == 2) launch_planes<256, 2>(p, Ap, Wp, KS, grid, stream); else launch_planes<256, 3>(p, Ap, Wp, KS, grid, stream); }
-    else     { if (NS == 1) launch_planes<128, 1>(p, Ap, Wp, KS, grid, stream); else if (NS == 2) launch_planes<128, 2>(p, Ap, Wp, KS, grid, stream); else launch_planes<128, 3>(p, Ap, Wp, KS, grid, stream); }
     GNNLM_LAUNCH_CHECK();
+    out->A = Ap; out->W = Wp; out->KS = KS;
     return OK;
+}
+
+// Pass 2: the GEMM over the images on the route's tile
+void gemm_launch_split(GemmRoute route, const GemmParams& p, const GemmPlanes& planes, dim3 grid, hipStream_t stream) {
+    const uint4* Ap = static_cast<const uint4*>(planes.A);
+    const uint4* Wp = static_cast<const uint4*>(planes.W);
+    const int KS = planes.KS;
+    if (route == GemmRoute::SPLIT256) {
+        if (p.precision == 3) launch_planes<256, 1>(p, Ap, Wp, KS, grid, stream);
+        else if (p.precision == 1) launch_planes<256, 2>(p, Ap, Wp, KS, grid, stream);
+        else launch_planes<256, 3>(p, Ap, Wp, KS, grid, stream);
+    } else {
+        if (p.precision == 3) launch_planes<128, 1>(p, Ap, Wp, KS, grid, stream);
+        else if (p.precision == 1) launch_planes<128, 2>(p, Ap, Wp, KS, grid, stream);
+        else launch_planes<128, 3>(p, Ap, Wp, KS, grid, stream);
+    }
 }
 
 }  // namespace gnnlm

@@ -31,17 +31,18 @@ int ivfpq_tau(const gnnlm_ivfpq_tau_t& d, hipStream_t stream);
 int ivfpq_select_probes(const gnnlm_ivfpq_select_probes_t& d, hipStream_t stream);
 int ivfpq_select_final(const gnnlm_ivfpq_select_final_t& d, hipStream_t stream);
 
+// gemm.hip: refusals, the route (gemm_route.h), one launch
 int gemm_nt(const GemmParams& p, hipStream_t stream);
-// big-tile split-bf16 path (gemm_split.hip): taken by gemm_nt for precision != 0 when the problem fills the chip
-bool gemm_split_eligible(const GemmParams& p);
-int gemm_nt_split(const GemmParams& p, hipStream_t stream);
-// f32 MFMA kernel with LDS-DMA staging (gemm_f32_dma.hip): taken by gemm_nt for 128x128-tile problems with K % 16 == 0
-bool gemm_dma_eligible(const GemmParams& p);
-int gemm_nt_dma(const GemmParams& p, hipStream_t stream);
-bool gemm_sched_eligible(const GemmParams& p);
-int gemm_nt_sched(const GemmParams& p, hipStream_t stream);
-bool gemm_skinny_eligible(const GemmParams& p);
-int gemm_nt_skinny(const GemmParams& p, hipStream_t stream);
+// the launchers of the kernel files, called by gemm_nt with a normalised descriptor, the route gemm_route() chose and its grid
+enum class GemmRoute : int;
+void gemm_launch_reg(GemmRoute route, const GemmParams& p, dim3 grid, hipStream_t stream);       // gemm_f32.hip: reg64, reg128
+int gemm_launch_sched(const GemmParams& p, dim3 grid, hipStream_t stream);                       // gemm_f32_sched.hip: sched128
+int gemm_launch_dma(GemmRoute route, const GemmParams& p, dim3 grid, hipStream_t stream);        // gemm_f32_dma.hip: dma128, dma256, astat128
+void gemm_launch_skinny(const GemmParams& p, dim3 grid, hipStream_t stream);                     // gemm_f32_skinny.hip: skinny32
+// gemm_split.hip (split128, split256): the plane images of both operands in the stream's scratch, then the GEMM over them
+struct GemmPlanes { const void* A = nullptr; const void* W = nullptr; int KS = 0; };
+int gemm_split_planes(GemmRoute route, const GemmParams& p, hipStream_t stream, GemmPlanes* out);
+void gemm_launch_split(GemmRoute route, const GemmParams& p, const GemmPlanes& planes, dim3 grid, hipStream_t stream);
 // precision used by gemm_nt for descriptors that leave `precision` at 0 (set by the orchestrators)
 extern thread_local int g_default_gemm_precision;
 struct GemmPrecisionScope {

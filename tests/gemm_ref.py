@@ -1,5 +1,5 @@
-"""numpy restatement of gnnlm_gemm_nt and gnnlm_lse_reduce (include/gnnlm.h: gnnlm_gemm_t), of the dispatcher of csrc/gemm_f32.hip
-and of the tile walk its kernels share; and the case table of tests/test_gemm_abi_gpu.py.  No torch, no device code.
+"""numpy restatement of gnnlm_gemm_nt and gnnlm_lse_reduce (include/gnnlm.h: gnnlm_gemm_t), of the dispatcher and the tile walk of
+csrc/gemm_route.h; and the case table of tests/test_gemm_abi_gpu.py.  No torch, no device code.
 
 A descriptor is a dict (``DESC_DEFAULTS``): every buffer is the flat float32 / int32 array that starts AT the descriptor's pointer,
 so the strides, leading dimensions and batch offsets of the header are plain index arithmetic here.
@@ -7,8 +7,8 @@ so the strides, leading dimensions and batch offsets of the header are plain ind
   gemm_ref(d)        what the header promises, in float64: the whole C image (the bytes the call must leave untouched included),
                      or lse_part / lse_picked with the rows and entries that stay untouched
   lse_reduce_ref     log sum exp of the (max, sum) pairs
-  route(d)           the kernel gemm_nt() launches, the dispatcher followed line by line (GNNLM_GEMM_SCHED, GNNLM_GEMM_SCHED_MINK and
-                     GNNLM_GEMM_SKINNY unset)
+  route(d)           the kernel gemm_nt() launches: gemm_route() restated, and compared with it by test_gemm_ref_cpu.py
+                     (GNNLM_GEMM_SCHED, GNNLM_GEMM_SCHED_MINK and GNNLM_GEMM_SKINNY unset)
   tile_walk          list position -> (tm, tn) of the four kernels that walk a tile list
   CASES / make_case  the table: per route exact data (small integers: every partial sum is exact in float32 in any order, the result
                      is the reference bit for bit at every precision) and random data (held to the accuracy bars)
@@ -24,30 +24,26 @@ import zlib
 
 import numpy as np
 
-# ------------------------------------------------------------------------------------------ dispatch constants (pinned to the sources
-# by test_gemm_ref_cpu.py)
-DMA_BK = 32                  # gemm_f32_dma.hip: GNNLM_DMA_BK
-DMA_BIG_TILES = 2048         # GNNLM_DMA_BIG_TILES: 256x256 tiles from this many of them on
-DMA_MIN_K = 128              # GNNLM_DMA_MIN_K
+# ------------------------------------------------------------------------------------------ dispatch constants (csrc/gemm_route.h has
+# the same names; test_gemm_ref_cpu.py compares the values)
+DMA_BK = 32                  # the LDS-DMA kernel
+DMA_BIG_TILES = 2048         # 256x256 tiles from this many of them on
+DMA_MIN_K = 128
 DMA_STORE_MIN_K = 512        # store problems below it only with the big tiles
 ASTAT_K = 64                 # the A-stationary log-sum-exp kernel
 ASTAT_MAX_M = 128 * 768
-SCHED_MIN_K = 256            # gemm_f32_sched.hip
+SCHED_MIN_K = 256            # the hand-placed loop
 SCHED_K_MULT = 64
 SCHED_HEAD_TILES = 2048      # log-sum-exp problems of this many 256x256 tiles stay on the LDS-DMA kernel
-SKINNY_MAX_N = 256           # gemm_f32_skinny.hip
+SKINNY_MAX_N = 256           # narrow outputs
 SKINNY_K_MULT = 32
 SKINNY_MIN_K = 512
-SPLIT_MIN_K = 256            # gemm_split.hip
+SPLIT_MIN_K = 256            # pre-split planes
 SPLIT_MIN_TILES = 256        # 128x128 tiles
 SPLIT_BIG_TILES = 512        # 256x256 tiles
 SPLIT_MDEV_BIG_M = 1 << 17
-SMALL_TILES = 256            # gemm_f32.hip: fewer 128x128 tiles than this -> 64x64 tiles (store only)
+SMALL_TILES = 256            # fewer 128x128 tiles than this -> 64x64 tiles (store only)
 MAX_TILE_ORDER = 66
-
-# the band walk as the four kernels spell it (whitespace and line continuations removed)
-TILE_WALK_SOURCE = ("constintGM=p.tile_order-2;", "constintband=t/(GM*tiles_n);", "constintm_in=min(GM,tiles_m-band*GM);",
-                    "constintr=t-band*GM*tiles_n;", "tn=r/m_in;", "tm=band*GM+r%m_in;")
 
 SENT_BITS = 0x7FC0BEEF       # a NaN with a payload of its own: "untouched" is compared as bits
 
@@ -309,23 +305,23 @@ def route(d):
     if M == 0:
         return "none"
     tiles128, tiles256 = cdiv(M, 128) * cdiv(N, 128), cdiv(M, 256) * cdiv(N, 256)
-    # gemm_split_eligible, then the tile choice of gemm_nt_split
+    # pre-split planes and their tile
     if prec != 0 and nb == 1 and K >= SPLIT_MIN_K and tiles128 >= SPLIT_MIN_TILES:
         big = (not m_dev or M >= SPLIT_MDEV_BIG_M) and tiles256 >= SPLIT_BIG_TILES
         return "split256" if big else "split128"
-    # gemm_skinny_eligible
+    # narrow outputs
     if prec == 0 and not lse and nb == 1 and N <= SKINNY_MAX_N and K % SKINNY_K_MULT == 0 and K >= SKINNY_MIN_K:
         return "skinny32"
     small = not lse and tiles128 * nb < SMALL_TILES
     if not small:
-        # gemm_sched_eligible
+        # the hand-placed loop
         a_rows = p["a_rows_bound"] if p["a_rows"] is not None else M
         sched = (prec == 0 and not (lse and not m_dev and tiles256 >= SCHED_HEAD_TILES)
                  and K % SCHED_K_MULT == 0 and K >= SCHED_MIN_K and tiles128 * nb >= SMALL_TILES
                  and N * p["ldw"] * 4 < 2 ** 32 and a_rows > 0 and a_rows * p["lda"] * 4 < 2 ** 32)
         if sched:
             return "sched128"
-        # gemm_dma_eligible, then gemm_nt_dma
+        # LDS-DMA staging, the A-stationary kernel, the tile
         dma = True
         if not lse and (m_dev or (K < DMA_STORE_MIN_K and tiles256 * nb < DMA_BIG_TILES)):
             dma = False

@@ -4,9 +4,11 @@ dispatcher and can tell a kernel that ignores a descriptor field from one that h
 1. gemm_ref equals what the project already trusts: a plain float64 A @ W.T through every stride of the store flavour, and the head
    and tail log-probabilities of oracle.adaptive_softmax through the log-sum-exp flavour (parts -> lse_reduce_ref, picked logit).
    The plane splits of precisions 1 and 2 stay within the bars the kernels are held to; the three truncated planes add up exactly.
-2. route() uses the dispatch constants of the five sources, parsed from them, and the dispatcher's order of questions; the 32-bit
-   offset guards of the scheduled kernel are pinned here (no GPU case allocates 4 GiB).
-3. tile_walk is a permutation of the tiles for every order; the four kernels spell the band walk the same way, the way tile_walk does.
+2. route() is the dispatcher: it is compared with gemm_route() of csrc/gemm_route.h itself (tests/gemm_route_main.cpp, built with the host
+   compiler) over the edge shapes, the case table and a pair of shapes either side of every constant, under the three runtime switches
+   too; the header's constants are gemm_ref's by value.  The 32-bit offset guards of the scheduled kernel are pinned here (no GPU case
+   allocates 4 GiB).
+3. tile_walk is a permutation of the tiles for every order; the one walk of the sources (gemm_route.h) is tile_walk.
 4. For every case and every field it sets, the reference with that one field neutralised or shifted differs in the expected bytes.
 5. Every case reaches the route it names; the table reaches every route route() can name, in both flavours where the route has both
    and at every precision the route serves; every route that walks tiles has a tile_order case in both flavours.
@@ -14,6 +16,8 @@ dispatcher and can tell a kernel that ignores a descriptor field from one that h
 import collections
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -190,70 +194,164 @@ def test_operand_planes(precision, bar):
     assert 0 < err < bar / 2, err
 
 
-# ------------------------------------------------------------------------------------------ 2. the dispatcher's constants
-def const(text, pattern):
-    m = re.search(pattern, text)
-    assert m, pattern
-    return eval(m.group(1), {"__builtins__": {}})
+# ------------------------------------------------------------------------------------------ 2. the dispatcher itself
+CONSTANTS = ("DMA_BK", "DMA_BIG_TILES", "DMA_MIN_K", "DMA_STORE_MIN_K", "ASTAT_K", "ASTAT_MAX_M", "SCHED_MIN_K", "SCHED_K_MULT",
+             "SCHED_HEAD_TILES", "SKINNY_MAX_N", "SKINNY_K_MULT", "SKINNY_MIN_K", "SPLIT_MIN_K", "SPLIT_MIN_TILES", "SPLIT_BIG_TILES",
+             "SPLIT_MDEV_BIG_M", "SMALL_TILES")
 
 
-def test_route_constants_are_the_sources():
-    dma, sched, skinny, split, main = (src(f) for f in ("gemm_f32_dma.hip", "gemm_f32_sched.hip", "gemm_f32_skinny.hip", "gemm_split.hip",
-                                                        "gemm_f32.hip"))
-    assert const(dma, r"#define GNNLM_DMA_BK (\d+)") == ref.DMA_BK
-    assert const(dma, r"#define GNNLM_DMA_BIG_TILES (\d+)") == ref.DMA_BIG_TILES
-    assert const(dma, r"#define GNNLM_DMA_MIN_K (\d+)") == ref.DMA_MIN_K
-    elig = dma[dma.index("bool gemm_dma_eligible"):dma.index("template <int EPI, int BK, int BT>\nint launch_dma")]
-    assert const(elig, r"if \(!p\.lse_part && \(p\.m_dev \|\| \(p\.K < (\d+) && cdiv\(p\.M, 256\) \* cdiv\(p\.N, 256\) \* p\.batch1 \* p\.batch2 < "
-                       r"GNNLM_DMA_BIG_TILES\)\)\) return false;") == ref.DMA_STORE_MIN_K
-    assert const(elig, r"if \(p\.precision == 0 && p\.K == (\d+) && p\.lse_part && p\.batch1 \* p\.batch2 == 1 && p\.M <= 128 \* 768\) return true;") == ref.ASTAT_K
-    assert const(elig, r"p\.M <= (128 \* 768)\)") == ref.ASTAT_MAX_M
-    assert "return p.precision == 0 && p.K % GNNLM_DMA_BK == 0 && p.K >= GNNLM_DMA_MIN_K;" in elig
-    run = dma[dma.index("int gemm_nt_dma("):]
-    assert const(run, r"if \(p\.K == (\d+) && p\.lse_part\) \{") == ref.ASTAT_K
-    assert "const bool big = !p.m_dev && cdiv(p.M, 256) * cdiv(p.N, 256) * nb >= GNNLM_DMA_BIG_TILES;" in run
-    assert "gemm_lse_astationary_kernel<64>" in run and "static_assert(K == 64" in dma
+@pytest.fixture(scope="module")
+def route_program(tmp_path_factory):
+    """tests/gemm_route_main.cpp: csrc/gemm_route.h behind a command line, built with the host compiler alone"""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not found")
+    exe = str(tmp_path_factory.mktemp("gemm_route") / "gemm_route_main")
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", os.path.join(os.path.dirname(os.path.abspath(__file__)), "gemm_route_main.cpp"),
+                        "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return exe
 
-    elig = sched[sched.index("bool gemm_sched_eligible"):sched.index("template <int EPI>\nstatic int launch_sched")]
-    assert const(elig, r'getenv\("GNNLM_GEMM_SCHED"\); return e \? atoi\(e\) : (\d+);') == 3          # store and log-sum-exp, not the head
-    assert const(elig, r'getenv\("GNNLM_GEMM_SCHED_MINK"\); return e \? atoi\(e\) : (\d+);') == ref.SCHED_MIN_K
-    assert const(elig, r"if \(p\.K % (\d+) != 0 \|\| p\.K < min_k\) return false;") == ref.SCHED_K_MULT
-    assert "if (p.precision != 0) return false;" in elig
-    assert const(elig, r"if \(p\.lse_part && !p\.m_dev && !\(on & 4\) && cdiv\(p\.M, 256\) \* cdiv\(p\.N, 256\) >= (\d+)\) return false;") == ref.SCHED_HEAD_TILES
-    assert const(elig, r"if \(cdiv\(p\.M, 128\) \* cdiv\(p\.N, 128\) \* nb < (\d+)\) return false;") == ref.SMALL_TILES
-    assert "if ((int64_t)p.N * p.ldw * 4 >= (1ll << 32)) return false;" in elig
-    assert "const int64_t a_rows = p.a_rows ? p.a_rows_bound : (int64_t)p.M;" in elig
-    assert "if (a_rows <= 0 || a_rows * p.lda * 4 >= (1ll << 32)) return false;" in elig
 
-    elig = skinny[skinny.index("bool gemm_skinny_eligible"):skinny.index("int gemm_nt_skinny(")]
-    assert "if (!on || p.precision != 0 || p.lse_part) return false;" in elig
-    assert const(elig, r"if \(p\.batch1 \* p\.batch2 != 1 \|\| p\.N > (\d+)\) return false;") == ref.SKINNY_MAX_N
-    m = re.search(r"return p\.K % (\d+) == 0 && p\.K >= (\d+);", elig)
-    assert (int(m.group(1)), int(m.group(2))) == (ref.SKINNY_K_MULT, ref.SKINNY_MIN_K)
+def ask(exe, *args, stdin="", env=None):
+    e = {k: v for k, v in os.environ.items() if not k.startswith("GNNLM_GEMM_")}
+    e.update(env or {})
+    r = subprocess.run([exe, *args], input=stdin, capture_output=True, text=True, env=e)
+    assert r.returncode == 0, r.stderr
+    return r.stdout.split("\n")[:-1]
 
-    m = re.search(r"bool gemm_split_eligible\(const GemmParams& p\) \{\s*return p\.precision != 0 && p\.batch1 \* p\.batch2 == 1 && p\.K >= (\d+) &&\s*"
-                  r"cdiv\(p\.M, 128\) \* cdiv\(p\.N, 128\) >= (\d+);", split)
-    assert (int(m.group(1)), int(m.group(2))) == (ref.SPLIT_MIN_K, ref.SPLIT_MIN_TILES)
-    m = re.search(r"const bool big = \(!p\.m_dev \|\| p\.M >= \((1 << \d+)\)\) && cdiv\(p\.M, 256\) \* cdiv\(p\.N, 256\) >= (\d+);", split)
-    assert (eval(m.group(1)), int(m.group(2))) == (ref.SPLIT_MDEV_BIG_M, ref.SPLIT_BIG_TILES)
 
-    body = main[main.index("int gemm_nt(const GemmParams& desc"):main.index("int lse_reduce(")]
-    assert const(body, r"const bool small = !p\.lse_part && tiles128 < (\d+);") == ref.SMALL_TILES
-    assert const(body, r"p\.tile_order >= 0 && p\.tile_order <= (\d+),") == ref.MAX_TILE_ORDER
-    assert "p.tile_order = (!p.m_dev && (double)p.M > (double)p.N) ? 1 : 2;" in body
-    order = [body.index(s) for s in ("if (p.M == 0) return OK;", "if (gemm_split_eligible(p)) return gemm_nt_split(p, stream);",
-                                     "if (gemm_skinny_eligible(p)) return gemm_nt_skinny(p, stream);", "const bool small =",
-                                     "if (!small && gemm_sched_eligible(p)) return gemm_nt_sched(p, stream);",
-                                     "if (!small && gemm_dma_eligible(p)) return gemm_nt_dma(p, stream);", "const int BMN = small ? 64 : 128;")]
-    assert order == sorted(order)
-    assert "if constexpr (BN == 128) {" in main                        # the LSE flavour exists for 128-wide tiles only: LSE is never `small`
+def real_routes(exe, descs, env=None):
+    """[(route name, resolved tile_order)] of gemm_route() / gemm_tile_order() for normalised descriptors"""
+    lines = []
+    for d in descs:
+        p = ref.norm(d)
+        lines.append(" ".join(str(int(x)) for x in (
+            p["M"], p["N"], p["K"], p["precision"], bool(p["lse"]), p["m_dev"] is not None, p["batch1"], p["batch2"], p["lda"], p["ldw"],
+            p["a_rows"] is not None, p["a_rows_bound"], p["tile_order"])))
+    out = [l.split() for l in ask(exe, "route", stdin="\n".join(lines) + "\n", env=env)]
+    assert len(out) == len(descs)
+    return [(r, int(o)) for r, o in out]
+
+
+def _shape(M, N, K, **kw):
+    d = dict(ref.DESC_DEFAULTS)
+    d.update(A=True, W=True, C=True, M=M, N=N, K=K, lda=K, ldw=K)
+    d.update(kw)
+    return d
+
+
+_BIG = dict(M=2050, N=1990)
+_G = dict(a_rows=True, K=256, **_BIG)
+# (descriptor, the route it must take): one step to either side of every constant, written by hand
+EDGES = [
+    (_shape(K=256, **_BIG), "sched128"), (_shape(K=192, **_BIG), "reg128"), (_shape(K=288, **_BIG), "reg128"),
+    (_shape(K=320, **_BIG), "sched128"), (_shape(K=256, precision=3, **_BIG), "split128"),
+    (_shape(K=252, precision=3, **_BIG), "reg128"),
+    (_shape(2048, 2048, 256), "sched128"), (_shape(2048, 1920, 256), "reg64"),             # 256 / 240 tiles of 128
+    (_shape(2048, 1920, 256, lse=True), "dma128"),                                              # LSE is never small
+    (_shape(2048, 1920, 256, precision=1), "reg64"),
+    (_shape(K=544, **_BIG), "dma128"), (_shape(K=544, m_dev=5, **_BIG), "reg128"),
+    (_shape(K=480, **_BIG), "reg128"), (_shape(K=512 + 32, batch1=2, **_BIG), "dma128"),
+    (_shape(257, 261, 128, batch1=16, batch2=32), "dma256"), (_shape(257, 261, 128, batch1=16, batch2=31), "reg128"),
+    (_shape(257, 261, 96, batch1=16, batch2=32), "reg128"),
+    (_shape(2049, 58200, 128, lse=True), "dma256"), (_shape(2048, 58200, 128, lse=True), "dma128"),
+    (_shape(2049, 58200, 256, lse=True), "dma256"), (_shape(2049, 58200, 256, lse=True, m_dev=9), "sched128"),
+    (_shape(129, 300, 64, lse=True), "astat128"), (_shape(129, 300, 64, lse=True, precision=3), "reg128"),
+    (_shape(128 * 768, 300, 64, lse=True), "astat128"), (_shape(128 * 768 + 1, 300, 64, lse=True), "reg128"),
+    (_shape(129, 300, 96, lse=True), "reg128"), (_shape(129, 300, 128, lse=True), "dma128"),
+    (_shape(129, 300, 64), "reg64"),
+    (_shape(70, 256, 512), "skinny32"), (_shape(70, 257, 512), "reg64"), (_shape(70, 256, 480), "reg64"),
+    (_shape(70, 256, 528), "reg64"), (_shape(70, 256, 512, batch2=2), "reg64"),
+    (_shape(70, 256, 512, precision=2), "reg64"), (_shape(70, 256, 512, lse=True), "dma128"),
+    (_shape(100000, 256, 512), "skinny32"),                                                     # never from the row count
+    (_shape(5900, 5900, 256, precision=1), "split256"), (_shape(5900, 5632, 256, precision=1), "split256"),    # 24 x 22 = 528, 24 x 21 = 504
+    (_shape(5900, 5376, 256, precision=1), "split128"),
+    (_shape(5900, 5900, 256, precision=1, m_dev=1), "split128"),
+    (_shape(1 << 17, 300, 256, precision=2, m_dev=1), "split256"), (_shape((1 << 17) - 1, 300, 256, precision=2, m_dev=1), "split128"),
+    (_shape(0, 5, 8), "none"),
+    # the 32-bit byte offsets of the scheduled kernel: N * ldw * 4 and a_rows_bound * lda * 4 below 2^32
+    (_shape(300, 1 << 20, 256, ldw=1020), "sched128"), (_shape(300, 1 << 20, 256, ldw=1024), "dma256"),
+    (_shape(1 << 20, 300, 256, lda=1020), "sched128"), (_shape(1 << 20, 300, 256, lda=1024), "dma256"),
+    (_shape(a_rows_bound=0, **_G), "reg128"), (_shape(a_rows_bound=5, **_G), "sched128"),
+    (_shape(a_rows_bound=1 << 22, **_G), "reg128"), (_shape(a_rows_bound=(1 << 22) - 1, **_G), "sched128"),
+    (_shape(a_rows_bound=0, lse=True, **_G), "dma128"),
+]
+HEAD = _shape(2049, 58200, 256, lse=True)                              # the head shape of EDGES: >= 2048 tiles of 256, no m_dev
+assert any(d == HEAD for d, _ in EDGES)
+
+# per constant, two shapes one step either side of it (and the routes that tells them apart)
+PAIRS = {
+    "DMA_BK": ((_shape(K=544, **_BIG), "dma128"), (_shape(K=548, **_BIG), "reg128")),
+    "DMA_BIG_TILES": ((_shape(257, 261, 128, batch1=16, batch2=32), "dma256"), (_shape(257, 261, 128, batch1=16, batch2=31), "reg128")),
+    "DMA_MIN_K": ((_shape(129, 300, 128, lse=True), "dma128"), (_shape(129, 300, 96, lse=True), "reg128")),
+    "DMA_STORE_MIN_K": ((_shape(K=544, **_BIG), "dma128"), (_shape(K=480, **_BIG), "reg128")),
+    "ASTAT_K": ((_shape(129, 300, 64, lse=True), "astat128"), (_shape(129, 300, 68, lse=True), "reg128")),
+    "ASTAT_MAX_M": ((_shape(128 * 768, 300, 64, lse=True), "astat128"), (_shape(128 * 768 + 1, 300, 64, lse=True), "reg128")),
+    "SCHED_MIN_K": ((_shape(K=256, **_BIG), "sched128"), (_shape(K=192, **_BIG), "reg128")),
+    "SCHED_K_MULT": ((_shape(K=320, **_BIG), "sched128"), (_shape(K=288, **_BIG), "reg128")),
+    "SCHED_HEAD_TILES": ((_shape(2048, 58200, 256, lse=True), "sched128"), (HEAD, "dma256")),     # 8 x 228 = 1824, 9 x 228 = 2052
+    "SKINNY_MAX_N": ((_shape(70, 256, 512), "skinny32"), (_shape(70, 257, 512), "reg64")),
+    "SKINNY_K_MULT": ((_shape(70, 256, 544), "skinny32"), (_shape(70, 256, 528), "reg64")),
+    "SKINNY_MIN_K": ((_shape(70, 256, 512), "skinny32"), (_shape(70, 256, 480), "reg64")),
+    "SPLIT_MIN_K": ((_shape(K=256, precision=3, **_BIG), "split128"), (_shape(K=252, precision=3, **_BIG), "reg128")),
+    "SPLIT_MIN_TILES": ((_shape(2048, 2048, 256, precision=1), "split128"), (_shape(2048, 1920, 256, precision=1), "reg64")),
+    "SPLIT_BIG_TILES": ((_shape(5900, 5632, 256, precision=1), "split256"), (_shape(5900, 5376, 256, precision=1), "split128")),
+    "SPLIT_MDEV_BIG_M": ((_shape(1 << 17, 300, 256, precision=2, m_dev=1), "split256"),
+                         (_shape((1 << 17) - 1, 300, 256, precision=2, m_dev=1), "split128")),
+    "SMALL_TILES": ((_shape(2048, 2048, 192), "reg128"), (_shape(2048, 1920, 192), "reg64")),
+}
+
+
+def _all_shapes():
+    cases = [ref.shape_desc(c)[0] for c in ref.CASES]
+    cases = [dict(d, alpha=0.0) if isinstance(d["alpha"], str) else d for d in cases]      # "unit": a value make_case() works out
+    return [d for d, _ in EDGES] + cases + [d for pair in PAIRS.values() for d, _ in pair]
+
+
+def test_route_constants_are_the_sources(route_program):
+    """gemm_ref.route() against the dispatcher itself (csrc/gemm_route.h: gemm_route, gemm_tile_order), and the header's constants
+    against gemm_ref's, by value."""
+    got = dict(l.split() for l in ask(route_program, "constants"))
+    assert set(got) == set(CONSTANTS) | {"MAX_TILE_ORDER"} and set(PAIRS) == set(CONSTANTS) and len(CONSTANTS) == 17
+    for name in got:
+        assert int(got[name]) == getattr(ref, name), name
+    for name, pair in PAIRS.items():                                   # the pairs straddle: two routes, as written
+        assert pair[0][1] != pair[1][1] and [ref.route(d) for d, _ in pair] == [r for _, r in pair], name
+    shapes = _all_shapes()
+    real = real_routes(route_program, shapes)
+    for d, (rt, order) in zip(shapes, real):
+        assert rt == ref.route(d), (d, rt)
+        assert order == ref.resolved_tile_order(d), d
+    for (d, want), (rt, _) in zip(EDGES, real):                       # (the hand-written expectations, asked of the code too)
+        assert rt == want, d
+    # the three runtime switches
+    lse = [bool(d["lse"]) for d in shapes]
+    base = [r for r, _ in real]
+    assert "sched128" in base and "skinny32" in base and any(r == "sched128" and l for r, l in zip(base, lse))
+    off = [r for r, _ in real_routes(route_program, shapes, env={"GNNLM_GEMM_SCHED": "0"})]
+    assert "sched128" not in off and all(a == b for a, b in zip(off, base) if b != "sched128")
+    one = [r for r, _ in real_routes(route_program, shapes, env={"GNNLM_GEMM_SCHED": "1"})]
+    assert not any(r == "sched128" and l for r, l in zip(one, lse)) and any(r == "sched128" for r in one)
+    assert all(a == b for a, b, l in zip(one, base, lse) if not l)
+    assert real_routes(route_program, [HEAD])[0][0] == "dma256"
+    assert real_routes(route_program, [HEAD], env={"GNNLM_GEMM_SCHED": "7"})[0][0] == "sched128"
+    noskinny = [r for r, _ in real_routes(route_program, shapes, env={"GNNLM_GEMM_SKINNY": "0"})]
+    assert "skinny32" not in noskinny and all(a == b for a, b in zip(noskinny, base) if b != "skinny32")
+    k256, k512 = _shape(K=256, **_BIG), _shape(K=512, **_BIG)
+    assert [r for r, _ in real_routes(route_program, [k256, k512])] == ["sched128", "sched128"]
+    assert [r for r, _ in real_routes(route_program, [k256, k512], env={"GNNLM_GEMM_SCHED_MINK": "512"})] == ["reg128", "sched128"]
+    # what the sources still say in text: the log-sum-exp flavour exists for 128-wide tiles only (LSE is never `small`), the
+    # A-stationary kernel is written for one K, and lse_reduce's choice of kernel
+    main, dma = src("gemm_f32.hip"), src("gemm_f32_dma.hip")
+    assert "if constexpr (BN == 128) {" in main
+    assert "gemm_lse_astationary_kernel<ASTAT_K>" in dma and "static_assert(K == 64" in dma and ref.ASTAT_K == 64
     red = main[main.index("int lse_reduce("):]
     assert "if (n_parts >= 1024)" in red
 
 
 def test_refusals_are_the_sources():
     """every GNNLM_REQUIRE of gemm_nt() has its line in refusal()"""
-    main = src("gemm_f32.hip")
+    main = src("gemm.hip")
     body = main[main.index("int gemm_nt(const GemmParams& desc"):main.index("if (p.M == 0) return OK;")]
     msgs = re.findall(r'GNNLM_REQUIRE\(.*?"gemm: ([^"]*)"\);', body)
     assert len(msgs) == 11
@@ -277,49 +375,10 @@ def test_refusals_are_the_sources():
         assert ref.refusal(dict(lse, **change)) is None, change
 
 
-def _shape(M, N, K, **kw):
-    d = dict(ref.DESC_DEFAULTS)
-    d.update(A=True, W=True, C=True, M=M, N=N, K=K, lda=K, ldw=K)
-    d.update(kw)
-    return d
-
-
 def test_route_edges():
     """One step to either side of every constant."""
-    r = ref.route
-    big = dict(M=2050, N=1990)
-    assert r(_shape(K=256, **big)) == "sched128" and r(_shape(K=192, **big)) == "reg128" and r(_shape(K=288, **big)) == "reg128"
-    assert r(_shape(K=320, **big)) == "sched128" and r(_shape(K=256, precision=3, **big)) == "split128"
-    assert r(_shape(K=252, precision=3, **big)) == "reg128"
-    assert r(_shape(2048, 2048, 256)) == "sched128" and r(_shape(2048, 1920, 256)) == "reg64"             # 256 / 240 tiles of 128
-    assert r(_shape(2048, 1920, 256, lse=True)) == "dma128"                                              # LSE is never small
-    assert r(_shape(2048, 1920, 256, precision=1)) == "reg64"
-    assert r(_shape(K=544, **big)) == "dma128" and r(_shape(K=544, m_dev=5, **big)) == "reg128"
-    assert r(_shape(K=480, **big)) == "reg128" and r(_shape(K=512 + 32, batch1=2, **big)) == "dma128"
-    assert r(_shape(257, 261, 128, batch1=16, batch2=32)) == "dma256" and r(_shape(257, 261, 128, batch1=16, batch2=31)) == "reg128"
-    assert r(_shape(257, 261, 96, batch1=16, batch2=32)) == "reg128"
-    assert r(_shape(2049, 58200, 128, lse=True)) == "dma256" and r(_shape(2048, 58200, 128, lse=True)) == "dma128"
-    assert r(_shape(2049, 58200, 256, lse=True)) == "dma256" and r(_shape(2049, 58200, 256, lse=True, m_dev=9)) == "sched128"
-    assert r(_shape(129, 300, 64, lse=True)) == "astat128" and r(_shape(129, 300, 64, lse=True, precision=3)) == "reg128"
-    assert r(_shape(128 * 768, 300, 64, lse=True)) == "astat128" and r(_shape(128 * 768 + 1, 300, 64, lse=True)) == "reg128"
-    assert r(_shape(129, 300, 96, lse=True)) == "reg128" and r(_shape(129, 300, 128, lse=True)) == "dma128"
-    assert r(_shape(129, 300, 64)) == "reg64"
-    assert r(_shape(70, 256, 512)) == "skinny32" and r(_shape(70, 257, 512)) == "reg64" and r(_shape(70, 256, 480)) == "reg64"
-    assert r(_shape(70, 256, 528)) == "reg64" and r(_shape(70, 256, 512, batch2=2)) == "reg64"
-    assert r(_shape(70, 256, 512, precision=2)) == "reg64" and r(_shape(70, 256, 512, lse=True)) == "dma128"
-    assert r(_shape(100000, 256, 512)) == "skinny32"                                                       # never from the row count
-    assert r(_shape(5900, 5900, 256, precision=1)) == "split256" and r(_shape(5900, 5632, 256, precision=1)) == "split256"    # 24 x 22 = 528, 24 x 21 = 504
-    assert r(_shape(5900, 5376, 256, precision=1)) == "split128"
-    assert r(_shape(5900, 5900, 256, precision=1, m_dev=1)) == "split128"
-    assert r(_shape(1 << 17, 300, 256, precision=2, m_dev=1)) == "split256" and r(_shape((1 << 17) - 1, 300, 256, precision=2, m_dev=1)) == "split128"
-    assert r(_shape(0, 5, 8)) == "none"
-    # the 32-bit byte offsets of the scheduled kernel: N * ldw * 4 and a_rows_bound * lda * 4 below 2^32
-    assert r(_shape(300, 1 << 20, 256, ldw=1020)) == "sched128" and r(_shape(300, 1 << 20, 256, ldw=1024)) == "dma256"
-    assert r(_shape(1 << 20, 300, 256, lda=1020)) == "sched128" and r(_shape(1 << 20, 300, 256, lda=1024)) == "dma256"
-    g = dict(a_rows=True, K=256, **big)
-    assert r(_shape(a_rows_bound=0, **g)) == "reg128" and r(_shape(a_rows_bound=5, **g)) == "sched128"
-    assert r(_shape(a_rows_bound=1 << 22, **g)) == "reg128" and r(_shape(a_rows_bound=(1 << 22) - 1, **g)) == "sched128"
-    assert r(_shape(a_rows_bound=0, lse=True, **g)) == "dma128"
+    for d, want in EDGES:
+        assert ref.route(d) == want, d
     # tile_order: resolved before the dispatch, never part of it
     assert ref.resolved_tile_order(_shape(10, 9, 8)) == 1 and ref.resolved_tile_order(_shape(9, 9, 8)) == 2
     assert ref.resolved_tile_order(_shape(10, 9, 8, m_dev=3)) == 2 and ref.resolved_tile_order(_shape(10, 9, 8, tile_order=6)) == 6
@@ -344,22 +403,24 @@ def test_tile_walk_is_a_permutation(tile_order):
     assert ref.tile_walk(4, 3, 2) == [(0, 0), (1, 0), (0, 1), (1, 1), (2, 0), (2, 1)]      # GM = 2: a short last band
 
 
-def test_the_four_kernels_spell_one_walk():
-    copies = {}
-    for f in ("gemm_f32.hip", "gemm_f32_sched.hip", "gemm_f32_dma.hip", "gemm_split.hip"):
-        text = flat(re.sub(r"/\*.*?\*/", "", src(f), flags=re.S))
-        a = text.index("if(p.tile_order==1){tm=t/tiles_n;tn=t%tiles_n;}elseif(p.tile_order==2){tn=t/tiles_m;tm=t%tiles_m;}else{")
-        b = text.index("tm=band*GM+r%m_in;}", a)
-        copies[f] = text[a:b + len("tm=band*GM+r%m_in;}")]
-        assert text.count("p.tile_order==1") == 1, f                   # one walk per file
-    assert len(set(copies.values())) == 1, copies
-    walk = next(iter(copies.values()))
-    assert walk.endswith("else{" + "".join(ref.TILE_WALK_SOURCE) + "}")
+def test_the_four_kernels_spell_one_walk(route_program):
+    """One walk, in csrc/gemm_route.h: it is ref.tile_walk, and no kernel file decodes tile_order itself."""
+    for tile_order in (1, 2, 3, 4, 6, 9, 66):                          # the orders and tile counts of test_tile_walk_is_a_permutation
+        for tiles_m in (1, 2, 5, 17):
+            for tiles_n in (1, 3, 16):
+                got = [tuple(int(x) for x in l.split()) for l in ask(route_program, "walk", str(tile_order), str(tiles_m), str(tiles_n))]
+                assert got == ref.tile_walk(tile_order, tiles_m, tiles_n), (tile_order, tiles_m, tiles_n)
+    files = sorted(f for f in os.listdir(CSRC) if f.startswith("gemm") and f.endswith(".hip"))
+    assert {"gemm.hip", "gemm_f32.hip", "gemm_f32_sched.hip", "gemm_f32_dma.hip", "gemm_f32_skinny.hip", "gemm_split.hip"} <= set(files)
+    for f in files:
+        assert "tile_order ==" not in src(f) and "tile_order==" not in flat(src(f)), f
+    walkers = [f for f in files if "gemm_tile_walk(" in src(f) or "GNNLM_TILE_WALK(" in src(f)]
+    assert walkers == ["gemm_f32.hip", "gemm_f32_dma.hip", "gemm_f32_sched.hip", "gemm_split.hip"]
     # the two kernels without a walk do not read the field
     assert "tile_order" not in src("gemm_f32_skinny.hip")
     astat = src("gemm_f32_dma.hip")
-    astat = astat[astat.index("void gemm_lse_astationary_kernel"):astat.index("#ifndef GNNLM_DMA_BK")]
-    assert "tile_order" not in astat
+    astat = astat[astat.index("void gemm_lse_astationary_kernel"):astat.index("int launch_dma(")]
+    assert "tile_order" not in astat and "void gemm_nt_f32_dma_kernel" not in astat
 
 
 # ------------------------------------------------------------------------------------------ 4. no case is blind to a field it sets

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Writes gnn-lm_amd/csrc/gemm_sched_loop.inc: the hand-placed main loop (one inline-asm statement) of the scheduled
+"""Writes gnn-lm_amd/csrc/gemm_sched_loop.inc (and gemm_sched_clobbers.inc): the hand-placed main loop (one inline-asm statement) of the scheduled
 f32 GEMM kernel (csrc/gemm_f32_sched.hip).  128x128x32 stages, 4 waves of 64x64, v_mfma_f32_32x32x2_f32.
 
 Per stage and wave: 64 MFMAs, 16 ds_read_b128 (fragments of k-group g + 1 under the MFMAs of group g), 8 global loads of the
@@ -15,6 +15,8 @@ Operands of the asm statement (named):
   oa0..3 / ow0..3   per-thread byte offsets of the four A / W rows it stages ("v")
   lw   LDS write address of the thread (row t/8, swizzled 16-B slot)
   ra0..3 / rb0..3   LDS read addresses of the A / W fragments of k-groups 0..3
+Every MFMA line takes its two source operands through GNNLM_MFMA_AB(a, w), which the kernel defines before the #include: (a, w) for the
+store epilogue, (w, a) for the log-sum-exp epilogue (transposed accumulators).  The preprocessor joins the pieces into one string.
 Fixed registers (clobbers): v160-v191 staging, v192-v207 A fragments (2 sets x 2 tiles x 4), v208-v223 W fragments."""
 import os
 
@@ -49,8 +51,7 @@ def stage(b, last_of_pair):
         nxt = frag_reads(g + 1, b, 1 - s) if g < 3 else []
         for kk in range(4):
             for (i, j) in ((0, 0), (0, 1), (1, 1), (1, 0)):
-                x, y = (FB(s, j, kk), FA(s, i, kk)) if SWAP else (FA(s, i, kk), FB(s, j, kk))     # SWAP: transposed accumulators (LSE epilogue)
-                L.append(f"v_mfma_f32_32x32x2_f32 {ACC[(i, j)]}, {x}, {y}, {ACC[(i, j)]}")
+                L.append((f"v_mfma_f32_32x32x2_f32 {ACC[(i, j)]}, ", FA(s, i, kk), FB(s, j, kk), f", {ACC[(i, j)]}"))
                 m = n % 16
                 if g == 0 and m < 8:
                     L.append(loads[m])                                      # the next stage's rows, early
@@ -71,22 +72,18 @@ def stage(b, last_of_pair):
     return L
 
 
-SWAP = False
-
-
 OUT_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gnn-lm_amd", "csrc")
 
 
 def main():
-    global SWAP, OUT_DIR
+    global OUT_DIR
     import sys
     if len(sys.argv) > 1:                      # tools/gen_gemm_sched.py <dir>: write there (tests compare with csrc/)
         OUT_DIR = sys.argv[1]
-    for SWAP, fname in ((False, "gemm_sched_loop.inc"), (True, "gemm_sched_loop_t.inc")):
-        emit(fname)
+    emit("gemm_sched_loop.inc")
     out = os.path.join(OUT_DIR, "gemm_sched_clobbers.inc")
     with open(out, "w") as f:
-        f.write("// generated by tools/gen_gemm_sched.py -- do not edit: the fixed registers of gemm_sched_loop*.inc\n")
+        f.write("// generated by tools/gen_gemm_sched.py -- do not edit: the fixed registers of gemm_sched_loop.inc\n")
         regs = [f'"v{BASE + i}"' for i in range(64)]
         for i in range(0, 64, 16):
             f.write(", ".join(regs[i:i + 16]) + ("," if i < 48 else "") + "\n")
@@ -99,12 +96,14 @@ def emit(fname):
     L += stage(1, True)
     L += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cmp_lg_u32 %[cnt], 0", "s_cbranch_scc1 1b",
           "s_waitcnt lgkmcnt(0)", "s_nop 15", "s_nop 7"]
-    txt = "\n".join(L)
     out = os.path.join(OUT_DIR, fname)
     with open(out, "w") as f:
         f.write("// generated by tools/gen_gemm_sched.py -- do not edit\n")
-        for l in txt.split("\n"):
-            f.write('"' + l + '\\n"\n')
+        for l in L:
+            if isinstance(l, tuple):                # an MFMA: head, A fragment, W fragment, tail
+                f.write(f'"{l[0]}" GNNLM_MFMA_AB("{l[1]}", "{l[2]}") "{l[3]}\\n"\n')
+            else:
+                f.write('"' + l + '\\n"\n')
     print(out, len(L), "lines")
 
 
