@@ -2,6 +2,7 @@
 
     python -m gnnlm_amd.beam_search DATA --path base.pt --gen-subset test --n-prompts 8 --prompt-len 32 --max-len-b 64 \\
         [--beam 5] [--nbest 1] [--lenpen 1] [--unnormalized] [--min-len 1] [--temperature 1] [--unkpen X] [--fp16] [--score-prompt] \\
+        [--diverse-beam-groups G --diverse-beam-strength 0.5 | --diversity-rate R] \\
         [--knnlm --k 1024 --lmbda 0.25 --knn-temperature 1 --probe 32 --dstore-dir D --index-file F --knn-sim-func do_not_recomp_ip]
 
 Mirror of ``SequenceGenerator`` (fairseq/sequence_generator.py) with ``search.BeamSearch`` (fairseq/search.py:49-85) for one
@@ -15,7 +16,10 @@ row at the prompt's cumulative log-probability, count length from p.  That is th
   rules     t == n: every column but ``eos`` is -inf (the forced ``eos`` at max_len, sequence_generator.py:283-285); otherwise
             ``len0[b] + t < min_len`` forbids ``eos`` for sentence b (:315-317)
   top       ``ops.topk_merge`` with k = 2 * beam
-  select    ``ops.beam_select``: candidates, finalization, survivors, the table of cache slots, ``finished`` / ``done`` -- one launch
+  select    ``ops.beam_select``: candidates, finalization, survivors, the table of cache slots, ``finished`` / ``done`` -- one launch;
+            with ``--diverse-beam-groups`` (``search.DiverseBeamSearch``, search.py:105-164) or ``--diversity-rate``
+            (``search.DiverseSiblingsSearch``, :291-353) ``ops.beam_select_diverse``, the same launch with the candidates drawn group
+            by group under the Hamming penalty, or with the sibling penalty
   step      ``TransformerLM.step(next, cache, src=table)`` unless t == n
 
 Hypothesis j of sentence b is cache sequence ("slot") ``b * beam + j``; key row u of a hypothesis lives in slot ``table[slot, u]``, so
@@ -27,7 +31,9 @@ the cumulative history, a stable sort by score descending, ``nbest`` returned.
 Not the reference's: when MORE than ``beam`` of a step's 2 * beam candidates are ``eos`` the reference carries the surplus as
 ignored hypotheses; here the slots without a survivor are dead (``pad``, -inf).  Refused by name: ``--sampling``, ``--sampling-topp``,
 ``--no-repeat-ngram-size``, ``--graph``, ``--sweep-*``, more than one process, ``2 * beam > V - 1``, ``--beam`` > 32, ``--nbest`` > beam,
-``--score-prompt`` with ``--knnlm``.
+``--score-prompt`` with ``--knnlm``, a negative ``--diverse-beam-strength`` and a ``--diversity-rate`` in (-1, 0): the selection is made
+from each hypothesis's best 2 * beam tokens, which holds every candidate a penalty can leave among the best only if penalties lower.
+``--diversity-rate`` -1 (the default) or below is "off" and 0 is plain beam search, as in the reference (fairseq_task.py:257).
 """
 import logging
 import sys
@@ -95,6 +101,15 @@ class BeamGenerator(Generator):
         if nbest is not None and not 1 <= nbest <= beam:
             raise ValueError(f"--nbest {nbest}: between 1 and --beam {beam}")
 
+    @staticmethod
+    def check_diverse(beam, groups, strength, diversity_rate):
+        if groups < 1 or beam % groups:
+            raise ValueError("DiverseBeamSearch requires --beam to be divisible by the number of groups")
+        if not 0 <= strength < float("inf") or not 0 <= diversity_rate < float("inf"):
+            raise ValueError("--diverse-beam-strength / --diversity-rate: a penalty is finite and not negative")
+        if groups > 1 and diversity_rate != 0:
+            raise ValueError("Provided Search parameters are mutually exclusive.")
+
     def start(self, prompts, max_new, beam, temperature=1.0, unk_penalty=0.0, score0=None, len0=None, score_prompt=False):
         """Prefill the prompts once per sentence into a cache of ``B * beam`` slots -> dict(cache, state, table, x, extra, len0, score0,
         want_ffn): everything :meth:`advance` needs; ``x`` / ``extra`` are the B rows the first selection is made from."""
@@ -140,19 +155,27 @@ class BeamGenerator(Generator):
         return val, idx
 
     def generate(self, prompts, max_new, beam=5, nbest=None, lenpen=1.0, unnormalized=False, min_len=1, temperature=1.0, unk_penalty=0.0,
-                 score0=None, len0=None, score_prompt=False):
+                 score0=None, len0=None, score_prompt=False, groups=1, strength=0.5, diversity_rate=0.0):
         """prompts: a list of non-empty lists of token ids, fed as they are -> per prompt the ``nbest`` (default: all finalized, at most
         ``beam``) hypotheses, best first: dicts of ``tokens`` (numpy int64: up to ``max_new`` new tokens and the ``eos``), ``score``, ``raw``,
         ``positional_scores``.  ``score0`` / ``len0`` [B]: the prompts' cumulative log-probability and length as the reference counts them
-        (default zeros: a hypothesis is scored over what was generated); ``score_prompt`` computes both from the prefill."""
+        (default zeros: a hypothesis is scored over what was generated); ``score_prompt`` computes both from the prefill.  ``groups`` > 1:
+        diverse beam search, ``beam / groups`` hypotheses per group, a token costs ``strength`` for every earlier group's candidate that
+        chose it at the step; ``diversity_rate`` > 0: the c-th best continuation of a hypothesis loses ``c * diversity_rate``.  The
+        penalties stay in the scores.  With ``groups`` 1 and ``diversity_rate`` 0 the plain selection is launched."""
         lm = self.lm
         self.check_beam(max_new, beam, nbest, float(temperature), self.vocab)
+        self.check_diverse(beam, groups, strength, diversity_rate)
+        diverse = groups > 1 or diversity_rate != 0
         run = self.start(prompts, max_new, beam, float(temperature), float(unk_penalty), score0, len0, score_prompt)
         cache, state, table = run["cache"], run["state"], run["table"]
         x, extra = run["x"], run["extra"]
         for t in range(max_new + 1):
             val, idx = self.candidates(run, x, extra, t, min_len, temperature, unk_penalty)
-            ops.beam_select(val, idx, state, src=table, eos=EOS, pad=PAD)
+            if diverse:
+                ops.beam_select_diverse(val, idx, state, src=table, eos=EOS, pad=PAD, groups=groups, strength=strength, rate=diversity_rate)
+            else:
+                ops.beam_select(val, idx, state, src=table, eos=EOS, pad=PAD)
             if t == max_new or ((t + 1) % DONE_EVERY == 0 and bool(state.finished.all())):
                 break
             x, extra = lm.step(state.next, cache, want_ffn_input=run["want_ffn"], src=table)
@@ -177,7 +200,21 @@ def get_parser():
     p.add_argument("--lenpen", type=float, default=1.0)
     p.add_argument("--unnormalized", action="store_true")
     p.add_argument("--score-prompt", action="store_true", help="score and count the prompt as the reference's prefix_tokens run does")
+    # the reference's defaults (-1, 0.5, -1.0) are what diverse_args / check_args read when a flag is not given: a flag left out
+    # leaves no name in the namespace, so the namespace of a plain run is what it was before these flags
+    S = argparse.SUPPRESS
+    p.add_argument("--diverse-beam-groups", type=int, default=S, help="diverse beam search with this many groups (default -1: off)")
+    p.add_argument("--diverse-beam-strength", type=float, default=S, help="what a token costs a group per earlier group's candidate that chose it (default 0.5)")
+    p.add_argument("--diversity-rate", type=float, default=S, help="sibling penalty: the c-th best continuation of a hypothesis loses c * rate (default -1.0: off)")
     return p
+
+
+def diverse_args(args):
+    """-> (groups, strength, diversity_rate) as :meth:`BeamGenerator.generate` takes them.  The flags are read with their defaults when the
+    namespace lacks them; groups <= 0 and a rate <= -1 mean "off" (fairseq_task.py:247, :257), a rate of 0 is plain beam search."""
+    groups = getattr(args, "diverse_beam_groups", -1)
+    rate = getattr(args, "diversity_rate", -1.0)
+    return (groups if groups > 0 else 1), getattr(args, "diverse_beam_strength", 0.5), (rate if rate > 0 else 0.0)
 
 
 def check_args(args):
@@ -189,6 +226,16 @@ def check_args(args):
         raise ValueError(f"--beam {args.beam}: between 1 and {MAX_BEAM}")
     if not 1 <= args.nbest <= args.beam:
         raise ValueError(f"--nbest {args.nbest}: between 1 and --beam {args.beam}")
+    groups, strength, rate = getattr(args, "diverse_beam_groups", -1), getattr(args, "diverse_beam_strength", 0.5), getattr(args, "diversity_rate", -1.0)
+    if groups > 0 and rate > 0:                              # (fairseq_task.py:229-241; sampling is refused above)
+        raise ValueError("Provided Search parameters are mutually exclusive.")
+    if groups > 0 and args.beam % groups:
+        raise ValueError("DiverseBeamSearch requires --beam to be divisible by the number of groups")
+    if not 0 <= strength < float("inf"):
+        raise ValueError(f"--diverse-beam-strength {strength}: finite and not negative (a negative penalty can lift a token from outside a hypothesis's best 2 * beam)")
+    if -1 < rate < 0 or rate != rate or rate == float("inf"):
+        raise ValueError(f"--diversity-rate {rate}: the reference runs DiverseSiblingsSearch with any rate above -1; a rate in (-1, 0) rewards siblings "
+                         "and is not built (the candidates are each hypothesis's best 2 * beam tokens); -1 is off, 0 is plain beam search")
     if args.max_len_b < 1:
         raise ValueError("--max-len-b must be at least 1")
     if not args.temperature > 0:
@@ -210,8 +257,10 @@ def main(args, model=None, file=None):
     knn = gen_common.load_knn(args, model, device)
     g = BeamGenerator(model, knn, args.knn_keytype, k=args.k if args.knnlm else 0, lmbda=args.lmbda if args.knnlm else 0.0,
                       knn_temperature=args.knn_temperature)
+    groups, strength, rate = diverse_args(args)
     hyps = g.generate(prompts, args.max_len_b, beam=args.beam, nbest=args.nbest, lenpen=args.lenpen, unnormalized=args.unnormalized,
-                      min_len=args.min_len, temperature=args.temperature, unk_penalty=args.unkpen, score_prompt=args.score_prompt)
+                      min_len=args.min_len, temperature=args.temperature, unk_penalty=args.unkpen, score_prompt=args.score_prompt,
+                      groups=groups, strength=strength, diversity_rate=rate)
     word = gen_common.word_of(args.data)
     for i, p in enumerate(prompts):
         print(f"S-{i}\t" + " ".join(word(t) for t in p[1:]), file=file)

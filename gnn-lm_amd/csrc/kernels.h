@@ -133,6 +133,7 @@ struct SlotTable { const int32_t* src; int64_t ld; };
 int decode_attn(const gnnlm_decode_attn_t& d, const SlotTable* tab, hipStream_t stream);
 // one beam-search step of every sentence (beam.hip)
 int beam_select(const gnnlm_beam_select_t& d, hipStream_t stream);
+int beam_select_diverse(const gnnlm_beam_select_diverse_t& d, hipStream_t stream);
 // K' | V' of the packed q | k | v rows [n_tok, ld_src] -> cache rows [0, min(len_b, max_rows)) of sequence b = block b of `layer`
 int kv_cache_fill(const float* qkv, int64_t ld_src, const gnnlm_kv_cache_t& c, int layer, const gnnlm_ragged_t& rg, int max_rows,
                   hipStream_t stream);

@@ -440,6 +440,26 @@ def beam_select(cand_val, cand_id, state, src=None, src_out=None, eos=2, pad=1):
     ``hist_tok`` i64 / ``hist_par`` int32 / ``hist_score`` f32 [B, max_new + 1, beam], ``fin_tok`` i64 / ``fin_cum`` f32 [B, beam, max_new + 1],
     ``fin_len`` int32 / ``fin_score`` f32 [B, beam] (``beam_search.BeamState`` is one).  ``src`` int32 [B * beam, cap]: the table of cache
     slots, updated in place (or into ``src_out``).  The rules are the header's; nothing is read back."""
+    d = _lib.gnnlm_beam_select_t()
+    _beam_select_desc(d, cand_val, cand_id, state, src, src_out, eos, pad)
+    call_desc("gnnlm_beam_select", d)
+    return state.next, state.parent
+
+
+def beam_select_diverse(cand_val, cand_id, state, src=None, src_out=None, eos=2, pad=1, groups=1, strength=0.5, rate=0.0):
+    """:func:`beam_select` with the step's candidates drawn by diverse groups or with the sibling penalty (``gnnlm_beam_select_diverse``):
+    ``groups`` G divides ``state.beam``; group g owns the hypotheses g, g + G, .. and a candidate's value is lowered by ``strength`` for every
+    time the groups before its own chose its token at this step; the groups' lists are interleaved, not sorted again.  ``rate`` (with
+    ``groups`` 1): the c-th best candidate of a hypothesis loses ``c * rate``.  ``groups=1, rate=0`` gives :func:`beam_select`'s results."""
+    d = _lib.gnnlm_beam_select_diverse_t()
+    _beam_select_desc(d.sel, cand_val, cand_id, state, src, src_out, eos, pad)
+    d.groups, d.strength, d.rate = int(groups), float(strength), float(rate)
+    call_desc("gnnlm_beam_select_diverse", d)
+    return state.next, state.parent
+
+
+def _beam_select_desc(d, cand_val, cand_id, state, src, src_out, eos, pad):
+    """Fill a ``gnnlm_beam_select_t`` from the arguments of :func:`beam_select`."""
     _dev(cand_val, cand_id)
     _f32(cand_val, state.score, state.hist_score, state.fin_cum, state.fin_score)
     _dtype(cand_id, torch.int64, "cand_id")
@@ -457,7 +477,6 @@ def beam_select(cand_val, cand_id, state, src=None, src_out=None, eos=2, pad=1):
         x = getattr(state, name)
         if tuple(x.shape) != shp or not x.is_cuda or not x.is_contiguous():
             raise ValueError(f"beam_select: state.{name} must be a contiguous device tensor {shp}")
-    d = _lib.gnnlm_beam_select_t()
     d.cand_val, d.ld_val = cand_val.data_ptr(), _row_stride(cand_val)
     d.cand_id, d.ld_id = cand_id.data_ptr(), _row_stride(cand_id)
     d.B, d.beam, d.beam_in, d.N = B, beam, cand_val.shape[0] // B if B else 1, cand_val.shape[1]
@@ -476,8 +495,6 @@ def beam_select(cand_val, cand_id, state, src=None, src_out=None, eos=2, pad=1):
         if _src_table(dst, B * beam, d.cap, "beam_select") != d.ld_src or dst.shape != src.shape:
             raise ValueError("beam_select: src and src_out must share shape and row stride")
         d.src_in, d.src_out = src.data_ptr(), dst.data_ptr()
-    call_desc("gnnlm_beam_select", d)
-    return state.next, state.parent
 
 
 def ptr_strided(t):

@@ -1180,6 +1180,38 @@ typedef struct gnnlm_beam_select {
 } gnnlm_beam_select_t;
 int gnnlm_beam_select(const gnnlm_beam_select_t* desc, void* stream);
 
+/* gnnlm_beam_select with the reference's two diverse strategies: search.DiverseBeamSearch (fairseq/search.py:105-164: groups,
+ * strength) and search.DiverseSiblingsSearch (:291-353: rate).  Only how the step's candidate list is drawn differs; finalize,
+ * survive, table and finish are gnnlm_beam_select's own, run on that list.  One launch, one workgroup per sentence, nothing read back.
+ * Additive to ABI 12: a new struct and a new entry; gnnlm_beam_select_t and gnnlm_beam_select are as they were.
+ *   groups   G = groups, beam_g = beam / G.  Group g owns the hypotheses j = g, g + G, ..; with beam_in == 1 every group takes the
+ *            sentence's one row.  The groups run in order.  The value of group g's candidate (j, c) with token k is
+ *            fl32(score_in[j] + fl32(cand_val + fl32(-strength * n[k]))), n[k] = how many candidates the groups before g chose for
+ *            token k at this step -- all of their chosen candidates, survivors or not; with n[k] == 0 the value is
+ *            gnnlm_beam_select's fl32(score_in[j] + cand_val).  Absent: cand_val or the value not finite.  Inside a group the order
+ *            is gnnlm_beam_select's (value descending, j ascending, token ascending); its first C_g = min(2 * beam_g, present) are
+ *            chosen.  The step's list has 2 * beam places: place c * G + g holds candidate c of group g, a place without one (c >=
+ *            C_g) is empty; the list is NOT sorted again.  The penalty stays in the value, hence in score_out and the histories.
+ *   siblings (groups == 1, rate != 0, beam_in == beam; with beam_in == 1 the rate is not applied) the candidate that is the c-th of
+ *            hypothesis j, c = 1 .. min(2 * beam, present of j) in j's own order (fl32(score_in[j] + cand_val) descending, token
+ *            ascending, column ascending), has the value fl32(fl32(score_in[j] + cand_val) - fl32(c * rate)); j's later
+ *            candidates are absent.  The list is the first min(2 * beam, present) of those under gnnlm_beam_select's order.
+ *   the list finalize scans the places below beam, survive every place, both in place order; an empty place is skipped.  When an eos
+ *            is finalized the survivors behind it move up, so a hypothesis of one group may continue another group's (the reference's
+ *            behaviour).  groups == 1 with rate == 0 gives gnnlm_beam_select's results bit for bit.
+ * Both penalties only lower a value and fewer than 2 * beam tokens can carry one, so the best 2 * beam_g penalised candidates of a
+ * hypothesis lie among its 2 * beam best unpenalised ones: N >= 2 * beam columns are enough, and negative penalties are refused.
+ * GNNLM_E_INVALID before anything is launched: whatever gnnlm_beam_select refuses in `sel`, groups < 1, beam % groups != 0, strength
+ * or rate negative or not finite, groups > 1 together with rate != 0. */
+typedef struct gnnlm_beam_select_diverse {
+    gnnlm_beam_select_t sel;
+    int32_t groups;                             /* G >= 1, beam % G == 0 */
+    float strength;                             /* >= 0; read with groups > 1 */
+    float rate;                                 /* >= 0; != 0 only with groups == 1 */
+    int32_t reserved;                           /* leave 0 */
+} gnnlm_beam_select_diverse_t;
+int gnnlm_beam_select_diverse(const gnnlm_beam_select_diverse_t* desc, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * kNN-LM on the base LM: the SCORED rows of packed samples (each sample = context rows, then scored rows: --context-window) as
  * one contiguous [n_out, d] query matrix, and / or the same rows scaled to unit length for a cosine index -- one launch instead of

@@ -2,7 +2,7 @@
 """One beam-search step of the base LM at the shape of adaptive_lm_wiki103 (16 layers, d = 1024, H = 8 so d_k = 128, ffn = 4096)
 against what a transcription of the reference's beam search would do on the same cache.
 
-    python tools/beam_bench.py [--steps 20 --warmup 3] [--beams 5,16] [--batches 1,8] [--lengths 512,3072]
+    python tools/beam_bench.py [--steps 20 --warmup 3] [--beams 5,16] [--batches 1,8] [--lengths 512,3072] [--groups 4 --strength 0.5]
 
 For every (beam, B, prompt length) it reports (device events, the median of --steps rounds after --warmup, the timed forms taking
 turns -- the protocol of tools/generate_bench.py):
@@ -15,6 +15,9 @@ turns -- the protocol of tools/generate_bench.py):
   * reorder              the index-select of one layer's K and V rows [0, len) by parent: ``reorder_incremental_state``, the copy the
                          table replaces.
   * select               ``gnnlm_beam_select`` alone (2 * beam candidates per hypothesis), the table update included.
+  * select, diverse      (``--groups`` G > 1) ``gnnlm_beam_select_diverse`` with G groups on the same buffers, taking turns with the plain
+                         select; the candidates' tokens are then drawn from 4 * beam ids per sentence, so that the groups' rows share tokens
+                         and the penalty reorders them (the plain select's work does not depend on the ids).
 Beside the attention times: the bytes each must move over the achievable HBM rate.  The plain attention reads 2 * B * beam * len * d * 4
 per layer; the table one reads the same rows but only 2 * (B * prompt + B * beam * generated) * d * 4 of them are distinct, the rest
 hits in cache.  Seeded synthetic weights, cache contents and candidates (none of them eos: no sentence ends).  One JSON line per case."""
@@ -46,6 +49,8 @@ def main():
     p.add_argument("--ffn", type=int, default=4096)
     p.add_argument("--vocab", type=int, default=267744)
     p.add_argument("--fp16", action="store_true")
+    p.add_argument("--groups", type=int, default=1, help="> 1: also time gnnlm_beam_select_diverse with this many groups")
+    p.add_argument("--strength", type=float, default=0.5)
     A = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("beam_bench needs the GPU: a timing taken elsewhere says nothing about it")
@@ -70,7 +75,8 @@ def main():
                 table = torch.zeros(S, cap, dtype=torch.int32, device=dev)
                 # sorted candidates, none of them eos, redrawn never: the selection's work does not depend on their values
                 cv = -torch.sort(torch.rand(S, N, device=dev, generator=g), dim=1).values
-                ci = torch.stack([torch.randperm(A.vocab - 4, device=dev, generator=g)[:N] + 4 for _ in range(S)])
+                pool = A.vocab - 4 if A.groups <= 1 else 2 * N
+                ci = torch.stack([torch.randperm(pool, device=dev, generator=g)[:N] + 4 for _ in range(S)])
 
                 def pair():
                     ops.beam_select(cv, ci, state, src=table)
@@ -128,7 +134,13 @@ def main():
                         fn()
                     prof = list(_lib.profile_end().values())[0]
                     kern.append(prof["total_ms"] / prof["launches"])
-                (t_select,), _ = median_ms([select], A.steps, A.warmup)
+                def select_diverse():
+                    ops.beam_select_diverse(cv, ci, state, src=table, groups=A.groups, strength=A.strength)
+
+                if A.groups > 1:
+                    (t_select, t_diverse), _ = median_ms([select, select_diverse], A.steps, A.warmup)
+                else:
+                    (t_select,), _ = median_ms([select], A.steps, A.warmup)
                 assert int(cache.n_bad.item()) == 0
                 gen = now - n
                 plain_bytes = 2 * S * now * d * 4
@@ -147,7 +159,9 @@ def main():
                                   "attn_plain_floor_ms": round(plain_bytes / HBM_RATE * 1e3, 5),
                                   "attn_table_floor_ms": round(distinct / HBM_RATE * 1e3, 5),
                                   "reorder_floor_ms": round(reorder_bytes / HBM_RATE * 1e3, 5),
-                                  "select_ms": round(t_select, 4)}), flush=True)
+                                  "select_ms": round(t_select, 4),
+                                  **({"groups": A.groups, "select_diverse_ms": round(t_diverse, 4),
+                                      "select_diverse_share_of_graph_step": round(t_diverse / t_graph, 4)} if A.groups > 1 else {})}), flush=True)
                 del cache, ws, bufk, bufv, table, state
                 torch.cuda.empty_cache()
 
