@@ -4,7 +4,7 @@
 //
 // A work item is (block, head, tile of 32 queries), looked up in a tile table the host derives from the block lengths
 // (ragged_tiles: heaviest tiles first, so one long block beside a thousand short ones does not become the tail of the launch);
-// one wave per item, four independent items per workgroup.  Layout as in the 256 x 128 kernel (attn.hip): scores as
+// one wave per item, four independent items per workgroup.  Layout as in the 256 x 128 kernel (causal_attn.hip): scores as
 // S^T = K' Q^T with v_mfma_f32_32x32x2_f32, so accumulator rows are KEYS and lane & 31 is the query -- a query's 32 scores of a
 // key tile sit in two lanes, the mask and the softmax are in-lane plus one v_permlane32_swap.  What is new is the running
 // maximum / sum over key tiles (a block of 3000 tokens has 94 of them; nothing but one tile of scores is ever live) and the

@@ -352,7 +352,7 @@ struct HgtForward {
         }
         GNNLM_TRY(linear(st.ht_in, d, w.wq_t, w.bq_t, b.q, Tt, d, d, nullptr, 1.f, s));
         GNNLM_TRY(linear(st.ht_in, d, w.wk_t, w.bk_t, b.k, Tt, d, d, nullptr, 1.f, s));
-        // recipe shape: V' row-major, then scores + masked softmax + P.V in one kernel (attn.hip)
+        // recipe shape: V' row-major, then scores + masked softmax + P.V in one kernel (causal_attn.hip)
         // (the kernel itself runs after the star branch and adds its result into the message sum, see tgt_output)
         if (p.fusedc) GNNLM_TRY(linear(st.ht_in, d, w.wv_t, w.bv_t, b.vt, Tt, d, d, nullptr, 1.f, s));
         return OK;

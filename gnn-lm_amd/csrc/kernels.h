@@ -63,10 +63,11 @@ int bucket_rows(const int64_t* rows, int64_t n, int64_t n_store, int64_t per, in
 int gather_rows_peer(const gnnlm_peer_gather_t& d, hipStream_t stream);
 int bucket_rows_padded(const int64_t* rows, int64_t n, int64_t n_store, int64_t per, int world, int64_t cap, int64_t* cursor,
                        int64_t* send_rows, int32_t* inv, int64_t* overflow, hipStream_t stream);
+// star_attn.hip: refusals, the route (star_route.h), one launch -- the generic kernel or one of the two launchers below
 int star_attn(const StarAttnParams& p, hipStream_t stream);
-// table-resident formulation for the PQ source, k_g <= 128 (star_tab.hip); star_attn dispatches to it
-bool star_attn_tab_eligible(const StarAttnParams& p);
-int star_attn_tab(const StarAttnParams& p, hipStream_t stream);
+struct StarPlan;
+// table-resident formulation for the PQ source, k_g <= 128 (star_tab.hip), called by star_attn with the plan star_route() made
+int star_attn_tab(const StarAttnParams& p, const StarPlan& plan, hipStream_t stream);
 
 // Neighbour (i, j) takes part in the star softmax iff its id is a row of the store, the row is present on this
 // shard (PQ source read from the store) and the caller's validity byte (exchange / gather_decode) says so: the
@@ -107,13 +108,13 @@ __device__ __forceinline__ const uint8_t* star_code_ptr(const StarAttnParams& p,
     return p.codes + star_code_row(p, i, j, id) * p.M;
 }
 // dense neighbour rows (layers >= 1), D in {256, 512, 1024}, H <= 8: one pass over the rows with a running softmax (star_dense.hip)
-bool star_attn_dense_eligible(const StarAttnParams& p);
-int star_attn_dense(const StarAttnParams& p, hipStream_t stream);
+int star_attn_dense(const StarAttnParams& p, const StarPlan& plan, hipStream_t stream);
+// chain_attn.hip
 int chain_attn(const ChainAttnParams& p, hipStream_t stream);
 
-// rows of S[b, h, w, :T] -> causal softmax (u <= w, and w-u < max_ctx if max_ctx > 0), in place
+// rows of S[b, h, w, :T] -> causal softmax (u <= w, and w-u < max_ctx if max_ctx > 0), in place (causal_attn.hip)
 int causal_softmax(float* S, int64_t n_mats, int T, int64_t ld, int max_ctx, hipStream_t stream);
-// fused scores + masked softmax + P.V for T = 256, d_k = 128 (attn.hip); Q, K', V are [n_blocks * T, ld] with head h at
+// fused scores + masked softmax + P.V for T = 256, d_k = 128 (causal_attn.hip); Q, K', V are [n_blocks * T, ld] with head h at
 // column h * dk
 bool causal_attn_fused_ok(int T, int dk);
 int causal_attn_fused(const float* Q, const float* K, const float* V, int64_t ld, float* out, int64_t ldo,

@@ -1,10 +1,10 @@
 // ('ntgt','inter','tgt') star attention over DENSE neighbour rows -- layers >= 1 of a multi-layer HGT, where a neighbour is
 // the centre state of its context group after l ntgt updates (fairseq/models/hgt.py:354-356,383-385 with the neighbour-side
-// projections absorbed into the query, see attn.hip): the rows come from the step's workspace or from the cross-batch
+// projections absorbed into the query, see star_attn.hip): the rows come from the step's workspace or from the cross-batch
 // centre-state cache.  HBM-bound by construction: 4 * D bytes per neighbour (4 KiB at d = 1024), 2.1 GB per layer for a
 // 4096-token batch with k_g = 128 -- and nothing else worth mentioning.
 //
-// The generic kernel (attn.hip: star_attn_kernel) walks the rows TWICE (scores, then the weighted sum; a token's 512 KiB of rows
+// The generic kernel (star_attn.hip: star_attn_kernel) walks the rows TWICE (scores, then the weighted sum; a token's 512 KiB of rows
 // do not survive in L2 between the passes: 1.7 ms per layer of a 4096-token batch = 1.2 TB/s of algorithmic bytes).  This one
 // reads every row ONCE: each wave owns whole rows (lane l holds floats [4 QPL l, 4 QPL (l + 1)) of the row), two rows per trip,
 // scores for the 8 heads by a transposing butterfly (reduce8), and a running softmax per head (max, normaliser and weighted sum
@@ -13,39 +13,10 @@
 // states over their quarter of the neighbours and are merged at the end in a fixed order (deterministic: same bits every run,
 // and for every way -- merged groups, cache slots, un-merged workspace rows -- the same neighbour rows reach the token).
 #include "kernels.h"
+#include "star_route.h"
 
 namespace gnnlm {
 namespace {
-
-constexpr int HB = 8;
-
-// lane 8 h ends up with the sum of v[h] over the wave (same butterfly as attn.hip)
-__device__ __forceinline__ float reduce8(const float (&v)[HB], int lane) {
-    const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8;
-    float w[4], y[2];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const float send = b5 ? v[t] : v[t + 4];
-        const float keep = b5 ? v[t + 4] : v[t];
-        w[t] = keep + __shfl_xor(send, 32, 64);
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const float send = b4 ? w[t] : w[t + 2];
-        const float keep = b4 ? w[t + 2] : w[t];
-        y[t] = keep + __shfl_xor(send, 16, 64);
-    }
-    float r;
-    {
-        const float send = b3 ? y[0] : y[1];
-        const float keep = b3 ? y[1] : y[0];
-        r = keep + __shfl_xor(send, 8, 64);
-    }
-    r += __shfl_xor(r, 4, 64);
-    r += __shfl_xor(r, 2, 64);
-    r += __shfl_xor(r, 1, 64);
-    return r;
-}
 
 // a wave-uniform value the compiler cannot see as one (read from LDS at a uniform address): into SGPRs
 __device__ __forceinline__ int64_t uniform64(int64_t v) {
@@ -184,24 +155,12 @@ __global__ __launch_bounds__(256, 2) void star_dense_kernel(StarAttnParams p) {
 
 }  // namespace
 
-static size_t star_dense_lds_bytes(const StarAttnParams& p) {
-    return (size_t)(HB * p.D + 4 * HB * 2) * sizeof(float) + (size_t)p.kg * sizeof(int64_t);
-}
-
-// (the LDS bound is part of eligibility: a shape with a very large k_g keeps the generic two-pass kernel instead of failing here)
-bool star_attn_dense_eligible(const StarAttnParams& p) {
-    static const bool off = getenv("GNNLM_STAR_GENERIC") != nullptr;      // A/B runs: the two-pass kernel of attn.hip
-    return !off && p.X && !p.codes && !p.shards && p.H <= HB && (p.D == 256 || p.D == 512 || p.D == 1024) && p.ldx % 4 == 0 &&
-           (uintptr_t)p.X % 16 == 0 && (uintptr_t)p.U % 16 == 0 && (uintptr_t)p.Z % 16 == 0 && p.kg >= 0 && star_dense_lds_bytes(p) <= 64 * 1024;
-}
-
-int star_attn_dense(const StarAttnParams& p, hipStream_t stream) {
-    GNNLM_REQUIRE(star_attn_dense_eligible(p), "star_attn_dense: shape not supported");
-    const size_t lds = star_dense_lds_bytes(p);
-    dim3 grid(p.T), block(256);
-    if (p.D == 1024) hipLaunchKernelGGL(star_dense_kernel<4>, grid, block, lds, stream, p);
-    else if (p.D == 512) hipLaunchKernelGGL(star_dense_kernel<2>, grid, block, lds, stream, p);
-    else hipLaunchKernelGGL(star_dense_kernel<1>, grid, block, lds, stream, p);
+// plan: a dense route of star_route() for p
+int star_attn_dense(const StarAttnParams& p, const StarPlan& plan, hipStream_t stream) {
+    const dim3 grid(p.T), block(plan.threads);
+    if (plan.route == StarRoute::DENSE4) hipLaunchKernelGGL(star_dense_kernel<4>, grid, block, plan.lds_bytes, stream, p);
+    else if (plan.route == StarRoute::DENSE2) hipLaunchKernelGGL(star_dense_kernel<2>, grid, block, plan.lds_bytes, stream, p);
+    else hipLaunchKernelGGL(star_dense_kernel<1>, grid, block, plan.lds_bytes, stream, p);
     GNNLM_LAUNCH_CHECK();
     return OK;
 }

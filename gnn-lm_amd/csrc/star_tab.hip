@@ -2,7 +2,7 @@
 // (('ntgt','inter','tgt') edges of layer 1: fn.v_dot_u + edge_softmax + u_mul_e/sum, fairseq/models/hgt.py:354-356,383-385,
 //  fused with quant_neighbor_feats[offset] and the look-up half of TorchPQCodec.decode, knn/pq_wrapper.py:189-196).
 //
-// Why this formulation.  Round 1's swept kernel (attn.hip) decoded every (neighbour, sub-quantizer) pair with a
+// Why this formulation.  Round 1's swept kernel (retired; its measurements are in HISTORY.md) decoded every (neighbour, sub-quantizer) pair with a
 // 16/32-B gather from the L1: 2 x 16,384 line look-ups per token at ~0.37 lines per clock per CU = 1.1 ms per 8192
 // tokens, while HBM (one 128-B code row per neighbour), the matrix pipe (40 %) and the LDS (8 %) idled.  An LDS
 // serves the same random 32-B row ~7x faster than the L1's tag pipeline, so here the TABLE goes to LDS instead of
@@ -28,6 +28,7 @@
 // 962 us (round 2 start, 16x16x4 ping-pong) -> 685 us; MFMA time alone is ~300 us at the ~1.9 GHz the part holds here.
 // HBM traffic is unchanged: the code rows (read once per token, staged in LDS), U and Z.
 #include "kernels.h"
+#include "star_route.h"
 
 namespace gnnlm {
 
@@ -50,27 +51,8 @@ namespace {
 #define GNNLM_STAB_CLK 0     // 1: cycle stamps of waves 0 and 4 of the first 256 workgroups written over has_nb (tools/star_clk.py)
 #endif
 
-constexpr int TPW = 4;                  // tokens per workgroup
-constexpr int KGM = 128;                // neighbours per token (padded)
-constexpr int HB = 8;                   // heads per launch
-constexpr int CD = 32;                  // feature dims per chunk
-constexpr int TABF = CD * 256;          // floats per table chunk (32 KiB)
-constexpr int SCS = KGM + 4;            // score row stride: the heads of a token land on different banks
-constexpr int NTHREADS = 768;           // 8 compute waves (two per token) + 4 loader waves (table and U in, Z out)
-
-struct Carve {
-    int tab, sc, ubuf, okf, lcodes, total;      // byte offsets
-};
-__host__ __device__ inline Carve carve(int M) {
-    Carve c;
-    c.tab = 0;
-    c.sc = c.tab + 2 * TABF * 4;
-    c.ubuf = c.sc + TPW * HB * SCS * 4;
-    c.okf = c.ubuf + 2 * TPW * 1024;
-    c.lcodes = c.okf + TPW * KGM;
-    c.total = c.lcodes + TPW * KGM * M;
-    return c;
-}
+// TPW, KGM, HB, CD, TABF, SCS and the LDS layout carve(M): star_route.h
+constexpr int NTHREADS = STAR_TAB_THREADS;      // 8 compute waves (two per token) + 4 loader waves (table and U in, Z out)
 
 // MT: the number of sub-quantizers when known at compile time (piece counts and loop bounds of the staging fold), else 0
 template <int DSUB, int MT>
@@ -539,24 +521,17 @@ __global__ __launch_bounds__(NTHREADS) void star_attn_tab_kernel(StarAttnParams 
 
 }  // namespace
 
-bool star_attn_tab_eligible(const StarAttnParams& p) {
-    return (p.codes || p.shards) && p.centroids && p.kg <= KGM && (p.dsub == 4 || p.dsub == 8) && p.M % 16 == 0 && p.D % CD == 0 &&
-           p.M * p.dsub == p.D && (uintptr_t)p.codes % 16 == 0 && (uintptr_t)p.centroids % 16 == 0 && !(p.shards && p.codes_direct) &&
-           (uintptr_t)p.U % 16 == 0 && carve(p.M).total <= 160 * 1024;
-}
-
-int star_attn_tab(const StarAttnParams& p, hipStream_t stream) {
-    GNNLM_REQUIRE(star_attn_tab_eligible(p), "star_attn_tab: shape not supported by the table-resident kernel");
-    const int lds_bytes = carve(p.M).total;
+// plan: a tab route of star_route() for p
+int star_attn_tab(const StarAttnParams& p, const StarPlan& plan, hipStream_t stream) {
     const auto k8m = &star_attn_tab_kernel<8, 128>, k8 = &star_attn_tab_kernel<8, 0>, k4 = &star_attn_tab_kernel<4, 0>;
-    GNNLM_LDS_OPT_IN(k8m, 160 * 1024);
-    GNNLM_LDS_OPT_IN(k8, 160 * 1024);
-    GNNLM_LDS_OPT_IN(k4, 160 * 1024);
-    const dim3 grid((unsigned)cdiv(p.T, TPW)), block(NTHREADS);
-    for (int h0 = 0; h0 < p.H; h0 += HB) {
-        if (p.dsub == 8 && p.M == 128) hipLaunchKernelGGL(k8m, grid, block, lds_bytes, stream, p, h0);
-        else if (p.dsub == 8) hipLaunchKernelGGL(k8, grid, block, lds_bytes, stream, p, h0);
-        else hipLaunchKernelGGL(k4, grid, block, lds_bytes, stream, p, h0);
+    GNNLM_LDS_OPT_IN(k8m, STAR_LDS_MAX);
+    GNNLM_LDS_OPT_IN(k8, STAR_LDS_MAX);
+    GNNLM_LDS_OPT_IN(k4, STAR_LDS_MAX);
+    const dim3 grid((unsigned)cdiv(p.T, TPW)), block(plan.threads);
+    for (int h0 = 0; h0 < p.H; h0 += plan.heads_per_pass) {
+        if (plan.route == StarRoute::TAB8M) hipLaunchKernelGGL(k8m, grid, block, plan.lds_bytes, stream, p, h0);
+        else if (plan.route == StarRoute::TAB8) hipLaunchKernelGGL(k8, grid, block, plan.lds_bytes, stream, p, h0);
+        else hipLaunchKernelGGL(k4, grid, block, plan.lds_bytes, stream, p, h0);
     }
     GNNLM_LAUNCH_CHECK();
     return OK;

@@ -11,7 +11,7 @@ Before the first forward the weights are *prepared* once (float64 on the host, r
   * relation matrices and ``relation_pri / sqrt(d_k)`` are folded into the K / V projections
     (``k' = (h W_k^T + b_k) R``  ==  ``h (W_k^T R) + b_k R``; hgt.py:347-348,355);
   * on the star edges the neighbour-side K / V projections (and, in layer 0, the OPQ rotation of
-    ``TorchPQCodec.decode``, pq_wrapper.py:198-202) are absorbed into the query side, see csrc/attn.hip;
+    ``TorchPQCodec.decode``, pq_wrapper.py:198-202) are absorbed into the query side, see csrc/star_attn.hip;
 all exact algebra -- only the floating-point association changes.
 """
 import ctypes

@@ -203,6 +203,8 @@ int gnnlm_neighbor_labels(const int64_t* ids, int64_t n, int64_t n_store, const 
  * x_j is decoded on the fly from PQ codes (codes != NULL) or read from dense rows (X != NULL).
  * Replaces: apply_edges(v_dot_u) + edge_softmax + u_mul_e/sum on the star edges
  *           (fairseq/models/hgt.py:354-356,383-385) fused with the gather/decode above.
+ * D % 4 == 0, D <= 1024; U, Z, X (with ldx % 4 == 0), centroids, and codes when M % 16 == 0, are 16-byte aligned: other
+ * operands are refused (GNNLM_E_INVALID).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct gnnlm_star_attn {
     const float* U;            /* [T, H, D] */

@@ -120,6 +120,7 @@ STAR_PQ_SHAPES = [
     ("generic<1>,staged",   dict(T=4, H=8, M=8, dsub=16, kg=21)),       # M % 16 != 0: byte-wise staging
     ("generic<2>,staged",   dict(T=3, H=5, M=32, dsub=16, kg=19)),
     ("generic<4>,staged",   dict(T=3, H=8, M=64, dsub=16, kg=40)),
+    ("generic<4>,staged",   dict(T=3, H=8, M=144, dsub=4, kg=40)),      # a tab shape but for its LDS: 91136 + 512 M > 160 KiB
     ("generic<4>,unstaged", dict(T=2, H=8, M=64, dsub=16, kg=330)),     # base + code LDS = 44656 + 21120 > 65536
 ]
 STAR_DENSE_SHAPES = [
@@ -140,15 +141,15 @@ def star_case_id(case):
 
 
 def star_route(T, H, kg, M=0, dsub=0, D=0, **_):
-    """The kernel star_attn (attn.hip) takes for a shape, from its eligibility functions (star_attn_tab_eligible,
-    star_attn_dense_eligible, the LDS formula and the QPL choice of star_attn), for 16-byte aligned buffers and ldx % 4 == 0, with
-    none of the A/B switches set."""
+    """The kernel star_attn (star_attn.hip) takes for a shape: star_route() of csrc/star_route.h restated (the tab and dense
+    conditions, the LDS formulas and the QPL choice), for 16-byte aligned buffers and ldx % 4 == 0 -- star_attn refuses others --
+    with the A/B switch unset.  tests/test_star_chain_ref_cpu.py compares it with star_route() itself."""
     pq = M > 0
     D = M * dsub if pq else D
     if pq and kg <= 128 and dsub in (4, 8) and M % 16 == 0 and D % 32 == 0 and \
             2 * 32 * 256 * 4 + 4 * 8 * 132 * 4 + 2 * 4 * 1024 + 4 * 128 + 4 * 128 * M <= 160 * 1024:
         return "tab<8,128>" if (dsub, M) == (8, 128) else f"tab<{dsub},0>"
-    if not pq and H <= 8 and D in (256, 512, 1024) and (8 * D + 32) * 4 + kg * 8 <= 64 * 1024:
+    if not pq and H <= 8 and D in (256, 512, 1024) and (8 * D + 4 * 8 * 2) * 4 + kg * 8 <= 64 * 1024:
         return f"dense<{D // 256}>"
     qpl = 1 if D // 4 <= 64 else 2 if D // 4 <= 128 else 4
     if not pq:

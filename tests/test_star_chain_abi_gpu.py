@@ -75,9 +75,9 @@ class Star:
             a.nb_valid, a.nb_valid_stride = self.up(kw["nb_valid"]), kw["nb_valid_stride"]
         if kw.get("x_index") is not None:
             a.x_index = self.up(kw["x_index"])
-        # what the routes of star_chain_ref.star_route take for granted: aligned operands, none of the A/B switches
+        # what the routes of star_chain_ref.star_route take for granted: aligned operands, the A/B switch unset
         assert all((getattr(a, f) or 0) % 16 == 0 for f in ("U", "codes", "centroids", "X"))
-        assert not any(os.environ.get(v) for v in ("GNNLM_STAR_SWEEP", "GNNLM_STAR_GENERIC"))
+        assert "GNNLM_STAR_GENERIC" not in os.environ
 
     def up(self, x):
         t = torch.from_numpy(np.ascontiguousarray(x)).to(self.dev)
@@ -152,6 +152,10 @@ def test_star_attn_refusals(dev):
     refused(Star(dev, pq(16, 4, D=128)))                                      # M * dsub != D
     refused(Star(dev, dense(1028, 1028)))                                     # D > 1024
     refused(Star(dev, dense(64, 66)))                                         # ldx % 4 != 0
+    for make, field in ((lambda: pq(16, 4), "U"), (lambda: pq(16, 4), "centroids"), (lambda: pq(16, 4), "codes"), (lambda: dense(64, 68), "U")):
+        st = Star(dev, make())                                                # one float off a 16-byte boundary: no kernel loads that
+        setattr(st.a, field, getattr(st.a, field) + 4)
+        refused(st)
 
 
 # ======================================================================================================== chain attention

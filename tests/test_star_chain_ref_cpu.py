@@ -7,7 +7,13 @@ that ignores a descriptor field from one that honours it.  No GPU.
    one by more than 100 x the GPU bar somewhere in Z / out, or in has_nb / the write mask.
 3. Per star case: 30 % .. 90 % of the neighbours valid, a token without any, and for every validity rule in force a neighbour that this
    rule alone excludes.  (A case of one token cannot have a token without neighbours next to one with: T = 1 is exempt from that
-   one condition, the T = 6 case of the same route and option carries it.)"""
+   one condition, the T = 6 case of the same route and option carries it.)
+4. star_chain_ref.star_route is the dispatcher: it is compared with star_route() of csrc/star_route.h itself
+   (tests/star_route_main.cpp, built with the host compiler)."""
+import os
+import shutil
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -145,6 +151,91 @@ def test_star_tables_cover_every_route_and_option():
                                                   "generic<4>,staged", "generic<4>,unstaged"}
     assert {r for r, _ in ref.STAR_DENSE_SHAPES} == {"dense<1>", "dense<2>", "dense<4>", "generic<1>,dense", "generic<4>,dense"}
     assert len({ref.star_case_id(c) for c in ref.STAR_CASES}) == len(ref.STAR_CASES)
+
+
+# ------------------------------------------------------------------------------------------ 4. the dispatcher itself
+ROUTE_NAMES = {"tab<8,128>", "tab<8,0>", "tab<4,0>", "dense<1>", "dense<2>", "dense<4>"} | \
+              {f"generic<{n}>,{how}" for n in (1, 2, 4) for how in ("staged", "unstaged", "dense")}
+PQ_GRID = [dict(T=4, H=8, M=M, dsub=dsub, kg=kg) for M in [8] + list(range(16, 257, 16)) for dsub in (4, 8, 16) if M * dsub <= 1024
+           for kg in (1, 128, 129, 330, 1024)]
+DENSE_GRID = [dict(T=4, H=H, D=D, kg=kg) for D in (64, 256, 512, 768, 1024) for H in (1, 8, 9, 12) for kg in (1, 128, 1024, 4000)]
+# the literals of ref.star_route, by the names csrc/star_route.h gives them
+STAR_CONSTANTS = dict(HB=8, KGM=128, CD=32, TPW=4, TABF=32 * 256, SCS=132, STAR_THREADS=256, STAR_TAB_THREADS=768,
+                      STAR_LDS_MAX=160 * 1024, STAR_LDS_TWO_WG=64 * 1024)
+
+
+@pytest.fixture(scope="module")
+def star_route_program(tmp_path_factory):
+    """tests/star_route_main.cpp: csrc/star_route.h behind a command line, built with the host compiler alone"""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not found")
+    exe = str(tmp_path_factory.mktemp("star_route") / "star_route_main")
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", os.path.join(os.path.dirname(os.path.abspath(__file__)), "star_route_main.cpp"),
+                        "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return exe
+
+
+def ask(exe, *args, stdin="", env=None):
+    e = {k: v for k, v in os.environ.items() if not k.startswith("GNNLM_STAR_")}
+    e.update(env or {})
+    r = subprocess.run([exe, *args], input=stdin, capture_output=True, text=True, env=e)
+    assert r.returncode == 0, r.stderr
+    return r.stdout.split("\n")[:-1]
+
+
+def real_routes(exe, shapes, env=None):
+    """[(route of star_route() spelt as ref.star_route spells it, dynamic LDS bytes, threads)] for the shapes"""
+    lines = [" ".join(str(s.get(k, 0)) for k in ("T", "H", "kg", "M", "dsub")) + f" {s['M'] * s['dsub'] if 'M' in s else s['D']}" for s in shapes]
+    out = [l.split() for l in ask(exe, "route", stdin="\n".join(lines) + "\n", env=env)]
+    assert len(out) == len(shapes)
+    res = []
+    for s, (name, staged, lds, threads, heads) in zip(shapes, out):
+        assert int(heads) == 8 and (name.startswith("generic") or staged == "0")
+        if name.startswith("generic"):
+            name += ",dense" if "M" not in s else ",staged" if staged == "1" else ",unstaged"
+        res.append((name, int(lds), int(threads)))
+    return res
+
+
+def lds_bytes(route, T, H, kg, M=0, dsub=0, D=0):
+    """the dynamic LDS of the route's launch, by the formulas of ref.star_route"""
+    D = M * dsub if M else D
+    if route.startswith("tab"):
+        return 2 * 32 * 256 * 4 + 4 * 8 * 132 * 4 + 2 * 4 * 1024 + 4 * 128 + 4 * 128 * M
+    if route.startswith("dense"):
+        return (8 * D + 4 * 8 * 2) * 4 + kg * 8
+    return (8 * kg + 8 * D + ((kg + 3) & ~3)) * 4 + (((kg * M + 15) & ~15) if route.endswith(",staged") else 0)
+
+
+def test_star_route_is_the_dispatcher(star_route_program):
+    """ref.star_route against star_route() of csrc/star_route.h itself: on every shape of the case tables and over a grid that
+    reaches every route; the LDS bytes and the workgroup size of the plan; the A/B switch; the header's constants by value."""
+    got = dict(l.split() for l in ask(star_route_program, "constants"))
+    assert {k: int(v) for k, v in got.items()} == STAR_CONSTANTS
+    listed = ref.STAR_PQ_SHAPES + ref.STAR_DENSE_SHAPES
+    for (want, shape), (rt, _, _) in zip(listed, real_routes(star_route_program, [s for _, s in listed])):
+        assert rt == want, (shape, rt)                                 # (the labels, asked of the code too)
+    # one step to either side of the two LDS bounds that choose a kernel, written by hand: the dense kernel's 64 KiB
+    # ((8 * 1024 + 64) * 4 + 8 kg: k_g = 4064) and the staging of the generic one (41792 + 23680 = 65472, 41840 + 23728 = 65568)
+    edges = [(dict(T=4, H=8, D=1024, kg=4064), "dense<4>"), (dict(T=4, H=8, D=1024, kg=4065), "generic<4>,dense"),
+             (dict(T=4, H=8, M=40, dsub=16, kg=592), "generic<4>,staged"), (dict(T=4, H=8, M=40, dsub=16, kg=593), "generic<4>,unstaged")]
+    for (s, want), (rt, _, _) in zip(edges, real_routes(star_route_program, [s for s, _ in edges])):
+        assert rt == want, (s, rt)
+    shapes = [s for _, s in listed] + [s for s, _ in edges] + PQ_GRID + DENSE_GRID
+    real = real_routes(star_route_program, shapes)
+    for s, (rt, lds, threads) in zip(shapes, real):
+        assert rt == ref.star_route(**s), (s, rt)
+        assert lds == lds_bytes(rt, **s), (s, rt, lds)
+        assert threads == (768 if rt.startswith("tab") else 256), (s, rt)
+    assert {rt for rt, _, _ in real[len(listed) + len(edges):]} == ROUTE_NAMES                 # the grid alone reaches every route
+    # GNNLM_STAR_GENERIC: neither tab nor dense, and the generic kernel as it would be chosen without them
+    off = real_routes(star_route_program, shapes, env={"GNNLM_STAR_GENERIC": "1"})
+    for s, (rt, lds, threads), (rt0, _, _) in zip(shapes, off, real):
+        assert rt.startswith("generic") and threads == 256 and lds == lds_bytes(rt, **s), (s, rt)
+        assert rt == rt0 or not rt0.startswith("generic"), (s, rt, rt0)
+    # T = 0: nothing to launch
+    assert real_routes(star_route_program, [dict(T=0, H=8, M=128, dsub=8, kg=128), dict(T=0, H=8, D=256, kg=9)]) == [("none", 0, 0)] * 2
 
 
 @pytest.mark.parametrize("case", ref.STAR_CASES, ids=ref.star_case_id)

@@ -1,4 +1,4 @@
-"""The dense-source launches of the star attention (layers >= 1 of a multi-layer model: `star_attn_kernel<4>`, csrc/attn.hip) on their own:
+"""The dense-source launches of the star attention (layers >= 1 of a multi-layer model: `star_attn_kernel<4>`, csrc/star_attn.hip) on their own:
 4096 tokens x 128 neighbour rows of 4 KiB gathered through an index (the cross-batch cache's slots), checked against torch.
 
 Round 4 A/B with this tool: the kernel's lane-to-row mapping (lane l owns 64 CONTIGUOUS bytes of a row, four 16-B loads) against an interleaved one
