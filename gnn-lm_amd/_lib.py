@@ -162,7 +162,7 @@ def lib():
         for nm in ("gnnlm_gemm_nt", "gnnlm_pq_gather_decode", "gnnlm_token_gather", "gnnlm_star_attn", "gnnlm_chain_attn",
                    "gnnlm_knn_interp", "gnnlm_knn_interp_grid", "gnnlm_knn_mix_dense", "gnnlm_knn_recompute_sims", "gnnlm_topk_merge", "gnnlm_ivfpq_scan", "gnnlm_gather_rows_peer",
                    "gnnlm_ivfpq_scan8", "gnnlm_ivfpq_rescore", "gnnlm_ivfpq_tau", "gnnlm_group_assign",
-                   "gnnlm_ivfpq_tables", "gnnlm_pack_rows", "gnnlm_decode_attn", "gnnlm_sample_topk", "gnnlm_beam_attn",
+                   "gnnlm_ivfpq_tables", "gnnlm_pack_rows", "gnnlm_decode_attn", "gnnlm_sample_topk", "gnnlm_sample_topp", "gnnlm_beam_attn",
                    "gnnlm_beam_select", "gnnlm_beam_select_diverse", "gnnlm_ivfpq_select_probes", "gnnlm_ivfpq_select_final"):
             getattr(L, nm).argtypes = [vp, vp]
         if L.gnnlm_target_arch() != b"gfx950" or L.gnnlm_abi_version() != ABI_VERSION:

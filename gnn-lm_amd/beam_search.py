@@ -221,6 +221,8 @@ def check_args(args):
     """Host only, before any device work: what this build does not compute is refused with the flag's name."""
     if args.sampling or args.sampling_topk > 0:
         raise ValueError("--sampling: beam search does not sample (python -m gnnlm_amd.generate does, at beam 1)")
+    if not args.sampling_topp <= 0:                          # (a NaN too)
+        raise ValueError("--sampling-topp: beam search does not sample (python -m gnnlm_amd.generate does, at beam 1)")
     gen_common.check_unbuilt(args)
     if args.beam > MAX_BEAM or args.beam < 1:
         raise ValueError(f"--beam {args.beam}: between 1 and {MAX_BEAM}")

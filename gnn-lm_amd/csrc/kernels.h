@@ -143,6 +143,7 @@ int kv_len_set(const gnnlm_kv_cache_t& c, const int32_t* block_off, int max_rows
 int kv_len_advance(const gnnlm_kv_cache_t& c, int bound, hipStream_t stream);
 // the next token of every row from its sorted top-N (sample.hip)
 int sample_topk(const gnnlm_sample_topk_t& d, hipStream_t stream);
+int sample_topp(const gnnlm_sample_topp_t& d, hipStream_t stream);
 // host: the (block, query tile) table of block_off [n_blocks + 1], heaviest tiles first; tiles == nullptr only counts.  -1: an empty block
 int64_t ragged_tiles(const int32_t* block_off, int n_blocks, int32_t* tiles);
 

@@ -151,7 +151,7 @@ size_t gnnlm_sizeof(const char* name) {
     GNNLM_SZ(gnnlm_adaptive_softmax_t) GNNLM_SZ(gnnlm_dense_softmax_t) GNNLM_SZ(gnnlm_knn_interp_t) GNNLM_SZ(gnnlm_knn_interp_grid_t) GNNLM_SZ(gnnlm_knn_mix_dense_t) GNNLM_SZ(gnnlm_knn_resim_t) GNNLM_SZ(gnnlm_hgt_layer_t)
     GNNLM_SZ(gnnlm_hgt_t) GNNLM_SZ(gnnlm_hgt_io_t) GNNLM_SZ(gnnlm_profile_entry_t) GNNLM_SZ(gnnlm_topk_t) GNNLM_SZ(gnnlm_ivfpq_scan_t) GNNLM_SZ(gnnlm_ivfpq_scan8_t) GNNLM_SZ(gnnlm_ivfpq_rescore_t) GNNLM_SZ(gnnlm_ivfpq_tau_t) GNNLM_SZ(gnnlm_ivfpq_tables_t) GNNLM_SZ(gnnlm_peer_gather_t) GNNLM_SZ(gnnlm_shards_t) GNNLM_SZ(gnnlm_ragged_t)
     GNNLM_SZ(gnnlm_lm_embed_t) GNNLM_SZ(gnnlm_tlm_layer_t) GNNLM_SZ(gnnlm_tlm_t) GNNLM_SZ(gnnlm_tlm_io_t) GNNLM_SZ(gnnlm_pack_rows_t)
-    GNNLM_SZ(gnnlm_kv_cache_t) GNNLM_SZ(gnnlm_decode_attn_t) GNNLM_SZ(gnnlm_tlm_step_io_t) GNNLM_SZ(gnnlm_sample_topk_t)
+    GNNLM_SZ(gnnlm_kv_cache_t) GNNLM_SZ(gnnlm_decode_attn_t) GNNLM_SZ(gnnlm_tlm_step_io_t) GNNLM_SZ(gnnlm_sample_topk_t) GNNLM_SZ(gnnlm_sample_topp_t)
     GNNLM_SZ(gnnlm_beam_attn_t) GNNLM_SZ(gnnlm_beam_select_t) GNNLM_SZ(gnnlm_beam_select_diverse_t) GNNLM_SZ(gnnlm_ivfpq_select_probes_t) GNNLM_SZ(gnnlm_ivfpq_select_final_t)
 #undef GNNLM_SZ
     return 0;

@@ -26,9 +26,12 @@ def add_common_args(p, beam, max_len_help, out_help):
     p.add_argument("--beam", type=int, default=beam, help="beam_search: 1 .. 32; generate decodes at 1 and refuses anything else")
     p.add_argument("--min-len", type=int, default=1, help="beam_search: eos is forbidden while the hypothesis (the scored prompt included) "
                                                           "is shorter; generate refuses anything but 1")
-    p.add_argument("--sampling", action="store_true", help="generate: sample from the top --sampling-topk; beam_search refuses it")
-    p.add_argument("--sampling-topk", type=int, default=-1)
-    p.add_argument("--sampling-topp", type=float, default=-1.0, help="not built: refused")
+    p.add_argument("--sampling", action="store_true", help="generate: sample, from the top --sampling-topk or from the nucleus of "
+                                                           "--sampling-topp (one of the two); beam_search refuses it")
+    p.add_argument("--sampling-topk", type=int, default=-1, help="generate: sample from the K most likely tokens, K <= 2048")
+    p.add_argument("--sampling-topp", type=float, default=-1.0,
+                   help="generate: sample from the smallest set of tokens whose probabilities sum to P or more (fairseq/search.py:174-217; the "
+                        "sum is not renormalised); P >= 1 samples from (essentially) the whole vocabulary, P <= 0 is off; beam_search refuses it")
     p.add_argument("--temperature", type=float, default=1.0,
                    help="the GENERATION temperature (fairseq/options.py:548): the decoder output is divided by it.  The kNN temperature, "
                         "which eval_lm calls --temperature (options.py:496), is --knn-temperature here")
@@ -54,8 +57,6 @@ def add_common_args(p, beam, max_len_help, out_help):
 
 def check_unbuilt(args):
     """The flags neither driver computes, and more than one process."""
-    if args.sampling_topp > 0:
-        raise ValueError("--sampling-topp is not built")
     if args.no_repeat_ngram_size:
         raise ValueError("--no-repeat-ngram-size is not built")
     if args.graph:

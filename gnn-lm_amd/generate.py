@@ -1,10 +1,10 @@
-"""Generate from the base transformer LM: K/V-cache decoding, greedy or top-k sampling, optionally mixed with kNN.
+"""Generate from the base transformer LM: K/V-cache decoding, greedy, top-k or nucleus (top-p) sampling, optionally mixed with kNN.
 
     python -m gnnlm_amd.generate DATA --path base.pt --gen-subset test --n-prompts 8 --prompt-len 32 --max-len-b 64 \\
-        [--sampling --sampling-topk 10] [--temperature 0.8] [--unkpen X] [--seed 1] [--fp16] \\
+        [--sampling --sampling-topk 10 | --sampling --sampling-topp 0.9] [--temperature 0.8] [--unkpen X] [--seed 1] [--fp16] \\
         [--knnlm --k 1024 --lmbda 0.25 --knn-temperature 1 --probe 32 --dstore-dir D --index-file F --knn-sim-func do_not_recomp_ip]
 
-Mirror of ``SequenceGenerator`` (fairseq/sequence_generator.py) with ``search.Sampling`` (fairseq/search.py:199-270) at beam 1 for
+Mirror of ``SequenceGenerator`` (fairseq/sequence_generator.py) with ``search.Sampling`` (fairseq/search.py:167-288) at beam 1 for
 one decoder-only model.  The loop:
 
   prefill   ``TransformerLM.prefill`` over the packed prompts fills the K/V cache; the last row of every prompt goes on.
@@ -14,13 +14,17 @@ one decoder-only model.  The loop:
             ``ops.knn_mix_dense`` exactly as ``predict.predict_rows`` feeds it.
   rules     ``lprobs[:, pad] = -inf`` and ``lprobs[:, unk] -= unk_penalty`` (sequence_generator.py:279-280).
   pick      ``ops.topk_merge`` with k = ``sampling_topk`` (1 when greedy), then ``ops.sample_topk`` with one uniform number per row from
-            a seeded device generator.
+            a seeded device generator.  With ``--sampling-topp P``: one ``ops.sample_topp`` on the dense rows instead -- the nucleus
+            of ``search.Sampling._sample_topp`` (search.py:174-217: the shortest prefix of the sorted row whose probabilities, not
+            renormalised, sum to P or more), found without a sort, and one draw from it; no top-k buffers.  P >= 1 samples from
+            (essentially) the whole vocabulary: every token with a finite log-probability.
   step      ``TransformerLM.step`` appends the picks; back to head.
 
 Without kNN the loop reads nothing back per token: ``done`` is looked at every 16 steps and at the end.
 
-Refused by name, never approximated: ``--beam`` > 1, ``--sampling-topp``, ``--sampling`` without ``--sampling-topk`` (pure sampling over the
-vocabulary), ``--sampling-topk`` > 2048, ``--no-repeat-ngram-size``, ``--min-len`` != 1, ``--graph``, ``--sweep-*``, more than one process.
+Refused by name, never approximated: ``--beam`` > 1, ``--sampling`` without ``--sampling-topk`` or ``--sampling-topp``, both of them at
+once (the reference lets top-p win silently), ``--sampling-topp`` without ``--sampling`` (fairseq_task.py:243) or NaN,
+``--sampling-topk`` > 2048, ``--no-repeat-ngram-size``, ``--min-len`` != 1, ``--graph``, ``--sweep-*``, more than one process.
 """
 import argparse
 import logging
@@ -78,10 +82,19 @@ class Generator:
         return lp
 
     @staticmethod
-    def check(max_new, sampling, sampling_topk, temperature, V):
+    def check(max_new, sampling, sampling_topk, temperature, V, sampling_topp=-1.0):
+        """-> the k of the top-k pick (1 when greedy; unused under top-p).  ``sampling_topp`` <= 0 is off (search.py:228)."""
         gen_common.check_decode(max_new, temperature)
+        if sampling_topp != sampling_topp:
+            raise ValueError("--sampling-topp must be a number (NaN given)")
+        if sampling_topp > 0:
+            if not sampling:
+                raise ValueError("--sampling-topp requires --sampling")
+            if sampling_topk > 0:
+                raise ValueError("--sampling-topp with --sampling-topk: give one of the two")
+            return 1
         if sampling and sampling_topk < 1:
-            raise ValueError("--sampling without --sampling-topk (pure sampling over the vocabulary) is not built")
+            raise ValueError("--sampling needs --sampling-topk K or --sampling-topp P")
         if sampling and sampling_topk > MAX_TOPK:
             raise ValueError(f"--sampling-topk {sampling_topk}: at most {MAX_TOPK} (gnnlm_topk_merge's k)")
         return min(sampling_topk, V) if sampling else 1
@@ -100,19 +113,21 @@ class Generator:
             cache.spread(into)
         return cache, tokens, lens, x, extra, last, want_ffn
 
-    def generate(self, prompts, max_new, sampling=False, sampling_topk=-1, temperature=1.0, unk_penalty=0.0, seed=None):
+    def generate(self, prompts, max_new, sampling=False, sampling_topk=-1, temperature=1.0, unk_penalty=0.0, seed=None, sampling_topp=-1.0):
         """prompts: a list of non-empty lists of token ids, fed as they are -> ``(tokens int64 [B, max_new], logp f32 [B, max_new],
         lengths int64 [B])`` on the device: row b's continuation is ``tokens[b, :lengths[b]]`` (its ``eos`` included when it came), ``pad``
-        behind it; ``logp`` the picks' own log-probabilities."""
+        behind it; ``logp`` the picks' own log-probabilities.  ``sampling_topp`` > 0 (with ``sampling``): nucleus sampling; the mean
+        nucleus size over the picks made is left in ``self.mean_nucleus``."""
         lm, dev = self.lm, self.lm.device
-        k = self.check(max_new, sampling, sampling_topk, float(temperature), self.vocab)
+        k = self.check(max_new, sampling, sampling_topk, float(temperature), self.vocab, float(sampling_topp))
+        topp = float(sampling_topp) if sampling and sampling_topp > 0 else 0.0
         cache, _, _, x, extra, last, want_ffn = self.prefill(prompts, max_new - 1)
         x, extra = gen_common.last_rows(x, extra, last)
         B = len(prompts)
         out = torch.full((B, max_new), PAD, dtype=torch.int64, device=dev)
         out_lp = torch.zeros(B, max_new, dtype=torch.float32, device=dev)
-        best_val = torch.empty(B, k, dtype=torch.float32, device=dev)
-        best_id = torch.empty(B, k, dtype=torch.int64, device=dev)
+        best_val = None if topp else torch.empty(B, k, dtype=torch.float32, device=dev)
+        best_id = None if topp else torch.empty(B, k, dtype=torch.int64, device=dev)
         nxt = torch.empty(B, dtype=torch.int64, device=dev)
         nxt_lp = torch.zeros(B, dtype=torch.float32, device=dev)
         gen = None
@@ -120,12 +135,22 @@ class Generator:
             gen = torch.Generator(device=dev)
             gen.manual_seed(int(seed) if seed is not None else 1)
         n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        if topp:
+            n_keep = torch.zeros(B, dtype=torch.int32, device=dev)      # this step's nucleus sizes (0 for a row that made no pick)
+            keep_sum = torch.zeros(2, dtype=torch.int64, device=dev)    # nucleus sizes summed, picks made
+        self.mean_nucleus = None
         for t in range(max_new):
             lp = self.next_log_probs(x, extra, float(temperature), float(unk_penalty))
-            ops.topk_merge(lp, best_val, best_id, init=True)
             u = torch.rand(B, generator=gen, device=dev, dtype=torch.float32) if sampling else None
             nxt_lp.zero_()
-            ops.sample_topk(best_val, best_id, u=u, pad=PAD, eos=EOS, done=cache.done, n_bad=n_bad, out=nxt, out_logp=nxt_lp)
+            if topp:
+                n_keep.zero_()
+                ops.sample_topp(lp, topp, u, pad=PAD, eos=EOS, done=cache.done, n_bad=n_bad, out=nxt, out_logp=nxt_lp, n_keep=n_keep)
+                keep_sum[0] += n_keep.sum()
+                keep_sum[1] += (n_keep > 0).sum()
+            else:
+                ops.topk_merge(lp, best_val, best_id, init=True)
+                ops.sample_topk(best_val, best_id, u=u, pad=PAD, eos=EOS, done=cache.done, n_bad=n_bad, out=nxt, out_logp=nxt_lp)
             out[:, t] = nxt
             out_lp[:, t] = nxt_lp
             if t == max_new - 1 or ((t + 1) % DONE_EVERY == 0 and bool(cache.done.all())):
@@ -134,6 +159,9 @@ class Generator:
         lm.check_tokens()
         if int(n_bad.item()) or int(cache.n_bad.item()):
             raise RuntimeError("generate: a row had nothing to pick from (non-finite log-probabilities) or left the cache's range")
+        if topp:
+            total, picks = (int(v) for v in keep_sum.tolist())
+            self.mean_nucleus = total / max(picks, 1)
         is_eos = out == EOS
         first = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full((B,), t + 1, device=dev))
         return out, out_lp, first.to(torch.int64)
@@ -155,7 +183,7 @@ def check_args(args):
     if args.min_len != 1:
         raise ValueError(f"--min-len {args.min_len} is not built (only --min-len 1)")
     gen_common.check_unbuilt(args)
-    Generator.check(args.max_len_b, args.sampling, args.sampling_topk, args.temperature, MAX_TOPK)
+    Generator.check(args.max_len_b, args.sampling, args.sampling_topk, args.temperature, MAX_TOPK, args.sampling_topp)
     gen_common.check_knn_and_prompts(args)
 
 
@@ -187,13 +215,17 @@ def main(args, model=None, file=None):
     torch.cuda.set_device(device)
     prompts = read_prompts(args)
     model = gen_common.load_model(args, device, model)
-    logger.info("%d prompt(s), up to %d new tokens each, %s, precision %s", len(prompts), args.max_len_b,
-                f"top-{args.sampling_topk} sampling at temperature {args.temperature}" if args.sampling else "greedy", model.precision)
+    how = "greedy" if not args.sampling else \
+        (f"top-p {args.sampling_topp} (nucleus) sampling" if args.sampling_topp > 0 else f"top-{args.sampling_topk} sampling") + \
+        f" at temperature {args.temperature}"
+    logger.info("%d prompt(s), up to %d new tokens each, %s, precision %s", len(prompts), args.max_len_b, how, model.precision)
     knn = gen_common.load_knn(args, model, device)
     g = Generator(model, knn, args.knn_keytype, k=args.k if args.knnlm else 0, lmbda=args.lmbda if args.knnlm else 0.0,
                   knn_temperature=args.knn_temperature)
     tokens, logp, lengths = g.generate(prompts, args.max_len_b, sampling=args.sampling, sampling_topk=args.sampling_topk,
-                                       temperature=args.temperature, unk_penalty=args.unkpen, seed=args.seed)
+                                       temperature=args.temperature, unk_penalty=args.unkpen, seed=args.seed, sampling_topp=args.sampling_topp)
+    if g.mean_nucleus is not None:
+        logger.info("top-p %s: mean nucleus size %.1f of %d tokens", args.sampling_topp, g.mean_nucleus, g.vocab)
     tokens, logp, lengths = tokens.cpu().numpy(), logp.cpu().numpy(), lengths.cpu().numpy()
     word = gen_common.word_of(args.data)
     for i, p in enumerate(prompts):

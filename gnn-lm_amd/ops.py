@@ -412,6 +412,40 @@ def sample_topk(logp, ids, u=None, pad=1, eos=2, done=None, n_bad=None, out=None
     return out, out_logp
 
 
+def sample_topp(logp, topp, u, pad=1, eos=2, done=None, n_bad=None, out=None, out_logp=None, want_logp=True, n_keep=None, keep_mass=None):
+    """Nucleus sampling over dense rows (``gnnlm_sample_topp``): ``logp`` f32 [B, V] (rows contiguous, any row stride), ``topp`` > 0
+    (``inf``: the whole vocabulary), ``u`` f32 [B] in [0, 1).  The nucleus is the shortest prefix of the row's order (larger value
+    first, then smaller id) whose unnormalised mass ``sum exp(logp)`` reaches ``topp`` (search.py:174-217); the pick is the smallest id
+    whose prefix sum of nucleus masses, in ascending id, exceeds ``u * S``.  -> ``(next i64 [B], next_logp f32 [B] or None)``;
+    ``done`` / ``n_bad`` as in :func:`sample_topk`; ``n_keep`` int32 [B] / ``keep_mass`` f32 [B] (optional outputs): the nucleus size and
+    mass.  No workspace, nothing read back."""
+    _dev(logp, u, done, n_bad, out, out_logp, n_keep, keep_mass)
+    _f32(logp, u, out_logp, keep_mass)
+    _dtype(out, torch.int64, "out"), _dtype(done, torch.int32, "done"), _dtype(n_bad, torch.int32, "n_bad"), _dtype(n_keep, torch.int32, "n_keep")
+    if logp.dim() != 2 or (logp.shape[1] > 1 and logp.stride(1) != 1):
+        raise ValueError("sample_topp: logp [B, V] with contiguous rows")
+    if u is None:
+        raise ValueError("sample_topp: u is required")
+    B, V = logp.shape
+    for t in (u, done, out, out_logp, n_keep, keep_mass):
+        if t is not None and (t.shape != (B,) or not t.is_contiguous()):
+            raise ValueError("sample_topp: u / done / out / out_logp / n_keep / keep_mass must be contiguous [B]")
+    if out is None:
+        out = torch.empty(B, device=logp.device, dtype=torch.int64)
+    if out_logp is None and want_logp:
+        out_logp = torch.empty(B, device=logp.device, dtype=torch.float32)
+    s = _lib.gnnlm_sample_topp_t()
+    s.logp, s.ld = logp.data_ptr(), _row_stride(logp)
+    s.B, s.V, s.topp = B, V, float(topp)
+    s.u = u.data_ptr()
+    s.pad, s.eos = int(pad), int(eos)
+    s.next = out.data_ptr()
+    for name, t in (("next_logp", out_logp), ("done", done), ("n_bad", n_bad), ("n_keep", n_keep), ("keep_mass", keep_mass)):
+        setattr(s, name, t.data_ptr() if t is not None else None)
+    call_desc("gnnlm_sample_topp", s)
+    return out, out_logp
+
+
 def _src_table(src, B, cap, what):
     _dtype(src, torch.int32, "src")
     if not src.is_cuda or src.dim() != 2 or src.shape[0] != B or src.shape[1] < cap or (src.stride(1) != 1 and src.shape[1] > 1) or \

@@ -1108,6 +1108,49 @@ typedef struct gnnlm_sample_topk {
 } gnnlm_sample_topk_t;
 int gnnlm_sample_topk(const gnnlm_sample_topk_t* desc, void* stream);
 
+/* Nucleus (top-p) sampling over DENSE rows: the next token of every row from logp [B, V] float32 as gnnlm_adaptive_log_probs /
+ * gnnlm_dense_log_probs / gnnlm_knn_mix_dense leave it -- search.Sampling._sample_topp and the draw of Sampling.step
+ * (fairseq/search.py:174-217, 228-265) with the caller's random numbers.  Additive to ABI 12: a new struct and a new entry.
+ * For a row lp[0 .. V) that is not done:
+ *   mass     m_j = exp(lp_j) for a finite lp_j, 0 for -inf.  Nothing is renormalised and no maximum is subtracted: the reference
+ *            compares cumsum(exp(lprobs)) with p in absolute terms (search.py:191-198), and a row need not sum to 1.
+ *   bad      a row with a NaN, a +inf or no positive mass (no finite entry, or none whose exp is a positive float32) is bad:
+ *            next = pad, done = 1 (if given), counted in *n_bad; next_logp, n_keep and keep_mass are left alone; the other rows
+ *            of the call are unaffected.
+ *   order    larger value first, then smaller id (gnnlm_topk_merge's and gnnlm_row_rank's rule; -0 equals +0).
+ *   nucleus  c_i the inclusive prefix sums of the masses in that order, n_pos the number of finite entries:
+ *            n = min(n_pos, 1 + #{i : c_i < topp}), the nucleus the first n entries of the order (mask = cumsum.lt(p) plus "one
+ *            more word", search.py:198-205); of the entries equal to the n-th value those with the smallest ids are in.  topp is any
+ *            value > 0, +inf included; at or above the row's mass, n = n_pos: sampling from the whole vocabulary.
+ *   draw     in ascending id: the smallest id whose inclusive prefix sum of nucleus masses exceeds u[b] * S, S the nucleus mass;
+ *            should u * S round up to S, the last member with mass.
+ * next[b] = the id; next_logp[b] (optional) = lp[id], bit for bit, not renormalised (search.py:258-265); n_keep[b] (optional) = n;
+ * keep_mass[b] (optional) = S.  done / eos / pad as in gnnlm_sample_topk: a done row gets next = pad and is otherwise untouched; a
+ * pick equal to eos sets done[b] = 1.
+ * One workgroup per row, one launch, no workspace, nothing read back: capturable.  A row's outputs are a function of its own lp, V,
+ * topp and u alone -- not of B, ld, the pointer's alignment or what else runs: every sum is an integer sum of the masses in a
+ * per-row fixed point, trunc(expf(lp_j) * 2^s) with 2^s chosen from the row's maximum so that V of them fit 63 bits.  Every sum that
+ * is compared with topp or with u * S is within a relative E(V) = 2^-21 + 2^(2 ceil(log2 V) - 62) of its exact value (the prefix
+ * sums of the draw: relative to S; 7.2e-7 at V = 2^20; csrc/sample_topp.hip derives it): where topp and u * S are further than
+ * that from every prefix sum, n, the set and the id are those of the float64 restatement (tests/topp_ref.py).
+ * Rows need 4-byte alignment only and ld >= V need not be a multiple of 4; nothing at or beyond column V is read.
+ * GNNLM_E_INVALID before anything is launched: topp not > 0 (NaN), V outside [1, 2^24] (the bound above is 6.2e-5 there), B < 0,
+ * ld < V, a NULL logp / u / next, a misaligned pointer.  B = 0 is accepted and touches nothing. */
+typedef struct gnnlm_sample_topp {
+    const float* logp;  int64_t ld;       /* [B, V], row stride ld */
+    int32_t B, V;
+    double topp;
+    const float* u;                       /* DEVICE [B], in [0, 1) */
+    int64_t pad, eos;
+    int64_t* next;                        /* [B] */
+    float* next_logp;                     /* optional [B] */
+    int32_t* done;                        /* optional [B] */
+    int32_t* n_bad;                       /* optional */
+    int32_t* n_keep;                      /* optional [B] */
+    float* keep_mass;                     /* optional [B] */
+} gnnlm_sample_topp_t;
+int gnnlm_sample_topp(const gnnlm_sample_topp_t* desc, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Beam search on the K/V cache: the decode attention through a per-hypothesis table of cache slots, the step that uses it, and
  * the selection of the next hypotheses.  Additive to ABI 12: new structs and new entries; nothing above launches anything else.

@@ -3,6 +3,7 @@
 embedding table has V = 267,744 rows) against what the build could do before it had a K/V cache.
 
     python tools/generate_bench.py [--steps 30 --warmup 5] [--batches 1,8,32] [--lengths 512,3072]
+    python tools/generate_bench.py --pick [--steps 30 --warmup 5] [--batches 1,8,32,128] [--out profiles/FILE.txt]
 
 For every (B, cached length) it reports, each named for what it is (device events, the median of --steps rounds after --warmup, the
 timed forms taking turns):
@@ -17,7 +18,17 @@ timed forms taking turns):
                 (B sequences cost B of them, or one packed batch of B samples).
 Beside the attention time: the bytes it must move, 2 * B * len * d * 4 per layer, over the achievable HBM rate (6.3 TB/s) = the least
 time, and the share of that rate reached.  Beside the step: the same with the weights (16 x (4 d^2 + 2 d ffn) x 4 bytes) added.
-Seeded synthetic weights and cache contents.  One JSON line per (B, length)."""
+Seeded synthetic weights and cache contents.  One JSON line per (B, length).
+
+``--pick`` times the per-token pick instead, on rows [B, V] at V = 267,744 with two profiles -- "peaked": the softmax of Zipf-like logits
+(-1.1 log rank, the ranks permuted per row); "flat": the softmax of unit normal logits, whose nucleus at 0.9 is tens of thousands of
+entries -- the same method, the forms taking turns:
+  * head        ``head.log_probs`` of B rows under the adaptive softmax at the WikiText-103 shape (cutoffs 20000 / 60000, d = 1024)
+  * top-k pick  the existing pick: ``gnnlm_topk_merge`` at k = 10 plus ``gnnlm_sample_topk``
+  * top-p 0.9   ``gnnlm_sample_topp`` at p = 0.9
+  * top-p inf   ``gnnlm_sample_topp`` at p = inf (the whole vocabulary: no refinement sweeps)
+and beside each top-p time the row bytes (B * V * 4) over it, next to the achievable HBM rate (6.3 TB/s) and the L2 rate (34.5 TB/s)
+of the chip.  The condition of the run: at every B the top-p pick costs no more than the head of the same rows."""
 import argparse
 import json
 import os
@@ -64,6 +75,77 @@ def build(A, dev):
                          device=dev, precision="fp16" if A.fp16 else None)
 
 
+def pick_bench(A, dev):
+    from gnnlm_amd import ops
+    from gnnlm_amd.adaptive_softmax import AdaptiveSoftmax
+    cutoff, d, V = (20000, 60000, A.vocab), A.d, A.vocab
+    g = torch.Generator(device=dev)
+    g.manual_seed(3)
+    rnd = lambda *s: torch.randn(*s, generator=g, device=dev)
+    emb, proj, prev = [], [], 0
+    for i, c in enumerate(cutoff):
+        dim = d // 4 ** i
+        emb.append(rnd(c - prev, dim) * dim ** -0.5)
+        proj.append(None if i == 0 else rnd(d, dim) * d ** -0.5)
+        prev = c
+    head = AdaptiveSoftmax(list(cutoff), emb, proj, rnd(len(cutoff) - 1, d) * d ** -0.5, dev)
+    batches = [int(v) for v in A.batches.split(",")]
+    Bmax = max(batches)
+    zipf = -1.1 * torch.log(torch.arange(1, V + 1, device=dev, dtype=torch.float32))
+    rows = {"peaked": torch.log_softmax(torch.stack([zipf[torch.randperm(V, generator=g, device=dev)] for _ in range(Bmax)]), dim=1),
+            "flat": torch.log_softmax(rnd(Bmax, V), dim=1)}
+    x = rnd(Bmax, d)
+    lines = []
+
+    def log(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    log(f"the pick of one decoding step, rows [B, {V}]; device events, median of {A.steps} after {A.warmup}, the forms taking turns; us")
+    log(f"{'profile':>7} {'B':>4} | {'head':>9} | {'top-k pick':>10} | {'top-p 0.9':>9} {'TB/s':>6} {'mean n':>8} | {'top-p inf':>9} {'TB/s':>6} | "
+        f"{'top-p <= head':>13}")
+    ok = True
+    for name, R in rows.items():
+        for B in batches:
+            lp, xb = R[:B], x[:B]
+            out = torch.empty(B, V, device=dev)
+            bv, bi = torch.empty(B, 10, device=dev), torch.empty(B, 10, dtype=torch.int64, device=dev)
+            u = torch.rand(B, generator=g, device=dev)
+            nxt, nlp = torch.empty(B, dtype=torch.int64, device=dev), torch.empty(B, device=dev)
+            n_keep = torch.zeros(B, dtype=torch.int32, device=dev)
+
+            def f_head():
+                head.log_probs(xb, out=out)
+
+            def f_topk():
+                ops.topk_merge(lp, bv, bi, init=True)
+                ops.sample_topk(bv, bi, u=u, out=nxt, out_logp=nlp)
+
+            def f_p09():
+                ops.sample_topp(lp, 0.9, u, out=nxt, out_logp=nlp, n_keep=n_keep)
+
+            def f_pinf():
+                ops.sample_topp(lp, float("inf"), u, out=nxt, out_logp=nlp)
+
+            (t_head, t_topk, t_p09, t_pinf), _ = median_ms([f_head, f_topk, f_p09, f_pinf], A.steps, A.warmup)
+            f_p09()
+            mean_n = float(n_keep.float().mean())
+            rate = lambda ms: B * V * 4 / (ms * 1e-3) / 1e12
+            good = max(t_p09, t_pinf) <= t_head
+            ok = ok and good
+            log(f"{name:>7} {B:>4} | {t_head * 1e3:>9.1f} | {t_topk * 1e3:>10.1f} | {t_p09 * 1e3:>9.1f} {rate(t_p09):>6.3f} {mean_n:>8.0f} | "
+                f"{t_pinf * 1e3:>9.1f} {rate(t_pinf):>6.3f} | {'yes' if good else 'NO':>13}")
+            print(json.dumps({"pick": name, "B": B, "V": V, "head_us": round(t_head * 1e3, 1), "topk_pick_us": round(t_topk * 1e3, 1),
+                              "topp09_us": round(t_p09 * 1e3, 1), "topp_inf_us": round(t_pinf * 1e3, 1), "mean_nucleus": mean_n,
+                              "topp09_row_TBps": round(rate(t_p09), 4), "topp_inf_row_TBps": round(rate(t_pinf), 4),
+                              "topp_le_head": bool(good)}), flush=True)
+    log(f"row bytes / pick time above; for scale: achievable HBM rate {HBM_RATE / 1e12} TB/s, L2 34.5 TB/s (chip-wide; one workgroup per row "
+        "uses one CU of 256).  " + ("At every B the top-p pick costs no more than the head." if ok else "THE TOP-P PICK COSTS MORE THAN THE HEAD SOMEWHERE."))
+    if A.out:
+        with open(A.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--steps", type=int, default=30)
@@ -76,9 +158,15 @@ def main():
     p.add_argument("--ffn", type=int, default=4096)
     p.add_argument("--vocab", type=int, default=267744)
     p.add_argument("--fp16", action="store_true")
+    p.add_argument("--pick", action="store_true", help="time the per-token pick (head, top-k pick, top-p pick) instead of the step")
+    p.add_argument("--out", default=None, help="--pick: also write the table to this file")
     A = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("generate_bench needs the GPU: a timing taken elsewhere says nothing about it")
+    if A.pick:
+        if A.batches == "1,8,32":
+            A.batches = "1,8,32,128"
+        return pick_bench(A, torch.device("cuda:0"))
     from gnnlm_amd import _lib, ops
     dev = torch.device("cuda:0")
     lm = build(A, dev)
