@@ -16,7 +16,7 @@ MFMA GEMM (``gnnlm_gemm_nt``), probe selection and k-selection by ``gnnlm_ivfpq_
 k-th-best threshold, the remaining lists only emit scores above that threshold.
 
 At M = 64 (the reference's PQ64) the thresholded round is a FILTER on the int8 matrix cores followed by an exact re-score
-(``csrc/ivfpq_mfma.hip``: 8-bit tables with a guaranteed one-sided bound, eight queries of a list per workgroup, the
+(``csrc/ivfpq8_scan.hip``: 8-bit tables with a guaranteed one-sided bound, eight queries of a list per workgroup, the
 sums taken by ``v_smfmac_i32_16x16x128_i8`` (round 3: ``v_mfma_i32_16x16x64_i8``); survivors re-scored in float32 in the summation order of the float32 scan), so
 candidates and scores are those of the one-pass float32 scan -- ``IVFPQIndex(..., scan="f32")`` selects that scan.
 With ``attach_vals`` the index carries each key's label next to its id (one 8-byte payload per key), and the search
@@ -73,7 +73,7 @@ class _LazyStats(dict):
 
 def choose_route(M, ntotal, max_list, nlist, scan=None, metric="ip", list_term_bytes=4 << 30):
     """The kernels an index is searched with, decided once from the constructor's numbers -> (route, L2 term | None).
-    route "int8": M = 64, the int8-MFMA filter + exact re-score over tiles of 16 code rows (csrc/ivfpq_mfma.hip);
+    route "int8": M = 64, the int8-MFMA filter + exact re-score over tiles of 16 code rows (csrc/ivfpq8_scan.hip, ivfpq8_rescore.hip);
     "packed": M = 32 / 64, the float32 scan over its own image of the code rows (blocks of 64 rows, bytes in rotated order) and
     tables in [half][code][sub-quantizer] order -- look-ups without LDS bank conflicts (csrc/ivfpq.hip); scan="f32" asks for it at
     M = 64 too (tests compare the int8 search with it);  "rowmajor": one table per (query, list) task over the codes as stored.
@@ -89,7 +89,7 @@ def choose_route(M, ntotal, max_list, nlist, scan=None, metric="ip", list_term_b
     if scan == "rowmajor":
         return "rowmajor", term
     # (a survivor record packs the row inside its list into 19 bits and the list into 18: longer / more lists take the float32 scan)
-    if M == 64 and ntotal and ntotal < (1 << 32) and scan != "f32" and max_list < (1 << 19) and nlist <= (1 << 18):
+    if M == 64 and ntotal and ntotal < (1 << 32) and scan != "f32" and max_list < (1 << IVFPQIndex.SURV_ROW_BITS) and nlist <= (1 << IVFPQIndex.SURV_LIST_BITS):
         return "int8", term
     return ("packed" if M in (32, 64) and ntotal else "rowmajor"), term
 
@@ -174,6 +174,20 @@ class IVFPQIndex:
     UNDERFLOW = 1 << 30      # "survivor count" of a query whose sampled threshold left fewer than k candidates: searched again like an overflow
     COLUMNS = (1 << 30) - 1  # ... of a query with more candidates than the selection has columns (a larger survivor capacity would not help it)
     LABEL_BITS = 24                                                          # payload = id << 24 | label (ids < 2^39, labels < 2^24)
+    # What the int8 search's kernels expect of the buffers allocated here: csrc/ivfpq8_layout.h by value (tests/test_ivfpq8_layout_cpu.py
+    # holds the two sides together)
+    QG = 8                       # queries per group of the scan's task table
+    HIST_BINS = 1024             # threshold pass: counters per (query, list) histogram
+    CNT_STRIDE = 16              # int32 per survivor counter: one 64-byte line each (column 0 counts)
+    WORK_CTR_SHAPE = (8, 16)     # the persistent workgroups' group counters: one 64-byte line per XCD
+    QLUT_SHAPE = (2, 256, 32)    # a query's byte table [half][code][slot]
+    QMETA = 4                    # ... and its {delta, sum_lo, absmax, 0}
+    SURV_ROW_BITS, SURV_LIST_BITS = 19, 18   # a survivor record holds the row inside its list and the list
+
+    @classmethod
+    def n_groups_cap(cls, nq, P, nlist):
+        """rows gnnlm_ivfpq_build_groups needs for nq queries with P probes each: every list's last group may be partly filled"""
+        return nq * P // cls.QG + nlist + 1
 
     def __init__(self, R, coarse, pq, list_off, list_ids, list_codes, nprobe=32, cosine=True, dense_probes=None, cand_cap=None,
                  score_bytes=6 << 30, scan=None, metric="ip", list_term_bytes=4 << 30):
@@ -226,7 +240,6 @@ class IVFPQIndex:
             self.cand_cap = 32768 if self.route == "int8" else 16384
         self.refine_tau = True                   # the threshold refinement inside the re-score's launch (False: the re-score alone, tests)
         self.keep_candidates, self.last_candidates = False, None             # tests / debugging: (cv, ci, cc, tau) of the last block's thresholded round
-        self.keep_work_ctr, self.last_work_ctr = False, None                 # instrumented builds (GNNLM_IVF8_EXP & 512) leave phase times in the last scan8's counters
         self._side_streams = {}                                              # raw stream -> its side stream
         self._worst_host, self._worst_next = None, 0                         # pinned landing slots (``_landing_slot``), pinned with the first search
         self.stats = {}                                                      # device-side work counters of the last search that finished (bench.py)
@@ -452,16 +465,16 @@ class IVFPQIndex:
         return blk.cc
 
     def _block_int8(self, plan, blk, out, stats):
-        """M = 64: everything on the int8 matrix cores (csrc/ivfpq_mfma.hip).  (1) threshold pass: histograms of the integer sums of the
+        """M = 64: everything on the int8 matrix cores (csrc/ivfpq8_prep.hip, ivfpq8_scan.hip, ivfpq8_rescore.hip).  (1) threshold pass: histograms of the integer sums of the
         first `dense` lists (a sample of them: plan.S) -> a lower bound tau of the query's k-th best score (no per-key output, no
         selection); (2) filter: every probed list, keys whose integer sum can reach tau; (3) exact float32 scores of the survivors,
         score > tau -> candidates; (4) one k-selection over the candidates.  -> the survivor counts to hold against plan.cap."""
         dev, nq, pi, cc = self.device, blk.pv.shape[0], blk.pi, blk.cc
-        hist = torch.empty(nq, plan.dense, 1024, device=dev, dtype=torch.int32)   # per (query, list): sum_u >> 4 counted on the device
-        self._scan8(blk.tables, blk.cs, self._groups(pi[:, :plan.dense], seg=1024), hist=hist, stride=plan.S)
+        hist = torch.empty(nq, plan.dense, self.HIST_BINS, device=dev, dtype=torch.int32)   # per (query, list): sum_u >> 4 counted on the device
+        self._scan8(blk.tables, blk.cs, self._groups(pi[:, :plan.dense], seg=self.HIST_BINS), hist=hist, stride=plan.S)
         tau = self._tau(plan, blk, hist)
         surv = torch.empty(nq, plan.cap, 2, device=dev, dtype=torch.int32)
-        sc16 = torch.zeros(nq, 16, device=dev, dtype=torch.int32)              # one 64-byte line per counter (column 0)
+        sc16 = torch.zeros(nq, self.CNT_STRIDE, device=dev, dtype=torch.int32)   # one 64-byte line per counter (column 0)
         g2 = self._groups(pi)
         stats.add("groups", lambda g=g2[2]: g[0].double())
         self._scan8(blk.tables, blk.cs, g2, filt=(tau, surv, sc16))
@@ -501,7 +514,7 @@ class IVFPQIndex:
         lut = torch.empty(nq, self.M * 256, device=dev, dtype=torch.float32)
         tables = side = None
         if self.route == "int8":
-            tables = (torch.empty(nq, 2, 256, 32, dtype=torch.uint8, device=dev), torch.empty(nq, 4, dtype=torch.float32, device=dev))
+            tables = (torch.empty(nq, *self.QLUT_SHAPE, dtype=torch.uint8, device=dev), torch.empty(nq, self.QMETA, dtype=torch.float32, device=dev))
             if not torch.cuda.is_current_stream_capturing():
                 cur = torch.cuda.current_stream()
                 side = self._side_streams.get(cur.cuda_stream)
@@ -554,10 +567,10 @@ class IVFPQIndex:
         of the ~25 of ``tests/ivfpq_groups_ref.py``, the torch reference of the same table); same tuple."""
         nq, P = pl.shape
         dev = pl.device
-        G = nq * P // 8 + self.nlist + 1
+        G = self.n_groups_cap(nq, P, self.nlist)
         grp_list = torch.empty(G, dtype=torch.int32, device=dev)
-        grp_q = torch.empty(G, 8, dtype=torch.int32, device=dev)
-        grp_out = torch.empty(G, 8, dtype=torch.int64, device=dev) if seg is not None else None
+        grp_q = torch.empty(G, self.QG, dtype=torch.int32, device=dev)
+        grp_out = torch.empty(G, self.QG, dtype=torch.int64, device=dev) if seg is not None else None
         n_groups = torch.empty(1, dtype=torch.int32, device=dev)
         scratch = torch.empty(2 * (self.nlist + 1), dtype=torch.int32, device=dev)
         _lib.call("gnnlm_ivfpq_build_groups", ctypes.c_void_p(pl.data_ptr()), pl.stride(0), nq, P, self.nlist, seg or 0, _lib.ptr(grp_list),
@@ -573,10 +586,8 @@ class IVFPQIndex:
         d.nlist, d.max_list = self.nlist, self.max_list
         d.qlut, d.qmeta, d.coarse, d.ld_coarse = tables[0].data_ptr(), tables[1].data_ptr(), cs.data_ptr(), cs.stride(0)
         d.grp_list, d.grp_q, d.n_groups, d.max_groups = groups[0].data_ptr(), groups[1].data_ptr(), groups[2].data_ptr(), groups[3]
-        ctr = torch.zeros(8, 16, device=self.device, dtype=torch.int32)          # the persistent workgroups' work counters (one per XCD)
+        ctr = torch.zeros(*self.WORK_CTR_SHAPE, device=self.device, dtype=torch.int32)   # the persistent workgroups' work counters (one per XCD)
         d.work_ctr = ctr.data_ptr()
-        if self.keep_work_ctr:
-            self.last_work_ctr = ctr
         if hist is not None:
             d.out_hist, d.grp_out = hist.data_ptr(), groups[4].data_ptr()
         else:

@@ -1032,7 +1032,7 @@ def topk_merge(scores, best_val, best_id, col0=0, col_ids=None, col_scale=None, 
 
 
 def ivfpq_pack_tiles(codes):
-    """codes [N, 64] u8 -> the int8-MFMA scan's image (csrc/ivfpq_mfma.hip): ceil(N / 16) tiles x [4 groups][16 rows][16 bytes],
+    """codes [N, 64] u8 -> the int8-MFMA scan's image (csrc/ivfpq8_prep.hip): ceil(N / 16) tiles x [4 groups][16 rows][16 bytes],
     byte p of (tile t, group g, row i) = codes[16 t + i][16 g + (i + p) % 16]; rows beyond N are zero."""
     _dev(codes)
     _dtype(codes, torch.uint8, "codes")

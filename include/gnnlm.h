@@ -636,7 +636,7 @@ int gnnlm_ivfpq_pack_codes(const uint8_t* codes, int64_t N, int32_t M, uint8_t* 
 int gnnlm_ivfpq_pack_lut(const float* lut, int64_t ld_lut, int64_t n, int32_t M, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * ABI 6: the filtered scan on the int8 matrix cores, M = 64 (csrc/ivfpq_mfma.hip) -- the thresholded round of the same
+ * ABI 6: the filtered scan on the int8 matrix cores, M = 64 (csrc/ivfpq8_scan.hip) -- the thresholded round of the same
  * search (faiss IndexIVFPQ.search behind knn/knn_model.py:100), as a FILTER with a guaranteed bound followed by an exact
  * float32 re-score, so that the candidates and their scores are those of the one-pass float32 scan above:
  *   gnnlm_ivfpq_pack_tiles     codes [N, 64] -> the scan's image: tiles of 16 rows, [tile][g 0..3][i 0..15][p 0..15] =

@@ -1,4 +1,4 @@
-"""gnnlm_ivfpq_tables (csrc/ivfpq_mfma.hip): the f32 ADC tables and their int8 image in one launch.  Contract under test: the
+"""gnnlm_ivfpq_tables (csrc/ivfpq8_prep.hip): the f32 ADC tables and their int8 image in one launch.  Contract under test: the
 three outputs are BIT-identical to the pair it replaces (gnnlm_gemm_nt with the descriptor of IVFPQIndex._tables_begin, then
 gnnlm_ivfpq_quantize_lut), and a whole search with it (the default) equals the float32 scan's.  Also: the work counters of a
 search are its own when two searches are in flight on one index."""

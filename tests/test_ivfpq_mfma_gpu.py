@@ -1,4 +1,4 @@
-"""The int8-MFMA filtered IVF-PQ scan (csrc/ivfpq_mfma.hip): the thresholded round of the on-device
+"""The int8-MFMA filtered IVF-PQ scan (csrc/ivfpq8_scan.hip, ivfpq8_rescore.hip): the thresholded round of the on-device
 replacement of faiss ``index.search`` (knn/knn_model.py:100; index ``OPQ64_1024,IVF4096,PQ64``, nprobe 32:
 gnnlm_scripts/wiki103/find_knn.sh:8-13).
 
