@@ -30,6 +30,9 @@ int ivfpq_tau(const gnnlm_ivfpq_tau_t& d, hipStream_t stream);
 // the search's probe selection and final k-selection in kernels of their own (ivfpq_select.hip)
 int ivfpq_select_probes(const gnnlm_ivfpq_select_probes_t& d, hipStream_t stream);
 int ivfpq_select_final(const gnnlm_ivfpq_select_final_t& d, hipStream_t stream);
+// adding keys: the residual encode of assigned rows and the merge behind the old rows of their lists (ivfpq_add.hip)
+int ivfpq_encode_rows(const gnnlm_ivfpq_encode_t& d, hipStream_t stream);
+int ivfpq_list_merge(const gnnlm_ivfpq_list_merge_t& d, hipStream_t stream);
 
 // gemm.hip: refusals, the route (gemm_route.h), one launch
 int gemm_nt(const GemmParams& p, hipStream_t stream);

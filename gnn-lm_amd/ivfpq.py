@@ -27,7 +27,7 @@ Host path of one search ("The search's host path"): the constructor n
 probes, capacities, block size, sampled rank, who splits the payloads); every query block fills one ``_Block`` of buffers and runs
 its route's rounds; the call's ``_Outcome`` waits in a ``_PendingSearch`` until ``_finish`` has looked at the survivor counts and
 repaired what overflowed.  One private function fills each kernel descriptor.  ``IVFPQIndex.build`` is the offline producer
-(``ivfpq_train.py``).
+(``ivfpq_train.py``); ``IVFPQIndex.train`` + ``add`` are its two halves: an index, however it was made, takes new keys without retraining.
 
 PARITY UNPINNED against faiss itself (not in the image, no version pinned): the pin is the numpy restatement
 ``oracle/ivfpq.py`` over the SAME index arrays (tests/test_knn_search_gpu.py)."""
@@ -194,6 +194,7 @@ class IVFPQIndex:
         self.R, self.coarse, self.pq = R, coarse, pq                         # [d, d], [nlist, d], [M, 256, dsub]  f32
         self.list_off, self.list_ids, self.list_codes = list_off, list_ids, list_codes   # i64 [nlist+1], i64 [N], u8 [N, M]
         self.nprobe, self.cosine, self.dense_probes, self.cand_cap = nprobe, cosine, dense_probes, cand_cap
+        self._given = dict(dense_probes=dense_probes, cand_cap=cand_cap, scan=scan, list_term_bytes=list_term_bytes)   # as passed (``add``)
         self.threshold_sample = 4                # every S-th tile of the threshold lists is histogrammed (1: all of them -- see plan_search)
         self.sample_min_keys_per_k = 64          # ... when the threshold lists hold at least this many keys per neighbour asked for
         self.sample_sigmas = 4.5                 # margin of the sample's rank (tests lower it to force the verification to fail)
@@ -264,6 +265,35 @@ class IVFPQIndex:
         """The offline producer: train and add every key (``ivfpq_train.build_arrays``), then the index over those arrays."""
         arrays = ivfpq_train.build_arrays(keys, nlist, M, device, cosine, iters, train_size, seed, chunk, opq_iters, metric)
         return cls(*arrays, nprobe=nprobe, cosine=cosine, metric=metric, **kw)
+
+    @classmethod
+    def train(cls, keys, nlist, M, device="cuda", cosine=True, nprobe=32, iters=10, train_size=262144, seed=0, opq_iters=0, metric="ip",
+              chunk=1 << 18, **kw):
+        """A trained index without keys (``ntotal == 0``; the reference's ``IndexBuilder.train`` and its ``faiss_store.trained.*``
+        file, knn/index_builder.py:66-95): it saves, loads and takes keys with ``add``; searching it is not supported."""
+        device = torch.device(device)
+        R, coarse, pq = ivfpq_train.train(keys, nlist, M, device, cosine, iters, train_size, seed, chunk, opq_iters, metric)
+        return cls(R, coarse, pq, *ivfpq_train.empty_lists(nlist, M, device), nprobe=nprobe, cosine=cosine, metric=metric, **kw)
+
+    def add(self, keys, ids=None, chunk=1 << 18):
+        """A NEW index that holds this one's keys and ``keys`` [n, d] (numpy array, memmap or torch tensor, fp16 / f32, read chunk by
+        chunk) under ``ids`` (default ntotal .. ntotal + n - 1: the reference's ``add_with_ids(keys, np.arange(start, end))``,
+        knn/index_builder.py:97-109), with this one's settings; nothing is retrained and this index is left as it is.  New keys go
+        behind the old keys of their lists (``ivfpq_train.add_rows``).  Labels are not carried over: ``attach_vals`` with the grown
+        table."""
+        n = keys.shape[0]
+        if keys.ndim != 2 or keys.shape[1] != self.R.shape[1]:
+            raise ValueError(f"add: keys [n, {self.R.shape[1]}], got {tuple(keys.shape)}")
+        if ids is None:
+            ids = torch.arange(self.ntotal, self.ntotal + n, dtype=torch.int64, device=self.device)
+        else:
+            ids = torch.as_tensor(ids if isinstance(ids, torch.Tensor) else np.asarray(ids)).to(self.device, torch.int64).contiguous()
+            if ids.shape != (n,):
+                raise ValueError("add: one id per key")
+        arrays = ivfpq_train.add_rows(self.R, self.coarse, self.pq, self.list_off, self.list_ids, self.list_codes, keys, ids,
+                                      self.cosine, self.metric, chunk)
+        return type(self)(self.R, self.coarse, self.pq, *arrays, nprobe=self.nprobe, cosine=self.cosine, score_bytes=self.score_bytes,
+                          metric=self.metric, **self._given)
 
     def save(self, path):
         arrays = dict(R=self.R, coarse=self.coarse, pq=self.pq, list_off=self.list_off, list_ids=self.list_ids, list_codes=self.list_codes)
@@ -498,14 +528,7 @@ class IVFPQIndex:
     # ------------------------------------------------------------------------------------------ one function per descriptor
     def _select_probes(self, plan, cs, pv, pi, col_bias=None):
         """the nprobe best lists of every query, best first (csrc/ivfpq_select.hip); shapes it does not take go to gnnlm_topk_merge"""
-        if not plan.select or cs.shape[1] > 4096 or pv.shape[1] > 64:
-            return ops.topk_merge(cs, pv, pi, largest=True, init=True, col_bias=col_bias)
-        d = _lib.gnnlm_ivfpq_select_probes_t()
-        d.scores, d.ld, d.n, d.ncols = cs.data_ptr(), cs.stride(0), cs.shape[0], cs.shape[1]
-        if col_bias is not None:
-            d.col_bias = col_bias.data_ptr()
-        d.k, d.largest, d.out_val, d.out_id = pv.shape[1], 1, pv.data_ptr(), pi.data_ptr()
-        _lib.call_desc("gnnlm_ivfpq_select_probes", d)
+        ops.ivfpq_select_probes(cs, pv, pi, col_bias, plan.select)
 
     def _tables_begin(self, qr):
         """lut[q][m][c] = <q'_m, p_mc> (M small GEMMs) and, for the int8 filter, its byte image: enqueued on a side stream of the

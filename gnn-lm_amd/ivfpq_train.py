@@ -1,12 +1,15 @@
 """The offline producer of an IVF-PQ index (``IVFPQIndex.build`` delegates here; the reference delegates it to faiss:
 knn/index_builder.py:79-150): plain Lloyd k-means for the product quantizers, spherical k-means (unit-norm centroids, what faiss's
 index_factory sets for inner-product indexes) for the coarse one, a random orthonormal matrix for R or OPQ rounds from it (faiss
-alternates OPQ updates; any orthonormal R gives a valid index).  It runs on the GPU with torch ops -- offline tooling, not the
-hot path; ``quantize_features.py`` trains its feature quantizer with the same ``kmeans`` / ``train_opq``."""
+alternates OPQ updates; any orthonormal R gives a valid index).  Training runs on the GPU with torch ops -- offline tooling, not the
+hot path; ``quantize_features.py`` trains its feature quantizer with the same ``kmeans`` / ``train_opq``.  ADDING keys (``add_rows``:
+to an empty index for a build, to an existing one to grow it) runs on this library's kernels: csrc/ivfpq_add.hip."""
+import os
+
 import numpy as np
 import torch
 
-from . import _lib
+from . import ops
 
 
 def kmeans(x, k, iters, gen, spherical=False, init=None):
@@ -67,28 +70,33 @@ def train_opq(x, M, R0, iters, gen, pq_iters=4):
     return R
 
 
-def build_arrays(keys, nlist, M, device="cuda", cosine=True, iters=10, train_size=262144, seed=0, chunk=1 << 18, opq_iters=0,
-                 metric="ip"):
-    """Train (rotation, coarse centroids, residual product quantizer) on a sample and add every key.  ``opq_iters`` = 0: a
-    random orthonormal rotation (spreads the variance over the sub-spaces); > 0: that many rounds of OPQ training from it
-    (``train_opq``: what the reference's ``OPQ64_1024`` block asks faiss for).
-    -> (R, coarse, pq, list_off, list_ids, list_codes), the constructor arguments of ``IVFPQIndex``."""
+def _rows(keys, lo, hi, device, cosine):
+    """rows lo .. hi of a key table (numpy array / memmap / torch tensor, fp16 or f32) on the device in f32, normalised if cosine"""
+    x = torch.from_numpy(np.ascontiguousarray(keys[lo:hi]).astype(np.float32)).to(device) if not isinstance(keys, torch.Tensor) \
+        else keys[lo:hi].to(device, torch.float32)
+    return x / (x ** 2).sum(1, keepdim=True).sqrt() if cosine else x
+
+
+def rotated_rows(keys, lo, hi, R, cosine):
+    """rows lo .. hi as the index sees them: normalised if cosine, rotated on ``gnnlm_gemm_nt`` (float32, on R's device)"""
+    return ops.gemm_nt(_rows(keys, lo, hi, R.device, cosine), R)
+
+
+def train(keys, nlist, M, device="cuda", cosine=True, iters=10, train_size=262144, seed=0, chunk=1 << 18, opq_iters=0, metric="ip"):
+    """Train (rotation, coarse centroids, residual product quantizer) on a sample of the keys.  ``opq_iters`` = 0: a random
+    orthonormal rotation (spreads the variance over the sub-spaces); > 0: that many rounds of OPQ training from it (``train_opq``:
+    what the reference's ``OPQ64_1024`` block asks faiss for).  -> (R, coarse, pq); the reference's ``IndexBuilder.train``
+    (knn/index_builder.py:66-95)."""
     device = torch.device(device)
     gen = torch.Generator(device=device)
     gen.manual_seed(seed)
     N, d = keys.shape
     assert d % M == 0 and (d // M) % 4 == 0 and M % 16 == 0, "need dsub % 4 == 0 and M % 16 == 0"
     dsub = d // M
-
-    def rows(lo, hi):
-        x = torch.from_numpy(np.ascontiguousarray(keys[lo:hi]).astype(np.float32)).to(device) if not isinstance(keys, torch.Tensor) \
-            else keys[lo:hi].to(device, torch.float32)
-        return x / (x ** 2).sum(1, keepdim=True).sqrt() if cosine else x
-
     cpu_gen = torch.Generator().manual_seed(seed)
     R = torch.linalg.qr(torch.randn(d, d, generator=cpu_gen, dtype=torch.float64))[0].to(torch.float32).to(device)
     pick = np.sort(np.random.RandomState(seed).choice(N, size=min(N, train_size), replace=False))
-    xt = torch.cat([rows(int(s), int(min(N, s + chunk)))[torch.from_numpy(pick[(pick >= s) & (pick < s + chunk)] - s).to(device)]
+    xt = torch.cat([_rows(keys, int(s), int(min(N, s + chunk)), device, cosine)[torch.from_numpy(pick[(pick >= s) & (pick < s + chunk)] - s).to(device)]
                     for s in range(0, N, chunk)])
     if opq_iters > 0:
         R = train_opq(xt, M, R, opq_iters, gen)
@@ -100,18 +108,51 @@ def build_arrays(keys, nlist, M, device="cuda", cosine=True, iters=10, train_siz
     nearest = lambda x: ((x @ coarse.t()) - (0.5 * (coarse ** 2).sum(1)[None, :] if l2 else 0.0)).argmax(1)
     resid = xt - coarse[nearest(xt)]
     pq = torch.stack([kmeans(resid[:, m * dsub:(m + 1) * dsub].contiguous(), 256, iters, gen) for m in range(M)])
-    # add every key: list assignment + residual PQ codes (HIP argmin kernel of TorchPQCodec.encode)
-    assign = torch.empty(N, dtype=torch.int64, device=device)
-    codes = torch.empty(N, M, dtype=torch.uint8, device=device)
+    return R.contiguous(), coarse.contiguous(), pq.contiguous()
+
+
+def add_rows(R, coarse, pq, list_off, list_ids, list_codes, keys, ids, cosine=True, metric="ip", chunk=1 << 18):
+    """Add ``keys`` [n, d] with the ids ``ids`` [n] (i64, on the device) to the list-ordered arrays of an index -> the merged
+    (list_off, list_ids, list_codes), new tensors; the reference's ``add_with_ids`` loop (knn/index_builder.py:97-109).  Per chunk
+    of rows: rotation and coarse scores on ``gnnlm_gemm_nt``, the list of a row by the SEARCH's probe selection at one probe (the
+    list the search ranks first for the key as a query, by the same arithmetic; ties to the lowest list), the residual codes by
+    ``gnnlm_ivfpq_encode_rows`` (no residual tensor).  Then one placement and one ``gnnlm_ivfpq_list_merge``: new rows go behind
+    the old rows of their lists in the order given."""
+    device, n, nlist = coarse.device, keys.shape[0], coarse.shape[0]
+    M = pq.shape[0]
+    assign = torch.empty(n, dtype=torch.int64, device=device)
+    codes = torch.empty(n, M, dtype=torch.uint8, device=device)
+    n_bad = torch.zeros(1, dtype=torch.int32, device=device)
     norm2 = (pq ** 2).sum(2).contiguous()
-    for s in range(0, N, chunk):
-        x = rows(s, min(N, s + chunk)) @ R.t()
-        a = nearest(x)
-        assign[s:s + chunk] = a
-        r = (x - coarse[a]).contiguous()
-        _lib.call("gnnlm_pq_encode", _lib.ptr(r), r.stride(0), _lib.ptr(pq), _lib.ptr(norm2), M, dsub, r.shape[0],
-                  _lib.ptr(codes[s:s + chunk]), _lib.stream())
-    order = torch.sort(assign, stable=True).indices
-    off = torch.zeros(nlist + 1, dtype=torch.int64, device=device)
-    off[1:] = torch.cumsum(torch.bincount(assign, minlength=nlist), 0)
-    return R.contiguous(), coarse.contiguous(), pq.contiguous(), off, order.contiguous(), codes[order].contiguous()
+    col_bias = -0.5 * (coarse ** 2).sum(1).contiguous() if metric == "l2" else None   # (``IVFPQIndex._block_begin``'s expression)
+    select = os.environ.get("GNNLM_IVF_SELECT", "1") != "0"
+    for s in range(0, n, chunk):
+        xr = rotated_rows(keys, s, min(n, s + chunk), R, cosine)
+        cs = ops.gemm_nt(xr, coarse)
+        pv = torch.empty(xr.shape[0], 1, dtype=torch.float32, device=device)
+        pi = torch.empty(xr.shape[0], 1, dtype=torch.int64, device=device)
+        ops.ivfpq_select_probes(cs, pv, pi, col_bias, select)
+        a = assign[s:s + chunk]
+        a.copy_(pi[:, 0])
+        ops.ivfpq_encode_rows(xr, a, coarse, pq, norm2, out=codes[s:s + chunk], n_bad=n_bad)
+    if n and int(n_bad.item()):
+        raise ValueError(f"ivfpq add: {int(n_bad.item())} keys have no list (NaN rows?)")
+    new_off, dest = ops.ivfpq_list_place(assign, list_off)
+    new_ids, new_codes = ops.ivfpq_list_merge(list_off, list_ids, list_codes, dest, ids, codes, new_off)
+    return new_off, new_ids, new_codes
+
+
+def empty_lists(nlist, M, device):
+    """the list arrays of an index without keys"""
+    return (torch.zeros(nlist + 1, dtype=torch.int64, device=device), torch.empty(0, dtype=torch.int64, device=device),
+            torch.empty(0, M, dtype=torch.uint8, device=device))
+
+
+def build_arrays(keys, nlist, M, device="cuda", cosine=True, iters=10, train_size=262144, seed=0, chunk=1 << 18, opq_iters=0,
+                 metric="ip"):
+    """``train`` and ``add_rows`` of every key over an empty index, ids 0 .. N - 1: lists in order, ids ascending inside a list.
+    -> (R, coarse, pq, list_off, list_ids, list_codes), the constructor arguments of ``IVFPQIndex``."""
+    device = torch.device(device)
+    R, coarse, pq = train(keys, nlist, M, device, cosine, iters, train_size, seed, chunk, opq_iters, metric)
+    ids = torch.arange(keys.shape[0], dtype=torch.int64, device=device)
+    return (R, coarse, pq) + add_rows(R, coarse, pq, *empty_lists(nlist, M, device), keys, ids, cosine, metric, chunk)

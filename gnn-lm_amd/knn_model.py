@@ -138,7 +138,7 @@ class KNNModel(object):
         if os.path.exists(own):
             from .ivfpq import IVFPQIndex
             LOGGING.info("IVF-PQ index %s searched on %s", own, self.device)
-            return IVFPQIndex.load(own, device=self.device, nprobe=self.probe)
+            return self._warn_if_stale(IVFPQIndex.load(own, device=self.device, nprobe=self.probe), own)
         if os.path.isfile(self.index_file):
             from . import faiss_io
             if faiss_io.sniff(self.index_file) in ("IxPT", "IwPQ"):
@@ -147,7 +147,7 @@ class KNNModel(object):
                 try:
                     index = IVFPQIndex.from_faiss_file(self.index_file, device=self.device, cosine=self.cosine, nprobe=self.probe)
                     LOGGING.info("faiss IVF-PQ file %s searched on %s", self.index_file, self.device)
-                    return index
+                    return self._warn_if_stale(index, self.index_file)
                 except ValueError as e:
                     LOGGING.warning("%s", e)
             elif faiss_io.sniff(self.index_file) in ("IxMp", "IxM2", "IxFI", "IxF2", "IxFl"):
@@ -173,6 +173,14 @@ class KNNModel(object):
         LOGGING.warning("faiss not available: exact search over %d keys on the GPU", self.dstore_size)
         base = "l2" if self.metric_type.endswith("l2") else "ip"
         return ExactIndex(self.keys, base, self.cosine, self.device)
+
+    def _warn_if_stale(self, index, path):
+        """an IVF-PQ index that does not cover the datastore as it is now (the reference is silent here): `run_index_build` adds the
+        missing rows without retraining"""
+        if index.ntotal != self.dstore_size:
+            LOGGING.warning("IVF-PQ index %s holds %d keys, the datastore %d: rerun gnnlm_amd.run_index_build to add the new rows",
+                            path, index.ntotal, self.dstore_size)
+        return index
 
     def _keys_device(self):
         if isinstance(getattr(self.index, "keys", None), torch.Tensor):

@@ -1061,6 +1061,101 @@ def ivfpq_key_terms(list_codes, list_off, coarse, pq):
     return out
 
 
+def ivfpq_select_probes(cs, pv, pi, col_bias=None, select=True):
+    """The pv.shape[1] best columns of every row of cs [n, ncols] (+ col_bias), best first, into pv / pi: gnnlm_ivfpq_select_probes
+    (csrc/ivfpq_select.hip); shapes it does not take (and select=False) go to gnnlm_topk_merge, which returns the same bits.  The
+    search picks its probes with it and the add path files a key with it at one probe: the list the search ranks first."""
+    if not select or cs.shape[1] > 4096 or pv.shape[1] > 64:
+        return topk_merge(cs, pv, pi, largest=True, init=True, col_bias=col_bias)
+    d = _lib.gnnlm_ivfpq_select_probes_t()
+    d.scores, d.ld, d.n, d.ncols = cs.data_ptr(), cs.stride(0), cs.shape[0], cs.shape[1]
+    if col_bias is not None:
+        d.col_bias = col_bias.data_ptr()
+    d.k, d.largest, d.out_val, d.out_id = pv.shape[1], 1, pv.data_ptr(), pi.data_ptr()
+    call_desc("gnnlm_ivfpq_select_probes", d)
+
+
+def ivfpq_encode_rows(x, assign, coarse, pq, norm2=None, out=None, list_cnt=None, n_bad=None):
+    """The residual PQ codes of assigned rows (gnnlm_ivfpq_encode_rows): x [n, d] f32 rotated rows (row stride free), assign [n]
+    i64 the list of each row, coarse [nlist, d], pq [M, 256, dsub], norm2 [M, 256] = |p_mc|^2 (computed if None) -> codes [n, M] u8
+    (``out``: a buffer or a row slice of one).  list_cnt [nlist] i64 is incremented per encoded row, n_bad [1] i32 per row whose
+    list does not exist (its codes are left alone)."""
+    _dev(x, assign, coarse, pq, norm2, out, list_cnt, n_bad)
+    _f32(x, coarse, pq, norm2)
+    _dtype(assign, torch.int64, "assign"), _dtype(out, torch.uint8, "out")
+    _dtype(list_cnt, torch.int64, "list_cnt"), _dtype(n_bad, torch.int32, "n_bad")
+    if x.dim() != 2 or pq.dim() != 3 or pq.shape[1] != 256 or coarse.dim() != 2 or not (coarse.is_contiguous() and pq.is_contiguous()):
+        raise ValueError("ivfpq_encode_rows: x [n, d], coarse [nlist, d] and pq [M, 256, dsub] contiguous")
+    (n, d), (M, _, dsub), nlist = x.shape, pq.shape, coarse.shape[0]
+    if coarse.shape[1] != d or assign.shape != (n,) or (list_cnt is not None and list_cnt.shape != (nlist,)):
+        raise ValueError("ivfpq_encode_rows: coarse [nlist, d], assign [n], list_cnt [nlist]")
+    if norm2 is None:
+        norm2 = (pq ** 2).sum(2).contiguous()
+    if norm2.shape != (M, 256) or not norm2.is_contiguous():
+        raise ValueError("ivfpq_encode_rows: norm2 [M, 256] contiguous")
+    if out is None:
+        out = torch.empty(n, M, dtype=torch.uint8, device=x.device)
+    elif out.shape != (n, M):
+        raise ValueError("ivfpq_encode_rows: out [n, M]")
+    e = _lib.gnnlm_ivfpq_encode_t()
+    e.x, e.ldx, e.n, e.assign = x.data_ptr(), max(x.stride(0), d), n, assign.data_ptr()
+    e.coarse, e.nlist, e.pq, e.norm2 = coarse.data_ptr(), nlist, pq.data_ptr(), norm2.data_ptr()
+    e.M, e.dsub, e.d = M, dsub, d
+    e.codes, e.ld_codes = out.data_ptr(), max(out.stride(0), M)
+    if list_cnt is not None:
+        e.list_cnt = list_cnt.data_ptr()
+    if n_bad is not None:
+        e.n_bad = n_bad.data_ptr()
+    call_desc("gnnlm_ivfpq_encode_rows", e)
+    return out
+
+
+def ivfpq_list_place(assign, list_off_old):
+    """Where new rows go: assign [n] i64 (the list of each new row, every one in [0, nlist)), list_off_old [nlist + 1] i64 ->
+    (new_off [nlist + 1], dest [n]): new_off the cumulative sum of old length + new count per list; the new rows of a list keep
+    the order given (a stable sort of assign) behind its old rows, dest = new_off[l] + old_len[l] + rank."""
+    _dev(assign, list_off_old)
+    _dtype(assign, torch.int64, "assign"), _dtype(list_off_old, torch.int64, "list_off_old")
+    nlist, n = list_off_old.numel() - 1, assign.numel()
+    old_len = list_off_old[1:] - list_off_old[:-1]
+    cnt = torch.bincount(assign, minlength=nlist) if n else torch.zeros_like(old_len)
+    if cnt.numel() != nlist:
+        raise ValueError("ivfpq_list_place: assign outside [0, nlist)")
+    new_off = torch.zeros(nlist + 1, dtype=torch.int64, device=assign.device)
+    new_off[1:] = torch.cumsum(old_len + cnt, 0)
+    order = torch.sort(assign, stable=True).indices
+    start = torch.cumsum(cnt, 0) - cnt                                   # first sorted position of every list's new rows
+    srt = assign[order]
+    dest = torch.empty(n, dtype=torch.int64, device=assign.device)
+    dest[order] = new_off[:-1][srt] + old_len[srt] + (torch.arange(n, device=assign.device) - start[srt])
+    return new_off, dest
+
+
+def ivfpq_list_merge(list_off_old, ids_old, codes_old, dest, ids_new, codes_new, new_off, n_bad=None):
+    """Old rows and new rows into the merged list-ordered arrays (gnnlm_ivfpq_list_merge): a list's old rows move as one run to
+    new_off[l], new row i goes to dest[i] (``ivfpq_list_place``).  -> (ids [N0 + n] i64, codes [N0 + n, M] u8), new buffers."""
+    _dev(list_off_old, ids_old, codes_old, dest, ids_new, codes_new, new_off, n_bad)
+    for t, what in ((list_off_old, "list_off_old"), (ids_old, "ids_old"), (dest, "dest"), (ids_new, "ids_new"), (new_off, "new_off")):
+        _dtype(t, torch.int64, what)
+    _dtype(codes_old, torch.uint8, "codes_old"), _dtype(codes_new, torch.uint8, "codes_new"), _dtype(n_bad, torch.int32, "n_bad")
+    N0, n, nlist = ids_old.numel(), ids_new.numel(), new_off.numel() - 1
+    M = codes_new.shape[1] if codes_new.dim() == 2 else -1
+    if (codes_old.shape != (N0, M) or codes_new.shape[0] != n or dest.shape != (n,) or list_off_old.numel() != nlist + 1
+            or not codes_old.is_contiguous()):
+        raise ValueError("ivfpq_list_merge: ids_old [N0], codes_old [N0, M] contiguous, dest / ids_new [n], codes_new [n, M], offsets [nlist + 1]")
+    ids = torch.empty(N0 + n, dtype=torch.int64, device=new_off.device)
+    codes = torch.empty(N0 + n, M, dtype=torch.uint8, device=new_off.device)
+    m = _lib.gnnlm_ivfpq_list_merge_t()
+    m.list_off_old, m.nlist, m.N0 = list_off_old.data_ptr(), nlist, N0
+    m.ids_old, m.codes_old, m.M = ids_old.data_ptr(), codes_old.data_ptr(), M
+    m.n, m.dest, m.ids_new, m.codes_new, m.ld_new = n, dest.data_ptr(), ids_new.data_ptr(), codes_new.data_ptr(), max(codes_new.stride(0), M)
+    m.new_off, m.ids, m.codes = new_off.data_ptr(), ids.data_ptr(), codes.data_ptr()
+    if n_bad is not None:
+        m.n_bad = n_bad.data_ptr()
+    call_desc("gnnlm_ivfpq_list_merge", m)
+    return ids, codes
+
+
 def ivfpq_quantize_lut(lut, M=64):
     """lut [n, M * 256] f32 -> (qlut [n, 2, 256, 32] u8, qmeta [n, 4] f32 = {delta, sum_m lo_m, max |lut|, 0}) with
     lut[m][c] < lo_m + (u + 1) * delta for every entry, u = qlut[m // 32][c][m % 32] ^ 0x80 (the table stores the signed

@@ -766,6 +766,44 @@ typedef struct gnnlm_ivfpq_rescore {
     const float* qmeta;  int32_t k;  int32_t* out_cnt;
 } gnnlm_ivfpq_rescore_t;
 int gnnlm_ivfpq_rescore(const gnnlm_ivfpq_rescore_t* desc, void* stream);
+/* Added within ABI 12 (additive: two new entries and structs).  ADDING keys to an index (faiss `add_with_ids` behind
+ * knn/index_builder.py:97-109), csrc/ivfpq_add.hip.
+ *
+ * gnnlm_ivfpq_encode_rows: the residual PQ codes of rows whose list is known.  x [n, d] are the ROTATED rows (row stride ldx),
+ * assign [n] the list of each row, coarse [nlist, d] contiguous, pq [M, 256, dsub], norm2 [M, 256] = |p_mc|^2, d = M * dsub:
+ *     codes[r][m] = argmin_c ( norm2[m][c] - 2 * dot ),  dot = the fmaf chain from 0 over e = 0 .. dsub - 1 (ascending) of
+ *                   (x[r][m dsub + e] - coarse[assign[r]][m dsub + e]) * pq[m][c][e]
+ * with the residual rounded to float32 once and ties going to the lowest c (no c below +inf: 0) -- gnnlm_pq_encode's arithmetic
+ * on the materialised residual, so the two agree bit for bit.  codes [n, M] u8 with row stride ld_codes.  list_cnt [nlist]
+ * (optional) is INCREMENTED by one per encoded row (integer atomics: the result does not depend on order), n_bad (optional) by one
+ * per row whose assign lies outside [0, nlist): such a row is skipped, its codes stay as they were, nothing out of range is read.
+ * Refused with nothing written: M % 16 != 0, dsub % 4 != 0, d != M * dsub, negative sizes, and with n > 0 null operands or row
+ * strides shorter than the rows.  n = 0 touches nothing.  Rows are addressed with 64 bits.  One launch, no allocation, no sync. */
+typedef struct gnnlm_ivfpq_encode {
+    const float* x;  int64_t ldx;  int64_t n;
+    const int64_t* assign;
+    const float* coarse;  int32_t nlist;
+    const float* pq;  const float* norm2;
+    int32_t M;  int32_t dsub;  int32_t d;
+    uint8_t* codes;  int64_t ld_codes;
+    int64_t* list_cnt;  int32_t* n_bad;
+} gnnlm_ivfpq_encode_t;
+int gnnlm_ivfpq_encode_rows(const gnnlm_ivfpq_encode_t* desc, void* stream);
+/* gnnlm_ivfpq_list_merge: new rows filed behind the old rows of their lists.  Old index: list_off_old [nlist + 1], ids_old [N0],
+ * codes_old [N0, M]; new rows: dest [n] (position in the merged arrays), ids_new [n], codes_new [n, M] (row stride ld_new);
+ * new_off [nlist + 1] the merged offsets.  Old row j of list l lands at new_off[l] + (j - list_off_old[l]) (a list's old rows move
+ * as one run), new row i at dest[i]; ids [N0 + n] and codes [N0 + n, M] are buffers of their own.  A position outside
+ * [0, N0 + n) is skipped and counted in n_bad (optional).  M % 16 == 0, codes_old and codes 16-byte aligned; all byte offsets are
+ * 64-bit.  One launch, no allocation, no sync; N0 = 0, n = 0 and empty lists are valid. */
+typedef struct gnnlm_ivfpq_list_merge {
+    const int64_t* list_off_old;  int32_t nlist;  int64_t N0;
+    const int64_t* ids_old;  const uint8_t* codes_old;  int32_t M;
+    int64_t n;  const int64_t* dest;  const int64_t* ids_new;  const uint8_t* codes_new;  int64_t ld_new;
+    const int64_t* new_off;
+    int64_t* ids;  uint8_t* codes;
+    int32_t* n_bad;
+} gnnlm_ivfpq_list_merge_t;
+int gnnlm_ivfpq_list_merge(const gnnlm_ivfpq_list_merge_t* desc, void* stream);
 
 /* out[0] += sum_i x[i] * (mask ? mask[i] != 0 : 1), accumulated in f64 (score_sum of
  * fairseq_cli/eval_lm.py:273; the reference accumulates in f32 on the CPU) */
