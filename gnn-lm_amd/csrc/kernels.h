@@ -33,6 +33,8 @@ int ivfpq_select_final(const gnnlm_ivfpq_select_final_t& d, hipStream_t stream);
 // adding keys: the residual encode of assigned rows and the merge behind the old rows of their lists (ivfpq_add.hip)
 int ivfpq_encode_rows(const gnnlm_ivfpq_encode_t& d, hipStream_t stream);
 int ivfpq_list_merge(const gnnlm_ivfpq_list_merge_t& d, hipStream_t stream);
+// the coarse step without the score matrix: MFMA scores, a running k-best per row on chip, slabs folded by topk_merge (ivfpq_coarse.hip)
+int ivfpq_coarse_probes(const gnnlm_ivfpq_coarse_t& d, hipStream_t stream);
 
 // gemm.hip: refusals, the route (gemm_route.h), one launch
 int gemm_nt(const GemmParams& p, hipStream_t stream);

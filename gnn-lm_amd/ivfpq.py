@@ -94,6 +94,26 @@ def choose_route(M, ntotal, max_list, nlist, scan=None, metric="ip", list_term_b
     return ("packed" if M in (32, 64) and ntotal else "rowmajor"), term
 
 
+def choose_coarse(route, nlist, coarse=None):
+    """How an index takes its coarse step (the nprobe best lists of a query), decided once from the constructor's numbers -> "dense":
+    the [queries, nlist] scores on ``gnnlm_gemm_nt``, then the probe selection over them; "fused": ``gnnlm_ivfpq_coarse_probes``
+    (csrc/ivfpq_coarse.hip), scores and selection in one kernel, no score matrix -- the float32 routes from
+    ``ivfpq_train.COARSE_FUSED_MIN_LISTS`` lists on.  The int8 route reads the coarse scores again in its scan and stays dense.
+    ``coarse`` = "dense" / "fused" forces a route; the environment's GNNLM_IVF_COARSE does the same for the float32 routes (A/B runs)."""
+    if coarse not in (None, "dense", "fused"):
+        raise ValueError(f"IVFPQIndex: coarse is 'dense' or 'fused', got {coarse!r}")
+    if coarse is not None:
+        return coarse
+    if route == "int8":
+        return "dense"
+    env = os.environ.get("GNNLM_IVF_COARSE")
+    if env:
+        if env not in ("dense", "fused"):
+            raise ValueError(f"GNNLM_IVF_COARSE is 'dense' or 'fused', got {env!r}")
+        return env
+    return "fused" if nlist >= ivfpq_train.COARSE_FUSED_MIN_LISTS else "dense"
+
+
 # What a plan depends on besides the call's own arguments: the index's route and sizes (score_bytes: the budget of the dense round's
 # score rows per query block), its sampling settings as they are now (``_finish`` may have changed them), and the two switches of the
 # environment as they are now (select: GNNLM_IVF_SELECT != "0"; env_query_block: GNNLM_IVF_QUERY_BLOCK)
@@ -135,7 +155,7 @@ def plan_search(ix, k, dense_probes, cap, query_block=None, fold=None):
 # The buffers every route's rounds work on, for one block of queries (``IVFPQIndex._block_begin``): qr [nq, d] = R q; cs [nq, nlist] =
 # <q', c_l>; pv, pi [nq, nprobe] the probed lists' bias and ids, best first (-1: none); lut [nq, M * 256] the ADC tables and, on the int8
 # route, tables = (qlut [nq, 2, 256, 32] u8, qmeta [nq, 4] f32), their byte image; cv, ci [nq, ccap] the scores and payloads of the
-# thresholded round's candidates, cc [nq] how many (zeroed)
+# thresholded round's candidates, cc [nq] how many (zeroed).  With the fused coarse step (``choose_coarse``) cs is None: no such matrix exists
 _Block = namedtuple("_Block", "qr cs pv pi lut tables cv ci cc")
 
 
@@ -190,11 +210,11 @@ class IVFPQIndex:
         return nq * P // cls.QG + nlist + 1
 
     def __init__(self, R, coarse, pq, list_off, list_ids, list_codes, nprobe=32, cosine=True, dense_probes=None, cand_cap=None,
-                 score_bytes=6 << 30, scan=None, metric="ip", list_term_bytes=4 << 30):
+                 score_bytes=6 << 30, scan=None, metric="ip", list_term_bytes=4 << 30, coarse_route=None):
         self.R, self.coarse, self.pq = R, coarse, pq                         # [d, d], [nlist, d], [M, 256, dsub]  f32
         self.list_off, self.list_ids, self.list_codes = list_off, list_ids, list_codes   # i64 [nlist+1], i64 [N], u8 [N, M]
         self.nprobe, self.cosine, self.dense_probes, self.cand_cap = nprobe, cosine, dense_probes, cand_cap
-        self._given = dict(dense_probes=dense_probes, cand_cap=cand_cap, scan=scan, list_term_bytes=list_term_bytes)   # as passed (``add``)
+        self._given = dict(dense_probes=dense_probes, cand_cap=cand_cap, scan=scan, list_term_bytes=list_term_bytes, coarse_route=coarse_route)   # as passed (``add``)
         self.threshold_sample = 4                # every S-th tile of the threshold lists is histogrammed (1: all of them -- see plan_search)
         self.sample_min_keys_per_k = 64          # ... when the threshold lists hold at least this many keys per neighbour asked for
         self.sample_sigmas = 4.5                 # margin of the sample's rank (tests lower it to force the verification to fail)
@@ -211,6 +231,12 @@ class IVFPQIndex:
         self.list_len = list_off[1:] - list_off[:-1]
         self.max_list = int(self.list_len.max().item()) if self.nlist else 0
         self.route, term = choose_route(self.M, self.ntotal, self.max_list, self.nlist, scan, metric, list_term_bytes)
+        # (the argument is `coarse_route`: `coarse` names the centroids)
+        self.coarse_route = choose_coarse(self.route, self.nlist, coarse_route)
+        if self.coarse_route == "fused" and (self.route == "int8" or self.d % 4):
+            if coarse_route == "fused":
+                raise ValueError("IVFPQIndex: coarse_route='fused' needs a float32 route (scan='f32' / 'rowmajor') and d % 4 == 0")
+            self.coarse_route = "dense"
         self.packed_codes = self.tiles = self.list_term = self.key_term = None
         if metric == "l2":
             # squared distances with residual codes: |q' - c_l - r|^2 = |q' - c_l|^2 + sum_m (T[l][m][code] - 2 <q'_m, p_mc>) with the
@@ -261,18 +287,19 @@ class IVFPQIndex:
 
     @classmethod
     def build(cls, keys, nlist, M, device="cuda", cosine=True, nprobe=32, iters=10, train_size=262144, seed=0, chunk=1 << 18,
-              opq_iters=0, metric="ip", **kw):
-        """The offline producer: train and add every key (``ivfpq_train.build_arrays``), then the index over those arrays."""
-        arrays = ivfpq_train.build_arrays(keys, nlist, M, device, cosine, iters, train_size, seed, chunk, opq_iters, metric)
+              opq_iters=0, metric="ip", d_out=None, **kw):
+        """The offline producer: train and add every key (``ivfpq_train.build_arrays``), then the index over those arrays.
+        ``d_out`` < d: a reducing rotation R [d_out, d] (the ``OPQ16_64`` block of the One Billion Word recipe)."""
+        arrays = ivfpq_train.build_arrays(keys, nlist, M, device, cosine, iters, train_size, seed, chunk, opq_iters, metric, d_out)
         return cls(*arrays, nprobe=nprobe, cosine=cosine, metric=metric, **kw)
 
     @classmethod
     def train(cls, keys, nlist, M, device="cuda", cosine=True, nprobe=32, iters=10, train_size=262144, seed=0, opq_iters=0, metric="ip",
-              chunk=1 << 18, **kw):
+              chunk=1 << 18, d_out=None, **kw):
         """A trained index without keys (``ntotal == 0``; the reference's ``IndexBuilder.train`` and its ``faiss_store.trained.*``
         file, knn/index_builder.py:66-95): it saves, loads and takes keys with ``add``; searching it is not supported."""
         device = torch.device(device)
-        R, coarse, pq = ivfpq_train.train(keys, nlist, M, device, cosine, iters, train_size, seed, chunk, opq_iters, metric)
+        R, coarse, pq = ivfpq_train.train(keys, nlist, M, device, cosine, iters, train_size, seed, chunk, opq_iters, metric, d_out)
         return cls(R, coarse, pq, *ivfpq_train.empty_lists(nlist, M, device), nprobe=nprobe, cosine=cosine, metric=metric, **kw)
 
     def add(self, keys, ids=None, chunk=1 << 18):
@@ -291,7 +318,7 @@ class IVFPQIndex:
             if ids.shape != (n,):
                 raise ValueError("add: one id per key")
         arrays = ivfpq_train.add_rows(self.R, self.coarse, self.pq, self.list_off, self.list_ids, self.list_codes, keys, ids,
-                                      self.cosine, self.metric, chunk)
+                                      self.cosine, self.metric, chunk, self._given["coarse_route"])
         return type(self)(self.R, self.coarse, self.pq, *arrays, nprobe=self.nprobe, cosine=self.cosine, score_bytes=self.score_bytes,
                           metric=self.metric, **self._given)
 
@@ -439,26 +466,47 @@ class IVFPQIndex:
         labels = torch.empty(n, plan.k, dtype=torch.int32, device=dev) if plan.fold and return_vals else None
         out, over = _Outcome(val, idx, labels, plan.fold), None
         block = self._block_int8 if self.route == "int8" else self._block_f32
+        # the fused coarse step takes the whole batch at once (nothing of it is [queries, nlist]-sized, and a workgroup's first chunks
+        # of a slab are its dearest: one call over 8192 queries takes half the time of eight over 1024)
+        pre = self._coarse_fused(plan, q) if self.coarse_route == "fused" else None
         for q0 in range(0, n, plan.qb):
-            o = block(plan, self._block_begin(plan, q[q0:q0 + plan.qb], stats), out.rows(q0, q0 + plan.qb), stats)
+            blk = self._block_begin(plan, q[q0:q0 + plan.qb], stats, None if pre is None else tuple(t[q0:q0 + plan.qb] for t in pre))
+            o = block(plan, blk, out.rows(q0, q0 + plan.qb), stats)
             if o is not None:
                 over = o if over is None else torch.cat([over, o])
         return out._replace(over=over)
 
-    def _block_begin(self, plan, qs, stats):
+    def _coarse_fused(self, plan, q):
+        """rotation and coarse step of a whole batch without its [n, nlist] scores -> (qr [n, d], pv, pi [n, nprobe]) as a block holds them"""
+        qr = ops.gemm_nt(q, self.R)
+        pv = torch.empty(q.shape[0], plan.nprobe, device=self.device, dtype=torch.float32)
+        pi = torch.empty(q.shape[0], plan.nprobe, device=self.device, dtype=torch.int64)
+        ops.ivfpq_coarse_probes(qr, self.coarse, pv, pi, -0.5 * self.coarse_n2 if self.metric == "l2" else None)
+        if self.metric == "l2":
+            pv = (2.0 * pv - (qr ** 2).sum(1, keepdim=True)).contiguous()      # the list's bias: -|q' - c_l|^2
+        return qr, pv, pi
+
+    def _block_begin(self, plan, qs, stats, pre=None):
+        """``pre``: the block's rows of ``_coarse_fused`` (the fused coarse route); None: rotation and coarse step of this block here"""
         dev, nq = self.device, qs.shape[0]
-        qr = ops.gemm_nt(qs, self.R)                                            # q' = R q
+        qr = ops.gemm_nt(qs, self.R) if pre is None else pre[0]                 # q' = R q
         # the ADC tables (a store-bound batched GEMM, 2 KB per query and sub-quantizer) and their 8-bit images depend on q' alone: they
         # are built on a side stream beside the coarse scores / probe selection / task table of this stream
         lut, tables, side = self._tables_begin(qr)
-        cs = ops.gemm_nt(qr, self.coarse)                                       # <q', c_l>
-        pv = torch.empty(nq, plan.nprobe, device=dev, dtype=torch.float32)
-        pi = torch.empty(nq, plan.nprobe, device=dev, dtype=torch.int64)
-        if self.metric == "l2":                                                 # the nprobe NEAREST lists: argmax <q', c> - |c|^2 / 2
-            self._select_probes(plan, cs, pv, pi, col_bias=-0.5 * self.coarse_n2)
-            pv = (2.0 * pv - (qr ** 2).sum(1, keepdim=True)).contiguous()      # the list's bias: -|q' - c_l|^2
+        # <q', c_l> and the nprobe best lists, best first; the fused coarse step has done both without the [nq, nlist] matrix
+        if pre is not None:
+            cs, pv, pi = None, pre[1], pre[2]
+        elif self.coarse_route == "fused":
+            cs, (_, pv, pi) = None, self._coarse_fused(plan, qs)
         else:
-            self._select_probes(plan, cs, pv, pi)                               # the nprobe best lists, best first
+            cs = ops.gemm_nt(qr, self.coarse)
+            pv = torch.empty(nq, plan.nprobe, device=dev, dtype=torch.float32)
+            pi = torch.empty(nq, plan.nprobe, device=dev, dtype=torch.int64)
+            if self.metric == "l2":                                             # the nprobe NEAREST lists: argmax <q', c> - |c|^2 / 2
+                self._select_probes(plan, cs, pv, pi, col_bias=-0.5 * self.coarse_n2)
+                pv = (2.0 * pv - (qr ** 2).sum(1, keepdim=True)).contiguous()  # the list's bias: -|q' - c_l|^2
+            else:
+                self._select_probes(plan, cs, pv, pi)                           # the nprobe best lists, best first
         stats.add("pairs", lambda pi=pi: self.list_len[pi.clamp(min=0)].masked_fill(pi < 0, 0).sum().double())
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)                       # (lut / tables were allocated on THIS stream: no record_stream needed)

@@ -1075,6 +1075,44 @@ def ivfpq_select_probes(cs, pv, pi, col_bias=None, select=True):
     call_desc("gnnlm_ivfpq_select_probes", d)
 
 
+def ivfpq_coarse_slabs(n, nlist, k):
+    """Slabs the lists are cut into for ``ivfpq_coarse_probes`` (pure numbers): enough workgroups (64 rows x one slab each) for four
+    per compute unit, slabs no narrower than 4096 lists (a slab's first chunks compact their rows every time), slabs * k columns at
+    most 4096 for the merge."""
+    tiles = max(1, -(-int(n) // 64))
+    return max(1, min(-(-1024 // tiles), int(nlist) // 4096, 4096 // max(int(k), 1), 64))
+
+
+def ivfpq_coarse_probes(x, coarse, pv, pi, col_bias=None, slabs=None):
+    """The pv.shape[1] <= 64 best rows of coarse [nlist, d] for every row of x [n, d] (row stride free) by <x, c> (+ col_bias),
+    best first, into pv [n, P] f32 / pi [n, P] i64: ``ivfpq_select_probes`` over ``gemm_nt(x, coarse)`` without the [n, nlist]
+    matrix (gnnlm_ivfpq_coarse_probes, csrc/ivfpq_coarse.hip).  ``slabs``: runs the lists are cut into (default
+    ``ivfpq_coarse_slabs``); beyond one, the slabs' lists go through an [n, slabs, P] partial and gnnlm_topk_merge."""
+    _dev(x, coarse, pv, pi, col_bias)
+    _f32(x, coarse, pv, col_bias)
+    _dtype(pi, torch.int64, "pi")
+    if x.dim() != 2 or coarse.dim() != 2 or not coarse.is_contiguous() or coarse.shape[1] != x.shape[1] or x.stride(1) != 1:
+        raise ValueError("ivfpq_coarse_probes: x [n, d] with unit column stride, coarse [nlist, d] contiguous")
+    (n, d), nlist, P = x.shape, coarse.shape[0], pv.shape[1] if pv.dim() == 2 else -1
+    if pv.shape != (n, P) or pi.shape != (n, P) or not (pv.is_contiguous() and pi.is_contiguous()):
+        raise ValueError("ivfpq_coarse_probes: pv / pi [n, P] contiguous")
+    if col_bias is not None and (col_bias.shape != (nlist,) or not col_bias.is_contiguous()):
+        raise ValueError("ivfpq_coarse_probes: col_bias [nlist] contiguous")
+    c = _lib.gnnlm_ivfpq_coarse_t()
+    c.x, c.ldx, c.n = x.data_ptr(), max(x.stride(0), d), n
+    c.coarse, c.nlist, c.d = coarse.data_ptr(), nlist, d
+    if col_bias is not None:
+        c.col_bias = col_bias.data_ptr()
+    c.k = P
+    c.slabs = ivfpq_coarse_slabs(n, nlist, P) if slabs is None else int(slabs)
+    if c.slabs > 1:
+        part_val = torch.empty(n, c.slabs, P, dtype=torch.float32, device=x.device)
+        part_id = torch.empty(n, c.slabs, P, dtype=torch.int64, device=x.device)
+        c.part_val, c.part_id = part_val.data_ptr(), part_id.data_ptr()
+    c.out_val, c.out_id = pv.data_ptr(), pi.data_ptr()
+    call_desc("gnnlm_ivfpq_coarse_probes", c)
+
+
 def ivfpq_encode_rows(x, assign, coarse, pq, norm2=None, out=None, list_cnt=None, n_bad=None):
     """The residual PQ codes of assigned rows (gnnlm_ivfpq_encode_rows): x [n, d] f32 rotated rows (row stride free), assign [n]
     i64 the list of each row, coarse [nlist, d], pq [M, 256, dsub], norm2 [M, 256] = |p_mc|^2 (computed if None) -> codes [n, M] u8

@@ -32,7 +32,7 @@ import torch
 from . import ops
 from .data_store import DataStore
 from .faiss_io import write_pq_quantizer
-from .ivfpq_train import kmeans, train_opq
+from .ivfpq_train import _initial_rotation, kmeans, train_opq
 from .path_utils import dstore_path, quantized_feature_path, quantizer_path
 from .pq_wrapper import TorchPQCodec
 
@@ -91,20 +91,6 @@ def training_sample(keys, total_tokens, chunk_size):
         out[offset: offset + len(rows)] = rows                                #  the reference's assignment raises there; here the
         offset += len(rows)                                                   #  sample is what exists)
     return out[:offset]
-
-
-def _initial_rotation(x, d_out, gen):
-    """[d_out, d_in] with orthonormal rows: a random rotation (d_out == d_in) or a random rotation of the d_out leading
-    principal directions (d_out < d_in: what an OPQ<M>_<d_out> block starts from)."""
-    d_in = x.shape[1]
-    cpu_gen = torch.Generator().manual_seed(int(gen.initial_seed()))
-    Q = torch.linalg.qr(torch.randn(d_out, d_out, generator=cpu_gen, dtype=torch.float64))[0]
-    if d_out == d_in:
-        return Q.to(torch.float32).to(x.device)
-    xc = x.double()
-    _, V = torch.linalg.eigh(xc.t() @ xc)                                     # ascending eigenvalues
-    P = V[:, -d_out:].t().cpu()                                               # [d_out, d_in] leading directions
-    return (Q @ P).to(torch.float32).to(x.device)
 
 
 def train_quantizer(xt, opq, d_out, M, opq_iters, pq_iters, opq_train, seed):

@@ -42,11 +42,26 @@ def get_parser():
 
 
 def parse_index_type(s):
-    """'OPQ64_1024,IVF4096,PQ64' -> (nlist, M); the OPQ block only fixes the rotation's shape (square here)."""
+    """'OPQ64_1024,IVF4096,PQ64' -> (nlist, M); the OPQ block fixes the rotation's shape (``parse_opq_block``)."""
     ivf, pq = re.search(r"IVF(\d+)", s), re.search(r"(?:^|,)PQ(\d+)", s)
     if not (ivf and pq):
         raise ValueError(f"--index-type {s!r}: only OPQ*,IVF<nlist>,PQ<M> indexes are built")
     return int(ivf.group(1)), int(pq.group(1))
+
+
+def parse_opq_block(s, hidden):
+    """The output dimension of the index type's OPQ block, ``quantize_features.parse_index``'s rule: 'OPQ16_64,IVF1048576,PQ16' -> 64
+    (the rotation reduces ``hidden`` to 64 dimensions, gnnlm_scripts/one_billion/find_knn.sh:8-21), 'OPQ64_1024,...' -> 1024, no OPQ
+    block or one without '_<d_out>' -> None (a square rotation).  d_out must divide into the PQ block's M sub-spaces and not exceed
+    ``hidden``."""
+    opq = re.search(r"OPQ(\d+)(?:_(\d+))?", s)
+    if opq is None or opq.group(2) is None:
+        return None
+    pq = re.search(r"(?:^|,)PQ(\d+)", s)
+    M, d_out = int(pq.group(1)) if pq else int(opq.group(1)), int(opq.group(2))
+    if d_out <= 0 or d_out % M or d_out > hidden:
+        raise ValueError(f"--index-type {s!r}: d_out = {d_out} must divide into {M} sub-spaces and not exceed the keys' {hidden} dimensions")
+    return d_out
 
 
 def main(args):
@@ -76,15 +91,17 @@ def main(args):
         nlist = max(1, min(nlist, ds.dstore_size // 30 or 1))                   # index_builder.py:56: at least ~30 keys per list
         index = IVFPQIndex.train(ds.keys, nlist, M, device=device, cosine=(args.metric == "cosine"), nprobe=args.nprobe,
                                  train_size=args.max_train, seed=args.seed, chunk=args.chunk_size,
-                                 opq_iters=args.opq_iters if "OPQ" in args.index_type else 0, metric="l2" if args.metric == "l2" else "ip")
+                                 opq_iters=args.opq_iters if "OPQ" in args.index_type else 0, metric="l2" if args.metric == "l2" else "ip",
+                                 d_out=parse_opq_block(args.index_type, ds.keys.shape[1]))
         index.save(trained)
     # a file that is reused fixes the index's shape; the seed and the OPQ rounds that made it are not on record in it
     want_nlist, want_M = parse_index_type(args.index_type)
     LOGGING.info("index: %d lists, PQ%d, %d of %d keys", index.nlist, index.M, index.ntotal, ds.dstore_size)
-    if index.M != want_M or index.nlist > want_nlist:
-        LOGGING.warning("the index file on disk has %d lists and PQ%d, --index-type %s asks for %d lists and PQ%d: the file wins "
-                        "(--overwrite retrains; --seed / --opq-iters of a reused file are whatever trained it)",
-                        index.nlist, index.M, args.index_type, want_nlist, want_M)
+    want_d = parse_opq_block(args.index_type, ds.keys.shape[1]) or ds.keys.shape[1]
+    if index.M != want_M or index.nlist > want_nlist or index.R.shape[0] != want_d:
+        LOGGING.warning("the index file on disk has %d lists, PQ%d and a rotation to %d dimensions, --index-type %s asks for %d lists, "
+                        "PQ%d and %d dimensions: the file wins (--overwrite retrains; --seed / --opq-iters of a reused file are "
+                        "whatever trained it)", index.nlist, index.M, index.R.shape[0], args.index_type, want_nlist, want_M, want_d)
     # every --save-every chunks the rows added so far are merged and the file rewritten (0: at the end only)
     span = args.save_every * args.chunk_size if args.save_every > 0 else max(ds.dstore_size, 1)
     while index.ntotal < ds.dstore_size:

@@ -804,6 +804,30 @@ typedef struct gnnlm_ivfpq_list_merge {
     int32_t* n_bad;
 } gnnlm_ivfpq_list_merge_t;
 int gnnlm_ivfpq_list_merge(const gnnlm_ivfpq_list_merge_t* desc, void* stream);
+/* Added within ABI 12 (additive: one entry and struct).  The COARSE step of an index with many lists without the [n, nlist] score
+ * matrix, csrc/ivfpq_coarse.hip: the k <= 64 best lists of every row of x [n, d] (row stride ldx) among coarse [nlist, d]
+ * (contiguous, 16-byte aligned), value = <x_r, c_l> (+ col_bias[l], optional), id = l.  The contract is that of
+ * gnnlm_ivfpq_select_probes applied to gnnlm_gemm_nt(x, coarse): out_val / out_id [n, k] best first, ties to the lower list, a list
+ * whose biased score is NaN or -inf is no entry, rows with fewer than k entries are padded with (-inf, -1).  The dot products are
+ * taken on the f32 matrix instruction (v_mfma_f32_16x16x4_f32), accumulated along ascending dimension from 0, the bias added after
+ * the sum is complete (one rounding each): on operands whose sums are exact in float32 the result equals the two-step route bit for
+ * bit; otherwise values differ from it in the last bits, as two GEMM routes do.
+ * The lists are cut into `slabs` >= 1 runs of ceil(nlist / slabs) rounded up to 64; a workgroup holds 64 rows and streams one
+ * slab through LDS, every row keeping the k best of its slab on chip.  slabs == 1: the result goes straight to out_val / out_id.
+ * slabs > 1: part_val [n, slabs, k] f32 and part_id [n, slabs, k] i64 (the caller's buffers) take the slabs' lists and
+ * gnnlm_topk_merge (ids = part_id, slabs * k <= 4096 columns) folds them: two launches.  No allocation, no sync.
+ * Refused with nothing written: k outside [1, 64], d <= 0 or d % 4 != 0, negative n / nlist, slabs outside [1, 4096 / k], ldx < d,
+ * and with n > 0: a null or host pointer among x, out_val, out_id, (nlist > 0) coarse, (given) col_bias, (slabs > 1) part_val /
+ * part_id, or a misaligned coarse.  n = 0 touches nothing; nlist = 0 writes the padding. */
+typedef struct gnnlm_ivfpq_coarse {
+    const float* x;  int64_t ldx;  int64_t n;
+    const float* coarse;  int32_t nlist;  int32_t d;
+    const float* col_bias;
+    int32_t k;  int32_t slabs;
+    float* part_val;  int64_t* part_id;
+    float* out_val;  int64_t* out_id;
+} gnnlm_ivfpq_coarse_t;
+int gnnlm_ivfpq_coarse_probes(const gnnlm_ivfpq_coarse_t* desc, void* stream);
 
 /* out[0] += sum_i x[i] * (mask ? mask[i] != 0 : 1), accumulated in f64 (score_sum of
  * fairseq_cli/eval_lm.py:273; the reference accumulates in f32 on the CPU) */
