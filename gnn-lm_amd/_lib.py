@@ -164,8 +164,11 @@ def lib():
                    "gnnlm_ivfpq_scan8", "gnnlm_ivfpq_rescore", "gnnlm_ivfpq_tau", "gnnlm_group_assign",
                    "gnnlm_ivfpq_tables", "gnnlm_pack_rows", "gnnlm_decode_attn", "gnnlm_sample_topk", "gnnlm_sample_topp", "gnnlm_beam_attn",
                    "gnnlm_beam_select", "gnnlm_beam_select_diverse", "gnnlm_ivfpq_select_probes", "gnnlm_ivfpq_select_final",
-                   "gnnlm_ivfpq_encode_rows", "gnnlm_ivfpq_list_merge", "gnnlm_ivfpq_coarse_probes"):
+                   "gnnlm_ivfpq_encode_rows", "gnnlm_ivfpq_list_merge", "gnnlm_ivfpq_coarse_probes",
+                   "gnnlm_ivfpq_keep_flags", "gnnlm_ivfpq_list_compact"):
             getattr(L, nm).argtypes = [vp, vp]
+        L.gnnlm_ivfpq_list_compact_workspace_bytes.restype = ctypes.c_size_t
+        L.gnnlm_ivfpq_list_compact_workspace_bytes.argtypes = [i64, i32]
         if L.gnnlm_target_arch() != b"gfx950" or L.gnnlm_abi_version() != ABI_VERSION:
             raise GnnlmError(f"libgnnlm_hip.so is not the gfx950 / ABI-{ABI_VERSION} build")
         _lib = L

@@ -35,6 +35,10 @@ int ivfpq_encode_rows(const gnnlm_ivfpq_encode_t& d, hipStream_t stream);
 int ivfpq_list_merge(const gnnlm_ivfpq_list_merge_t& d, hipStream_t stream);
 // the coarse step without the score matrix: MFMA scores, a running k-best per row on chip, slabs folded by topk_merge (ivfpq_coarse.hip)
 int ivfpq_coarse_probes(const gnnlm_ivfpq_coarse_t& d, hipStream_t stream);
+// removing keys: the rows that survive a set of id ranges, and their compaction list by list (ivfpq_remove.hip)
+int ivfpq_keep_flags(const gnnlm_ivfpq_keep_flags_t& d, hipStream_t stream);
+size_t ivfpq_list_compact_workspace_bytes(int64_t N0, int nlist);
+int ivfpq_list_compact(const gnnlm_ivfpq_list_compact_t& d, hipStream_t stream);
 
 // gemm.hip: refusals, the route (gemm_route.h), one launch
 int gemm_nt(const GemmParams& p, hipStream_t stream);

@@ -154,6 +154,7 @@ size_t gnnlm_sizeof(const char* name) {
     GNNLM_SZ(gnnlm_kv_cache_t) GNNLM_SZ(gnnlm_decode_attn_t) GNNLM_SZ(gnnlm_tlm_step_io_t) GNNLM_SZ(gnnlm_sample_topk_t) GNNLM_SZ(gnnlm_sample_topp_t)
     GNNLM_SZ(gnnlm_beam_attn_t) GNNLM_SZ(gnnlm_beam_select_t) GNNLM_SZ(gnnlm_beam_select_diverse_t) GNNLM_SZ(gnnlm_ivfpq_select_probes_t) GNNLM_SZ(gnnlm_ivfpq_select_final_t)
     GNNLM_SZ(gnnlm_ivfpq_encode_t) GNNLM_SZ(gnnlm_ivfpq_list_merge_t) GNNLM_SZ(gnnlm_ivfpq_coarse_t)
+    GNNLM_SZ(gnnlm_ivfpq_keep_flags_t) GNNLM_SZ(gnnlm_ivfpq_list_compact_t)
 #undef GNNLM_SZ
     return 0;
 }

@@ -319,8 +319,43 @@ class IVFPQIndex:
                 raise ValueError("add: one id per key")
         arrays = ivfpq_train.add_rows(self.R, self.coarse, self.pq, self.list_off, self.list_ids, self.list_codes, keys, ids,
                                       self.cosine, self.metric, chunk, self._given["coarse_route"])
+        return self._with_lists(arrays)
+
+    def _with_lists(self, arrays):
+        """a NEW index over (list_off, list_ids, list_codes) with this one's trained part and settings: the constructor derives the
+        tiles, packed codes and key terms again"""
         return type(self)(self.R, self.coarse, self.pq, *arrays, nprobe=self.nprobe, cosine=self.cosine, score_bytes=self.score_bytes,
                           metric=self.metric, **self._given)
+
+    def remove(self, ids=None, ranges=None):
+        """A NEW index without the keys whose ids are among ``ids`` (numpy / torch, any order, duplicates allowed) or inside one of
+        ``ranges`` (half-open (lo, hi) pairs: a document is one range) -- faiss's ``remove_ids``; this index is left as it is.  Ids
+        are datastore rows: the ids of the remaining keys and the label table do not change, ids the index does not hold are no
+        error, ``self.ntotal - new.ntotal`` keys were removed.  The result is, bit for bit, what ``add`` of the surviving keys in
+        their order would have built (``ivfpq_train.remove_rows``).  Removing everything gives the ``ntotal == 0`` state of
+        ``train``.  Labels are not carried over: ``attach_vals`` again."""
+        rg = ivfpq_train.normalize_ranges(ids, ranges, self.device)
+        return self._with_lists(ivfpq_train.remove_rows(self.list_off, self.list_ids, self.list_codes, rg))
+
+    def merge(self, other):
+        """A NEW index that holds this one's keys and ``other``'s (faiss's ``merge_from``): per list this one's rows, then the
+        other's -- what ``self.add(other's keys, other's ids)`` builds, without encoding anything.  Both must share one trained part
+        (``R``, ``coarse``, ``pq`` equal, the same ``cosine`` / ``metric``) and one device, else ``ValueError``.  As in ``add``,
+        ids present in both are NOT checked: such a key is then held twice.  Labels are not carried over: ``attach_vals`` again."""
+        if not isinstance(other, IVFPQIndex) or other.device != self.device:
+            raise ValueError("merge: both indexes live on one device")
+        if (self.cosine, self.metric) != (other.cosine, other.metric):
+            raise ValueError("merge: the indexes differ in cosine / metric")
+        for name in ("R", "coarse", "pq"):
+            a, b = getattr(self, name), getattr(other, name)
+            if a.shape != b.shape or not torch.equal(a, b):
+                raise ValueError(f"merge: the indexes were trained differently ({name} differs)")
+        return self._with_lists(ivfpq_train.merge_lists(self.list_off, self.list_ids, self.list_codes,
+                                                        other.list_off, other.list_ids, other.list_codes))
+
+    def replace(self, keys, ids):
+        """``remove(ids=ids).add(keys, ids)``: new keys under ids the index may already hold (a corrected document)"""
+        return self.remove(ids=ids).add(keys, ids)
 
     def save(self, path):
         arrays = dict(R=self.R, coarse=self.coarse, pq=self.pq, list_off=self.list_off, list_ids=self.list_ids, list_codes=self.list_codes)

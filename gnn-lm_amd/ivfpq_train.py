@@ -3,7 +3,8 @@ knn/index_builder.py:79-150): plain Lloyd k-means for the product quantizers, sp
 index_factory sets for inner-product indexes) for the coarse one, a random orthonormal matrix for R or OPQ rounds from it (faiss
 alternates OPQ updates; any orthonormal R gives a valid index).  Training runs on the GPU with torch ops -- offline tooling, not the
 hot path; ``quantize_features.py`` trains its feature quantizer with the same ``kmeans`` / ``train_opq``.  ADDING keys (``add_rows``:
-to an empty index for a build, to an existing one to grow it) runs on this library's kernels: csrc/ivfpq_add.hip."""
+to an empty index for a build, to an existing one to grow it) runs on this library's kernels: csrc/ivfpq_add.hip; REMOVING keys
+(``remove_rows``) and merging two indexes (``merge_lists``) on csrc/ivfpq_remove.hip and the add path's merge."""
 import os
 
 import numpy as np
@@ -200,6 +201,67 @@ def add_rows(R, coarse, pq, list_off, list_ids, list_codes, keys, ids, cosine=Tr
     new_off, dest = ops.ivfpq_list_place(assign, list_off)
     new_ids, new_codes = ops.ivfpq_list_merge(list_off, list_ids, list_codes, dest, ids, codes, new_off)
     return new_off, new_ids, new_codes
+
+
+def normalize_ranges(ids=None, ranges=None, device="cuda"):
+    """What to remove, as ``gnnlm_ivfpq_keep_flags`` reads it: i64 [n, 2] on ``device``, half-open [lo, hi) sorted by lo, pairwise
+    disjoint and not touching.  ``ids``: single ids (numpy or torch, any order, duplicates allowed), each the range [id, id + 1);
+    ``ranges``: (lo, hi) pairs in any order, lo >= hi raises ``ValueError``; overlapping and touching ranges are merged."""
+    device = torch.device(device)
+    parts = []
+    if ranges is not None:
+        r = torch.as_tensor(ranges if isinstance(ranges, torch.Tensor) else np.asarray(ranges, dtype=np.int64)).to(device, torch.int64).reshape(-1, 2)
+        if r.shape[0] and bool((r[:, 0] >= r[:, 1]).any()):
+            raise ValueError("normalize_ranges: every range needs lo < hi (half-open [lo, hi))")
+        parts.append(r)
+    if ids is not None:
+        i = torch.as_tensor(ids if isinstance(ids, torch.Tensor) else np.asarray(ids)).to(device, torch.int64).reshape(-1)
+        if i.numel() and int(i.max().item()) == torch.iinfo(torch.int64).max:
+            raise ValueError("normalize_ranges: id 2^63 - 1 has no half-open range")
+        parts.append(torch.stack([i, i + 1], 1))
+    if not parts or sum(p.shape[0] for p in parts) == 0:
+        return torch.empty(0, 2, dtype=torch.int64, device=device)
+    r = torch.cat(parts)
+    r = r[torch.sort(r[:, 0], stable=True).indices]
+    lo, hi = r[:, 0], torch.cummax(r[:, 1], 0).values                       # hi of everything that starts no later
+    first = torch.ones(r.shape[0], dtype=torch.bool, device=device)
+    first[1:] = lo[1:] > hi[:-1]                                            # a range opens where nothing before reaches it
+    last = torch.ones_like(first)
+    last[:-1] = first[1:]
+    return torch.stack([lo[first], hi[last]], 1).contiguous()
+
+
+def remove_rows(list_off, list_ids, list_codes, ranges):
+    """The list-ordered arrays without the keys whose ids lie in ``ranges`` (``normalize_ranges``) -> (new_off, ids, codes), new
+    tensors: ``gnnlm_ivfpq_keep_flags``, the cumulative sum of the lists' survivor counts, one read of the total to size the
+    outputs exactly, ``gnnlm_ivfpq_list_compact``.  Ids stay what they are (datastore rows); order inside a list is kept."""
+    device, nlist = list_off.device, list_off.numel() - 1
+    keep, list_keep = ops.ivfpq_keep_flags(list_ids, list_off, ranges)
+    new_off = torch.zeros(nlist + 1, dtype=torch.int64, device=device)
+    new_off[1:] = torch.cumsum(list_keep, 0)
+    n_bad = torch.zeros(1, dtype=torch.int32, device=device)
+    ids, codes = ops.ivfpq_list_compact(list_off, list_ids, list_codes, keep, new_off, n_bad=n_bad)
+    if int(n_bad.item()):
+        raise ValueError(f"ivfpq remove: {int(n_bad.item())} lists do not hold the survivors counted for them")
+    return new_off, ids, codes
+
+
+def merge_lists(off_a, ids_a, codes_a, off_b, ids_b, codes_b):
+    """Two sets of list-ordered arrays over the SAME lists as one -> (new_off, ids, codes): per list A's rows, then B's, both in their
+    order, through ``ops.ivfpq_list_merge`` with A as the old rows and B's row i of list l at new_off[l] + len_a[l] + (i - off_b[l])."""
+    if off_a.shape != off_b.shape or codes_a.shape[1:] != codes_b.shape[1:]:
+        raise ValueError("merge_lists: the two indexes differ in their lists or code width")
+    nlist, n_b = off_a.numel() - 1, ids_b.numel()
+    len_a, len_b = off_a[1:] - off_a[:-1], off_b[1:] - off_b[:-1]
+    new_off = torch.zeros(nlist + 1, dtype=torch.int64, device=off_a.device)
+    new_off[1:] = torch.cumsum(len_a + len_b, 0)
+    list_b = torch.repeat_interleave(torch.arange(nlist, device=off_a.device), len_b, output_size=n_b)   # the list of each row of B
+    dest = new_off[:-1][list_b] + len_a[list_b] + (torch.arange(n_b, device=off_a.device) - off_b[:-1][list_b])
+    n_bad = torch.zeros(1, dtype=torch.int32, device=off_a.device)
+    ids, codes = ops.ivfpq_list_merge(off_a, ids_a, codes_a, dest, ids_b.contiguous(), codes_b.contiguous(), new_off, n_bad=n_bad)
+    if int(n_bad.item()):
+        raise ValueError(f"ivfpq merge: {int(n_bad.item())} rows have no place (offsets that do not match the rows?)")
+    return new_off, ids, codes
 
 
 def empty_lists(nlist, M, device):

@@ -1194,6 +1194,62 @@ def ivfpq_list_merge(list_off_old, ids_old, codes_old, dest, ids_new, codes_new,
     return ids, codes
 
 
+def ivfpq_keep_flags(list_ids, list_off, ranges):
+    """Which rows of an index survive the removal of id ranges (gnnlm_ivfpq_keep_flags): list_ids [N] i64, list_off [nlist + 1] i64,
+    ranges [n, 2] i64 half-open [lo, hi), sorted by lo and pairwise disjoint (``ivfpq_train.normalize_ranges``), all on the device
+    -> (keep [N] u8: 1 survives, list_keep [nlist] i64: survivors per list)."""
+    _dev(list_ids, list_off, ranges)
+    for t, what in ((list_ids, "list_ids"), (list_off, "list_off"), (ranges, "ranges")):
+        _dtype(t, torch.int64, what)
+    N, nlist = list_ids.numel(), list_off.numel() - 1
+    if (list_ids.dim() != 1 or list_off.dim() != 1 or nlist < 0 or ranges.dim() != 2 or ranges.shape[1] != 2
+            or not (list_ids.is_contiguous() and list_off.is_contiguous() and ranges.is_contiguous())):
+        raise ValueError("ivfpq_keep_flags: list_ids [N], list_off [nlist + 1], ranges [n, 2], contiguous")
+    keep = torch.empty(N, dtype=torch.uint8, device=list_ids.device)
+    list_keep = torch.empty(nlist, dtype=torch.int64, device=list_ids.device)
+    f = _lib.gnnlm_ivfpq_keep_flags_t()
+    f.ids, f.N, f.list_off, f.nlist = list_ids.data_ptr(), N, list_off.data_ptr(), nlist
+    f.ranges, f.n_ranges = ranges.data_ptr() if ranges.shape[0] else None, ranges.shape[0]
+    f.keep, f.list_keep = keep.data_ptr(), list_keep.data_ptr()
+    call_desc("gnnlm_ivfpq_keep_flags", f)
+    return keep, list_keep
+
+
+def ivfpq_list_compact(list_off_old, ids_old, codes_old, keep, new_off, n_bad=None):
+    """The rows with keep != 0 of the list-ordered arrays, list by list in their order (gnnlm_ivfpq_list_compact): new_off
+    [nlist + 1] is the cumulative sum of ``ivfpq_keep_flags``'s list_keep.  -> (ids [n] i64, codes [n, M] u8), new buffers of
+    n = new_off[-1] rows (one read of that number).  n_bad [1] i32 is incremented per list whose survivors are not
+    new_off[l + 1] - new_off[l]."""
+    _dev(list_off_old, ids_old, codes_old, keep, new_off, n_bad)
+    for t, what in ((list_off_old, "list_off_old"), (ids_old, "ids_old"), (new_off, "new_off")):
+        _dtype(t, torch.int64, what)
+    _dtype(codes_old, torch.uint8, "codes_old"), _dtype(keep, torch.uint8, "keep"), _dtype(n_bad, torch.int32, "n_bad")
+    N0, nlist = ids_old.numel(), new_off.numel() - 1
+    M = codes_old.shape[1] if codes_old.dim() == 2 else -1
+    if (ids_old.dim() != 1 or codes_old.shape != (N0, M) or keep.shape != (N0,) or nlist < 0 or list_off_old.shape != (nlist + 1,)
+            or new_off.dim() != 1 or not (codes_old.is_contiguous() and ids_old.is_contiguous() and keep.is_contiguous()
+                                          and list_off_old.is_contiguous() and new_off.is_contiguous())):
+        raise ValueError("ivfpq_list_compact: ids_old / keep [N0], codes_old [N0, M], offsets [nlist + 1], contiguous")
+    n = int(new_off[-1].item()) if N0 and nlist > 0 else 0
+    if n < 0 or n > N0:
+        raise ValueError(f"ivfpq_list_compact: new_off ends at {n}, the index has {N0} rows")
+    ids = torch.empty(n, dtype=torch.int64, device=new_off.device)
+    codes = torch.empty(n, M, dtype=torch.uint8, device=new_off.device)
+    ws_bytes = _lib.lib().gnnlm_ivfpq_list_compact_workspace_bytes(N0, nlist)
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.int64, device=new_off.device)
+    out_ids = ids if n else torch.empty(1, dtype=torch.int64, device=new_off.device)         # (never written: the entry wants pointers)
+    out_codes = codes if n else torch.empty(1, max(M, 16), dtype=torch.uint8, device=new_off.device)
+    c = _lib.gnnlm_ivfpq_list_compact_t()
+    c.list_off_old, c.nlist, c.N0 = list_off_old.data_ptr(), nlist, N0
+    c.ids_old, c.codes_old, c.M, c.keep = ids_old.data_ptr(), codes_old.data_ptr(), M, keep.data_ptr()
+    c.new_off, c.ids, c.codes = new_off.data_ptr(), out_ids.data_ptr(), out_codes.data_ptr()
+    if n_bad is not None:
+        c.n_bad = n_bad.data_ptr()
+    c.workspace, c.workspace_bytes = ws.data_ptr(), ws_bytes
+    call_desc("gnnlm_ivfpq_list_compact", c)
+    return ids, codes
+
+
 def ivfpq_quantize_lut(lut, M=64):
     """lut [n, M * 256] f32 -> (qlut [n, 2, 256, 32] u8, qmeta [n, 4] f32 = {delta, sum_m lo_m, max |lut|, 0}) with
     lut[m][c] < lo_m + (u + 1) * delta for every entry, u = qlut[m // 32][c][m % 32] ^ 0x80 (the table stores the signed

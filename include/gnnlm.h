@@ -828,6 +828,47 @@ typedef struct gnnlm_ivfpq_coarse {
     float* out_val;  int64_t* out_id;
 } gnnlm_ivfpq_coarse_t;
 int gnnlm_ivfpq_coarse_probes(const gnnlm_ivfpq_coarse_t* desc, void* stream);
+/* Added within ABI 12 (additive: two structs, three entries).  REMOVING keys from an index (faiss `remove_ids`), csrc/ivfpq_remove.hip.
+ * Ids are datastore rows, so the ids of the remaining keys and the label table stay as they are: only the three list arrays shrink.
+ * Both entries only enqueue (no allocation, no sync), address rows and bytes with 64 bits, and refuse bad shapes with
+ * GNNLM_E_INVALID and nothing written.
+ *
+ * gnnlm_ivfpq_keep_flags: which rows survive.  ids [N] are the index's list_ids, list_off [nlist + 1] its offsets, ranges a DEVICE
+ * array [n_ranges][2] of half-open id ranges [lo, hi), sorted by lo, pairwise disjoint, lo < hi (one id: [id, id + 1)).
+ * keep[s] = 0 if some range holds ids[s], else 1 (bisection of the ranges); list_keep [nlist] (optional) = survivors per list,
+ * WRITTEN, not incremented (zeroed by a launch of its own, then integer atomics: no dependence on launch order).  n_ranges = 0 keeps
+ * everything; ids that the index does not hold are no error; ranges that break the precondition give unspecified flags and never an
+ * access outside the arrays.  N = 0 writes list_keep = 0 and nothing else; nlist = 0 (with N = 0) touches nothing.  Refused:
+ * negative sizes, N > 0 with nlist = 0 or a null ids / list_off / keep, n_ranges > 0 with null ranges. */
+typedef struct gnnlm_ivfpq_keep_flags {
+    const int64_t* ids;  int64_t N;
+    const int64_t* list_off;  int32_t nlist;
+    const int64_t* ranges;  int64_t n_ranges;
+    uint8_t* keep;  int64_t* list_keep;
+} gnnlm_ivfpq_keep_flags_t;
+int gnnlm_ivfpq_keep_flags(const gnnlm_ivfpq_keep_flags_t* desc, void* stream);
+/* gnnlm_ivfpq_list_compact: the surviving rows (keep[s] != 0) of list_off_old [nlist + 1], ids_old [N0], codes_old [N0, M] into ids
+ * and codes, buffers of their own with at least new_off[nlist] rows; new_off [nlist + 1] is the cumulative sum of list_keep, made by
+ * the caller.  The survivor of list l with r survivors of that list ahead of it lands at new_off[l] + r: order inside a list and the
+ * order of the lists are kept; rows from new_off[nlist] on are not touched.  A list whose survivor count differs from
+ * new_off[l + 1] - new_off[l] is counted once in n_bad (optional) and writes nothing outside [new_off[l], new_off[l + 1]).  The
+ * result is a pure function of the inputs (no dependence on the grid, on other work or on list lengths): the positions come from a
+ * scan in separate launches over chunks of 1024 rows (count, one-workgroup scan of the counts, scatter), never from one workgroup
+ * waiting for another.  `workspace`: gnnlm_ivfpq_list_compact_workspace_bytes(N0, nlist) bytes of device memory, 8-byte aligned,
+ * contents free.  M % 16 == 0, codes_old and codes 16-byte aligned (rows move as 16-byte pieces, ids as 8 bytes).  N0 = 0 touches
+ * nothing.  Refused: M % 16 != 0, negative sizes, N0 > 0 with nlist = 0, and with N0 > 0 a null operand, a misaligned codes pointer,
+ * an output that is an input, or a workspace that is null, misaligned or too small. */
+typedef struct gnnlm_ivfpq_list_compact {
+    const int64_t* list_off_old;  int32_t nlist;  int64_t N0;
+    const int64_t* ids_old;  const uint8_t* codes_old;  int32_t M;
+    const uint8_t* keep;
+    const int64_t* new_off;
+    int64_t* ids;  uint8_t* codes;
+    int32_t* n_bad;
+    void* workspace;  size_t workspace_bytes;
+} gnnlm_ivfpq_list_compact_t;
+size_t gnnlm_ivfpq_list_compact_workspace_bytes(int64_t N0, int32_t nlist);
+int gnnlm_ivfpq_list_compact(const gnnlm_ivfpq_list_compact_t* desc, void* stream);
 
 /* out[0] += sum_i x[i] * (mask ? mask[i] != 0 : 1), accumulated in f64 (score_sum of
  * fairseq_cli/eval_lm.py:273; the reference accumulates in f32 on the CPU) */
