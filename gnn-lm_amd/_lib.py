@@ -157,6 +157,10 @@ def lib():
         L.gnnlm_hgt_forward.argtypes = [vp, vp, vp, ctypes.c_size_t, vp]
         L.gnnlm_hgt_workspace_bytes_ragged.argtypes = [vp, vp, vp]
         L.gnnlm_hgt_forward_ragged.argtypes = [vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.gnnlm_hgt_prefill.argtypes = [vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.gnnlm_hgt_step_workspace_bytes.restype = ctypes.c_size_t
+        L.gnnlm_hgt_step_workspace_bytes.argtypes = [vp, vp, vp, i32]
+        L.gnnlm_hgt_step.argtypes = [vp, vp, vp, i32, vp, ctypes.c_size_t, vp]
         L.gnnlm_ragged_tiles.argtypes = [vp, i32, vp]
         L.gnnlm_causal_attn_varlen.argtypes = [vp, vp, vp, i64, vp, i64, vp, i32, i32, i32, vp]
         for nm in ("gnnlm_gemm_nt", "gnnlm_pq_gather_decode", "gnnlm_token_gather", "gnnlm_star_attn", "gnnlm_chain_attn",

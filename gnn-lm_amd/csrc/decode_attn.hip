@@ -198,7 +198,7 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(DecParams p) {
 }
 
 struct FillParams {
-    const float* src; int64_t ld_src;      // the q | k | v rows [n_tok, ld_src]; K' at column d, V' at column 2 d
+    const float *k, *v; int64_t ld_src;    // the K' and V' rows [n_tok, ld_src] of the packed tokens
     float *kc, *vc; int64_t ld_row, ld_seq;
     const int32_t* block_off; int n_blocks; int64_t n_tok;
     int d4, max_rows;
@@ -212,8 +212,8 @@ __global__ __launch_bounds__(256) void kv_cache_fill_kernel(FillParams p) {
     const int lo = last_block(p.block_off, p.n_blocks, r, base);
     const int64_t t = r - ((int64_t)p.block_off[lo] - base);
     if (t < 0 || t >= p.max_rows) return;                  // (the host refused a block longer than the cache: memory safety only)
-    const float4* ks = reinterpret_cast<const float4*>(p.src + r * p.ld_src) + p.d4;
-    const float4* vs = ks + p.d4;
+    const float4* ks = reinterpret_cast<const float4*>(p.k + r * p.ld_src);
+    const float4* vs = reinterpret_cast<const float4*>(p.v + r * p.ld_src);
     float4* kd = reinterpret_cast<float4*>(p.kc + lo * p.ld_seq + t * p.ld_row);
     float4* vd = reinterpret_cast<float4*>(p.vc + lo * p.ld_seq + t * p.ld_row);
     for (int e = lane; e < p.d4; e += 64) {
@@ -303,10 +303,10 @@ int decode_attn(const gnnlm_decode_attn_t& d, const SlotTable* tab, hipStream_t 
     return OK;
 }
 
-int kv_cache_fill(const float* qkv, int64_t ld_src, const gnnlm_kv_cache_t& c, int layer, const gnnlm_ragged_t& rg, int max_rows,
-                  hipStream_t stream) {
+int kv_cache_fill(const float* k, const float* v, int64_t ld_src, const gnnlm_kv_cache_t& c, int layer, const gnnlm_ragged_t& rg,
+                  int max_rows, hipStream_t stream) {
     if (rg.n_tok == 0) return OK;
-    FillParams p{qkv, ld_src, c.k + layer * c.ld_layer, c.v + layer * c.ld_layer, c.ld_row, c.ld_seq, rg.block_off, rg.n_blocks, rg.n_tok,
+    FillParams p{k, v, ld_src, c.k + layer * c.ld_layer, c.v + layer * c.ld_layer, c.ld_row, c.ld_seq, rg.block_off, rg.n_blocks, rg.n_tok,
                  c.d / 4, max_rows};
     ProfScope prof(K_MISC, stream, 0.0, 16.0 * rg.n_tok * c.d);
     hipLaunchKernelGGL(kv_cache_fill_kernel, dim3((unsigned)cdiv(rg.n_tok, 4)), dim3(256), 0, stream, p);

@@ -1,7 +1,8 @@
 // The HGT forward over the implicit token / neighbour graph (include/gnnlm.h: gnnlm_hgt_forward, gnnlm_hgt_forward_ragged and their
 // workspace sizes).  The orchestrator only enqueues kernels on the given stream (no allocation, no synchronisation), so a caller may
 // capture it into a hipGraph.  hgt_forward_impl at the end of the file is the table of contents: plan, carve, validate, the layer-0
-// ntgt states, then per layer the tgt update and the ntgt update.
+// ntgt states, then per layer the tgt update and the ntgt update.  gnnlm_hgt_prefill and gnnlm_hgt_step are the same loop with a
+// K' / V' cache: the prefill copies every layer's rows into it, the step runs its causal branch against it (decode_attn.hip).
 #include "host.h"
 
 namespace gnnlm {
@@ -29,6 +30,9 @@ bool row_keyed_kv(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io) {
 // it on descriptors that nobody has checked.
 struct HgtPlan {
     const gnnlm_hgt_t& m;  const gnnlm_hgt_io_t& io;  const gnnlm_ragged_t* rg;
+    // the incremental entries: the K' / V' cache that gnnlm_hgt_prefill (with rg) fills and gnnlm_hgt_step (without) decodes
+    // against, and the step's host bound on len[b] + 1
+    const gnnlm_kv_cache_t* kv = nullptr;  const int step_len = 0;
     const int d = m.d, H = m.n_heads, dk = H > 0 ? d / H : 0, T = io.T, kg = io.kg, nb = io.n_blocks, n_g = 1 + m.left + m.right, L = m.n_layers;
     const bool dense0 = io.ntgt_feats != nullptr;       // layer-0 ntgt states given (input adapters): no code store
     // `--reinit-nfeat`: ntgt features = rows of the token-embedding table (transformer.py:1046-1048); explicit layer-0 states win
@@ -40,8 +44,11 @@ struct HgtPlan {
     const bool cached = io.state_cache != nullptr;
     const int32_t* gdev = io.n_unique_dev;      // ABI 9: the number of groups lives on the device; n_unique is then the capacity of the group arrays
     const bool ragged = rg != nullptr;          // gnnlm_hgt_forward_ragged: the packed tokens are one run of io.T rows, cut into blocks by rg
+    const bool step = kv != nullptr && !ragged; // gnnlm_hgt_step: one new row per block, the causal branch is decode_attn -> HgtBufs.mc
     // the causal branch in one kernel that adds itself into the message sum: the recipe shape's, or the varlen one
-    const bool fusedc = ragged || causal_attn_fused_ok(T, dk);
+    const bool fusedc = !step && (ragged || causal_attn_fused_ok(T, dk));
+    const bool rowv = fusedc || step;           // V' row-major beside q and K' (the GEMM path wants V'^T instead)
+    const size_t attn_bytes = step ? decode_attn_workspace_bytes(nb, H, dk, step_len) : 0;
     const int dpq = (dense0 || token) ? d : m.M * m.dsub;       // width of layer 0's neighbour rows
     // the carve's own rule for that width: it does not look at ntgt_feats, so with dense layer-0 states on a model with M * dsub > d
     // it over-allocates U, Z and the slot buffers.  Kept: workspace sizes are something callers see
@@ -62,6 +69,7 @@ struct HgtPlan {
 struct HgtBufs {
     // tgt side
     float *q, *k, *vt, *scores, *mc, *U, *Z, *ms, *aout, *has_nb;
+    char* attn_ws;                   // gnnlm_hgt_step: the chunk partials of decode_attn (HgtPlan.attn_bytes)
     // ntgt side
     float *nq, *nk, *nv;
     uint8_t* valid;
@@ -90,9 +98,10 @@ void carve_hgt(const HgtPlan& p, Carver& c, HgtBufs& b, HgtState& st) {
     b = HgtBufs{};
     st.ht[0] = c.take<float>(Tt * d);
     st.ht[1] = c.take<float>(Tt * d);
-    if (p.ragged) {
+    if (p.ragged || p.step) {
         // packed blocks of unequal length: q | k' | v' row-major back to back (one 3d-wide GEMM writes them whatever the token
         // count), no V^T and no [n_blocks, H, T, T] score buffer -- the varlen kernel keeps one tile of scores in registers
+        // (the step: the new rows' q | k' | v' the same way, for decode_attn)
         b.q = c.take<float>(3 * Tt * d);
         b.k = b.q + Tt * d;
         b.vt = b.k + Tt * d;
@@ -108,6 +117,7 @@ void carve_hgt(const HgtPlan& p, Carver& c, HgtBufs& b, HgtState& st) {
     b.ms = c.take<float>(Tt * d);
     b.aout = c.take<float>(Tt * d);
     b.has_nb = c.take<float>(Tt);
+    if (p.step) b.attn_ws = c.take<char>((int64_t)p.attn_bytes);
     b.win_counts = p.gdev ? c.take<int32_t>(MAX_WINDOWS * 8) : nullptr;
     b.nb_row = p.nb_row ? c.take<int32_t>(Tt * p.kg) : nullptr;
     // token store: the labels live in aout when they fit (k_g <= d: every recipe; invariant (1) of HgtBufs), so that a one-layer
@@ -132,11 +142,12 @@ void carve_hgt(const HgtPlan& p, Carver& c, HgtBufs& b, HgtState& st) {
     b.xu = c.take<float>(S * dpq);
 }
 
-size_t hgt_workspace_bytes(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, const gnnlm_ragged_t* rg) {
+size_t hgt_workspace_bytes(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, const gnnlm_ragged_t* rg, const gnnlm_kv_cache_t* kv = nullptr,
+                           int step_len = 0) {
     Carver c(nullptr);
     HgtBufs b;
     HgtState st;
-    carve_hgt(HgtPlan{m, io, rg}, c, b, st);
+    carve_hgt(HgtPlan{m, io, rg, kv, step_len}, c, b, st);
     return c.off + 256;
 }
 
@@ -241,6 +252,28 @@ int HgtPlan::validate(const void* ws, const Carver& c) const {
     GNNLM_REQUIRE(!rg || (nb == 1 && rg->n_tok == Tt && rg->n_blocks >= 1 && rg->block_off && rg->tiles),
                   "hgt: a ragged batch needs io.n_blocks == 1, io.T == blocks.n_tok and the block / tile tables");
     GNNLM_REQUIRE(!rg || causal_attn_varlen_ok(dk), "hgt: ragged batches need d / n_heads in {16, 32, 64, 128}");
+    if (kv) {
+        // everything decode_attn would refuse in the middle of the layer loop is refused here, in front of the first launch
+        GNNLM_TRY(check_kv_cache(*kv));
+        GNNLM_REQUIRE(decode_attn_ok(dk), "hgt: a K/V cache needs d / n_heads in {16, 32, 64, 128}");
+        GNNLM_REQUIRE(kv->d == d, "hgt: cache->d != model->d");
+        GNNLM_REQUIRE(kv->L == m.n_layers, "hgt: cache->L != model->n_layers");
+    }
+    if (kv && rg) {
+        GNNLM_REQUIRE(rg->n_blocks == kv->B, "hgt_prefill: blocks->n_blocks != cache->B");
+        // the longest block holds at least ceil(n_tok / n_blocks) rows: what the host knows of max_len without reading the table
+        GNNLM_REQUIRE(cdiv(rg->n_tok, (int64_t)rg->n_blocks) <= kv->cap, "hgt_prefill: a block is longer than the cache (max_len > cache->cap)");
+    }
+    if (step) {
+        GNNLM_REQUIRE(io.T == 1, "hgt_step: io->T must be 1 (one new row per block)");
+        GNNLM_REQUIRE(io.n_blocks == kv->B, "hgt_step: io->n_blocks != cache->B");
+        GNNLM_REQUIRE(m.max_intra_context <= 0, "hgt_step: model->max_intra_context > 0 is not built (the decode kernel has no window)");
+        GNNLM_REQUIRE(!io.ntgt_feats, "hgt_step: io->ntgt_feats (input adapters) is not built");
+        GNNLM_REQUIRE(!io.fetched_codes && !m.shards, "hgt_step: io->fetched_codes / model->shards (sharded and peer stores) are not built");
+        GNNLM_REQUIRE(!m.token_embed, "hgt_step: model->token_embed (--reinit-nfeat) is not built");
+        GNNLM_REQUIRE(!io.out_ntgt && !io.out_valid, "hgt_step: io->out_ntgt / io->out_valid are not built");
+        GNNLM_REQUIRE(step_len >= 1 && step_len <= kv->cap, "hgt_step: max_len outside [1, cache->cap] (the cache is full)");
+    }
     GNNLM_REQUIRE(ws && c.fits(), "hgt: workspace too small (see gnnlm_hgt_workspace_bytes)");
     for (int l = 0; l < m.n_layers; ++l) {
         const gnnlm_hgt_layer_t& w = m.layers[l];
@@ -341,7 +374,7 @@ struct HgtForward {
         const int d = p.d;
         const int64_t Tt = p.Tt;
         o = TgtQkv{b.q, b.k, b.vt, d};
-        const bool qkv_one = p.fusedc && w.bq_t && w.wk_t == w.wq_t + (int64_t)d * d &&
+        const bool qkv_one = p.rowv && w.bq_t && w.wk_t == w.wq_t + (int64_t)d * d &&
                              w.wv_t == w.wk_t + (int64_t)d * d && w.bk_t == w.bq_t + d && w.bv_t == w.bk_t + d &&
                              b.k == b.q + Tt * d && b.vt == b.k + Tt * d;
         if (qkv_one) {
@@ -354,8 +387,20 @@ struct HgtForward {
         GNNLM_TRY(linear(st.ht_in, d, w.wk_t, w.bk_t, b.k, Tt, d, d, nullptr, 1.f, s));
         // recipe shape: V' row-major, then scores + masked softmax + P.V in one kernel (causal_attn.hip)
         // (the kernel itself runs after the star branch and adds its result into the message sum, see tgt_output)
-        if (p.fusedc) GNNLM_TRY(linear(st.ht_in, d, w.wv_t, w.bv_t, b.vt, Tt, d, d, nullptr, 1.f, s));
+        if (p.rowv) GNNLM_TRY(linear(st.ht_in, d, w.wv_t, w.bv_t, b.vt, Tt, d, d, nullptr, 1.f, s));
         return OK;
+    }
+
+    // (c') gnnlm_hgt_step's causal branch: the new row of every block against the layer's cached K' / V' rows -> b.mc.  q is used
+    // as given -- the scale is folded into K' -- and the new K' / V' rows are appended to the cache by the same kernel
+    int causal_step(const TgtQkv& qkv, int l) const {
+        gnnlm_decode_attn_t a{};
+        a.q = qkv.q; a.k_new = qkv.k; a.v_new = qkv.v; a.ld = qkv.ld;
+        a.out = b.mc; a.ldo = p.d;
+        a.cache = *p.kv; a.layer = l; a.H = p.H; a.dk = p.dk; a.max_len = p.step_len;
+        a.workspace = b.attn_ws; a.workspace_bytes = p.attn_bytes;
+        if (l > 0) a.cache.n_bad = nullptr;                 // a row out of range is counted once per step, not once per layer
+        return decode_attn(a, nullptr, s);
     }
 
     // (c) the causal branch as GEMMs: V'^T, scores, masked softmax, P.V -> b.mc
@@ -522,9 +567,12 @@ struct HgtForward {
     }
 };
 
-int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, size_t ws_bytes, hipStream_t s, const gnnlm_ragged_t* rg = nullptr) {
+// kv with rg: gnnlm_hgt_prefill, the ragged forward whose K' / V' rows also go to the cache.  kv without rg: gnnlm_hgt_step, one new
+// row per block whose causal branch reads the cache (step_len: the host's bound on len[b] + 1).
+int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, size_t ws_bytes, hipStream_t s, const gnnlm_ragged_t* rg = nullptr,
+                     const gnnlm_kv_cache_t* kv = nullptr, int step_len = 0) {
     // plan and carve are arithmetic only: nothing is read through a pointer or enqueued before the checks have passed
-    const HgtPlan p{m, io, rg};
+    const HgtPlan p{m, io, rg, kv, step_len};
     HgtBufs b;
     HgtState st;
     Carver c(ws, ws_bytes);
@@ -539,7 +587,7 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
     // (cached groups have no slot rows in this call, a one-layer model has none at all)
     if (p.token) GNNLM_TRY(neighbor_labels(io.ids, p.Tt * p.kg, m.n_store, m.vals, m.vals_itemsize, m.n_vocab, b.nb_label, s));
     // V^T buffer of the GEMM path: its padding columns (t >= T) are read by the P.V GEMM against zero probabilities
-    if (!p.fusedc) GNNLM_HIP(hipMemsetAsync(b.vt, 0, sizeof(float) * (size_t)p.nb * p.d * p.Tp, s));
+    if (!p.rowv) GNNLM_HIP(hipMemsetAsync(b.vt, 0, sizeof(float) * (size_t)p.nb * p.d * p.Tp, s));
 
     st.ht_in = io.tgt_feats;
     for (int l = 0; l < m.n_layers; ++l) {
@@ -547,13 +595,18 @@ int hgt_forward_impl(const gnnlm_hgt_t& m, const gnnlm_hgt_io_t& io, void* ws, s
         float* ht_out = l == m.n_layers - 1 ? io.out_tgt : st.ht[l & 1];
         TgtQkv qkv;
         GNNLM_TRY(f.tgt_projections(st, w, qkv));
-        if (!p.fusedc) GNNLM_TRY(f.causal_unfused(st, w));
+        // prefill: the block's K' / V' rows are rows [0, len_b) of its sequence in this layer of the cache
+        if (kv && rg) GNNLM_TRY(kv_cache_fill(qkv.k, qkv.v, qkv.ld, *kv, l, *rg, kv->cap, s));
+        if (p.step) GNNLM_TRY(f.causal_step(qkv, l));
+        else if (!p.fusedc) GNNLM_TRY(f.causal_unfused(st, w));
         GNNLM_TRY(f.star_branch(st, l, qkv));
         GNNLM_TRY(f.tgt_output(st, w, qkv, ht_out));
         const NtgtStep t = ntgt_step(p, l);
         if (t.run) GNNLM_TRY(f.ntgt_update(st, l, t));
         st.ht_in = ht_out;
     }
+    if (kv && rg) GNNLM_TRY(kv_len_set(*kv, rg->block_off, kv->cap, s));
+    if (p.step) GNNLM_TRY(kv_len_advance(*kv, step_len, s));
     return OK;
 }
 
@@ -582,6 +635,24 @@ int gnnlm_hgt_forward_ragged(const gnnlm_hgt_t* m, const gnnlm_hgt_io_t* io, con
     GNNLM_DESC(io);
     GNNLM_DESC(blocks);
     return hgt_forward_impl(*m, *io, workspace, workspace_bytes, (hipStream_t)stream, blocks);
+}
+int gnnlm_hgt_prefill(const gnnlm_hgt_t* m, const gnnlm_hgt_io_t* io, const gnnlm_ragged_t* blocks, const gnnlm_kv_cache_t* cache,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    GNNLM_DESC(m);
+    GNNLM_DESC(io);
+    GNNLM_DESC(blocks);
+    GNNLM_DESC(cache);
+    return hgt_forward_impl(*m, *io, workspace, workspace_bytes, (hipStream_t)stream, blocks, cache);
+}
+size_t gnnlm_hgt_step_workspace_bytes(const gnnlm_hgt_t* m, const gnnlm_hgt_io_t* io, const gnnlm_kv_cache_t* cache, int32_t max_len) {
+    return !m || !io || !cache ? 0 : hgt_workspace_bytes(*m, *io, nullptr, cache, max_len);
+}
+int gnnlm_hgt_step(const gnnlm_hgt_t* m, const gnnlm_hgt_io_t* io, const gnnlm_kv_cache_t* cache, int32_t max_len, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+    GNNLM_DESC(m);
+    GNNLM_DESC(io);
+    GNNLM_DESC(cache);
+    return hgt_forward_impl(*m, *io, workspace, workspace_bytes, (hipStream_t)stream, nullptr, cache, max_len);
 }
 
 }  // extern "C"

@@ -144,9 +144,9 @@ int decode_attn(const gnnlm_decode_attn_t& d, const SlotTable* tab, hipStream_t 
 // one beam-search step of every sentence (beam.hip)
 int beam_select(const gnnlm_beam_select_t& d, hipStream_t stream);
 int beam_select_diverse(const gnnlm_beam_select_diverse_t& d, hipStream_t stream);
-// K' | V' of the packed q | k | v rows [n_tok, ld_src] -> cache rows [0, min(len_b, max_rows)) of sequence b = block b of `layer`
-int kv_cache_fill(const float* qkv, int64_t ld_src, const gnnlm_kv_cache_t& c, int layer, const gnnlm_ragged_t& rg, int max_rows,
-                  hipStream_t stream);
+// the K' and V' rows [n_tok, ld_src] of the packed tokens -> cache rows [0, min(len_b, max_rows)) of sequence b = block b of `layer`
+int kv_cache_fill(const float* k, const float* v, int64_t ld_src, const gnnlm_kv_cache_t& c, int layer, const gnnlm_ragged_t& rg,
+                  int max_rows, hipStream_t stream);
 // len[b] = min(block_off[b + 1] - block_off[b], max_rows);  len[b] += 1 for rows that are not done and hold 0 <= len[b] < bound
 int kv_len_set(const gnnlm_kv_cache_t& c, const int32_t* block_off, int max_rows, hipStream_t stream);
 int kv_len_advance(const gnnlm_kv_cache_t& c, int bound, hipStream_t stream);

@@ -256,7 +256,7 @@ int tlm_forward(const gnnlm_tlm_t& m, const gnnlm_tlm_io_t& io, void* ws, size_t
 
     GNNLM_TRY(launch_embed(embed_of(m, io, b.x), rg, s));
     const auto attn = [&](int l) {
-        if (cache) GNNLM_TRY(kv_cache_fill(b.wide, 3 * (int64_t)d, *cache, l, rg, (int)io.max_len, s));
+        if (cache) GNNLM_TRY(kv_cache_fill(b.wide + d, b.wide + 2 * d, 3 * (int64_t)d, *cache, l, rg, (int)io.max_len, s));
         return causal_attn_varlen(b.wide, b.wide + d, b.wide + 2 * d, 3 * (int64_t)d, b.a, d, rg, m.H, d / m.H, 0, s);
     };
     GNNLM_TRY(tlm_layers(m, n, b, io, attn, s));

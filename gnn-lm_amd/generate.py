@@ -54,10 +54,15 @@ class Generator:
         self.vocab = head_vocab(lm.head)
         self._cool = {}
 
+    @property
+    def head(self):
+        """The output layer the picks are made from (``generate_gnn.GnnGenerator``: the GNN-LM's)."""
+        return self.lm.head
+
     def _head(self, temperature):
         """The head that gives log_softmax(decoder_out / temperature) of rows ALREADY divided by it: itself, or -- the plain output
         layer with a bias -- a twin whose bias is divided too."""
-        head = self.lm.head
+        head = self.head
         if temperature == 1.0 or getattr(head, "bias", None) is None:
             return head
         if temperature not in self._cool:
@@ -113,6 +118,21 @@ class Generator:
             cache.spread(into)
         return cache, tokens, lens, x, extra, last, want_ffn
 
+    # the two places where the loop of generate() meets the model: generate_gnn.GnnGenerator puts the graph decoder behind them
+    def _start(self, prompts, max_new):
+        """Prefill -> ``(cache, x, extra)``: the base LM's cache and the rows the first pick is made from."""
+        cache, _, _, x, extra, last, self._want_ffn = self.prefill(prompts, max_new - 1)
+        x, extra = gen_common.last_rows(x, extra, last)
+        return cache, x, extra
+
+    def _advance(self, nxt, cache):
+        """Append the picks -> ``(x, extra)`` of the new rows."""
+        return self.lm.step(nxt, cache, want_ffn_input=self._want_ffn)
+
+    def _out_of_range(self, cache):
+        """Rows that left a cache's range, over the whole run (one read at the end)."""
+        return int(cache.n_bad.item())
+
     def generate(self, prompts, max_new, sampling=False, sampling_topk=-1, temperature=1.0, unk_penalty=0.0, seed=None, sampling_topp=-1.0):
         """prompts: a list of non-empty lists of token ids, fed as they are -> ``(tokens int64 [B, max_new], logp f32 [B, max_new],
         lengths int64 [B])`` on the device: row b's continuation is ``tokens[b, :lengths[b]]`` (its ``eos`` included when it came), ``pad``
@@ -121,8 +141,7 @@ class Generator:
         lm, dev = self.lm, self.lm.device
         k = self.check(max_new, sampling, sampling_topk, float(temperature), self.vocab, float(sampling_topp))
         topp = float(sampling_topp) if sampling and sampling_topp > 0 else 0.0
-        cache, _, _, x, extra, last, want_ffn = self.prefill(prompts, max_new - 1)
-        x, extra = gen_common.last_rows(x, extra, last)
+        cache, x, extra = self._start(prompts, max_new)
         B = len(prompts)
         out = torch.full((B, max_new), PAD, dtype=torch.int64, device=dev)
         out_lp = torch.zeros(B, max_new, dtype=torch.float32, device=dev)
@@ -155,9 +174,9 @@ class Generator:
             out_lp[:, t] = nxt_lp
             if t == max_new - 1 or ((t + 1) % DONE_EVERY == 0 and bool(cache.done.all())):
                 break
-            x, extra = lm.step(nxt, cache, want_ffn_input=want_ffn)
+            x, extra = self._advance(nxt, cache)
         lm.check_tokens()
-        if int(n_bad.item()) or int(cache.n_bad.item()):
+        if int(n_bad.item()) or self._out_of_range(cache):
             raise RuntimeError("generate: a row had nothing to pick from (non-finite log-probabilities) or left the cache's range")
         if topp:
             total, picks = (int(v) for v in keep_sum.tolist())

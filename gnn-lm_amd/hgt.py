@@ -302,7 +302,8 @@ class CentreStateCache:
 
 
 class HGT(nn.Module):
-    """Drop-in for ``HGT`` of fairseq/models/hgt.py:459-513 (eval forward, non-incremental)."""
+    """Drop-in for ``HGT`` of fairseq/models/hgt.py:459-513 (eval forward, non-incremental); incremental decoding -- what
+    ``HGTLayer.infer`` (:81-297) sketches -- is :meth:`new_cache` / :meth:`prefill` / :meth:`step`."""
 
     def __init__(self, ntype2idx=None, etype2idx=None, in_dim=1024, hidden_dim=1024, out_dim=1024, n_layers=3,
                  n_heads=8, use_norm=True, dropout=0.0, two_stream=False, attn_drop=0.0):
@@ -491,6 +492,81 @@ class HGT(nn.Module):
         order when ``return_ntgt``; the eval path never consumes it, transformer.py:1053)."""
         if incremental_state is not None:
             raise NotImplementedError("incremental decoding (HGTLayer.infer) is out of scope (generation only)")
+        return self._run(G, features, return_ntgt)
+
+    def new_cache(self, B, cap, done=None, device=None):
+        """An empty K' / V' cache for ``B`` sequences of up to ``cap`` tokens (``gnnlm_kv_cache_t`` with L = n_layers, d = hidden_dim:
+        a ``transformer_lm.KVCache``) for :meth:`prefill` / :meth:`step`.  ``done``: the int32 [B] array of the base LM's cache, so
+        that one flag ends a sequence in both; the cache keeps a ``len`` of its own.  ``device``: default ``done``'s, else the
+        current device (the folded weights live where the features are, not where the module is)."""
+        from .transformer_lm import KVCache
+        if B < 1 or cap < 1:
+            raise ValueError("new_cache: B >= 1 and cap >= 1")
+        if device is None:
+            device = done.device if done is not None else torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.GnnlmError("HGT.new_cache needs a device; gnnlm_amd has no CPU fallback")
+        c = KVCache(self.n_layers, int(B), int(cap), self.hidden_dim, device)
+        if done is not None:
+            if done.dtype != torch.int32 or done.shape != (int(B),) or done.device != c.len.device:
+                raise ValueError("new_cache: done must be int32 [B] on the cache's device")
+            c.done = done
+        return c
+
+    def _check_cache(self, G, cache, what):
+        """What the incremental entries refuse, by name, BEFORE the prelude enqueues anything (the C side refuses the same)."""
+        if self.in_dim != self.hidden_dim:
+            raise NotImplementedError(f"{what}: input adapters (ntgt_feats) are not built for incremental decoding")
+        if is_token_store(G.store):
+            raise NotImplementedError(f"{what}: a token store (token_embed, --reinit-nfeat) is not built for incremental decoding")
+        if G.fetcher is not None or G.fetched_codes is not None or getattr(G.store, "shards", None):
+            raise NotImplementedError(f"{what}: sharded and peer stores (fetched_codes / shards) are not built for incremental decoding")
+        if G.max_intra_context > 0:
+            raise NotImplementedError(f"{what}: max_intra_context > 0 (--intra-context) is not built: the decode kernel has no window")
+        if self.hidden_dim // self.n_heads not in (16, 32, 64, 128):
+            raise ValueError(f"{what}: d / n_heads = {self.hidden_dim} / {self.n_heads} must be one of 16, 32, 64, 128")
+        if cache.d != self.hidden_dim or cache.L != self.n_layers:
+            raise ValueError(f"{what}: the cache holds L = {cache.L}, d = {cache.d}; the model has n_layers = {self.n_layers}, d = {self.hidden_dim}")
+        if G.n_blocks != cache.B:
+            raise ValueError(f"{what}: the graph has n_blocks = {G.n_blocks}, the cache B = {cache.B}")
+
+    def prefill(self, G: NeighborGraph, features: Dict[str, torch.Tensor], cache):
+        """:meth:`forward` over packed prompts (``G.block_off``; block b is sequence b of ``cache``) that also writes every layer's
+        K' / V' rows into the cache and sets ``cache.len`` (``gnnlm_hgt_prefill``).  Returns what ``forward`` returns, the same bits."""
+        from .ragged import as_ragged
+        if G.block_off is None:
+            raise ValueError("prefill: the prompts are packed blocks: NeighborGraph.block_off is required")
+        self._check_cache(G, cache, "prefill")
+        tgt = (features or {}).get("tgt", G.tgt_h)
+        rg = as_ragged(G.block_off, G.ids.device if tgt is None else tgt.device)
+        longest = int(rg.lengths.max()) if rg.n_blocks else 0
+        if longest > cache.cap:
+            raise ValueError(f"prefill: a block of {longest} tokens is longer than the cache (max_len > cap = {cache.cap})")
+        import dataclasses
+        out = self._run(dataclasses.replace(G, block_off=rg), features, False, kv=cache)       # (one table upload, not two)
+        cache.steps = longest
+        return out
+
+    def step(self, G: NeighborGraph, features: Dict[str, torch.Tensor], cache, max_len=None):
+        """One decoding step (``gnnlm_hgt_step``): ``G`` holds ONE new token per sequence (``n_blocks = cache.B``, ``T = 1``, ids
+        [B, kg]), ``features['tgt']`` its base-LM row [B, d] -> ``{'tgt': [B, d]}``, the rows :meth:`forward` over the whole prefix
+        would give for these tokens (exact: SURVEY.md Appendix A / B).  The group merge and the centre-state cache work as in
+        ``forward``.  Only enqueues: a step on fixed buffers can be captured in a HIP graph (``cache.len`` lives on the device).
+        ``max_len``: the host bound on ``len + 1`` (default ``cache.steps + 1``; for a captured step, the bound over every replay)."""
+        if G.block_off is not None or G.T != 1:
+            raise ValueError("step: one new token per sequence: NeighborGraph.T (io->T) must be 1 and block_off None")
+        self._check_cache(G, cache, "step")
+        bound = cache.steps + 1 if max_len is None else int(max_len)
+        if bound < 1 or bound > cache.cap:
+            raise ValueError(f"step: max_len = {bound} outside [1, cap = {cache.cap}] (the cache is full)")
+        out = self._run(G, features, False, kv=cache, step_len=bound)
+        cache.steps += 1                                        # (replays of a captured step: the caller adds them)
+        return out
+
+    def _run(self, G, features, return_ntgt=False, kv=None, step_len=0):
+        """The one body of :meth:`forward`, :meth:`prefill` (``kv`` and ``G.block_off``) and :meth:`step` (``kv``, ``step_len``):
+        store binding, group assignment, centre-state cache and the workspace of the stream are shared; the C entry differs."""
         tgt = (features or {}).get("tgt", G.tgt_h)
         if tgt is None:
             raise ValueError("tgt features missing: pass features={'tgt': ...} or G.tgt_h")
@@ -618,8 +694,12 @@ class HGT(nn.Module):
                 out_ntgt = torch.empty(S, self.hidden_dim, device=tgt.device, dtype=torch.float32)
                 out_valid = torch.empty(S, device=tgt.device, dtype=torch.uint8)
                 io.out_ntgt, io.out_valid = out_ntgt.data_ptr(), out_valid.data_ptr()
-            need = L.gnnlm_hgt_workspace_bytes(ctypes.byref(m), ctypes.byref(io)) if ragged is None else \
-                L.gnnlm_hgt_workspace_bytes_ragged(ctypes.byref(m), ctypes.byref(io), ctypes.byref(rdesc))
+            kvd = kv.desc() if kv is not None else None
+            if kv is not None and ragged is None:
+                need = L.gnnlm_hgt_step_workspace_bytes(ctypes.byref(m), ctypes.byref(io), ctypes.byref(kvd), step_len)
+            else:
+                need = L.gnnlm_hgt_workspace_bytes(ctypes.byref(m), ctypes.byref(io)) if ragged is None else \
+                    L.gnnlm_hgt_workspace_bytes_ragged(ctypes.byref(m), ctypes.byref(io), ctypes.byref(rdesc))
             # one arena per stream: concurrent forwards on different streams must not share scratch
             key = _lib.raw_stream()
             if prep["ws"] is None:
@@ -628,7 +708,13 @@ class HGT(nn.Module):
             if ws is None or ws.numel() < need or ws.device != tgt.device:
                 prep["ws"][key] = ws = None
                 ws = prep["ws"][key] = torch.empty(need, device=tgt.device, dtype=torch.uint8)
-            if ragged is None:
+            if kv is not None and ragged is None:
+                _lib.check(L.gnnlm_hgt_step(ctypes.byref(m), ctypes.byref(io), ctypes.byref(kvd), step_len, _lib.ptr(ws), ws.numel(),
+                                            _lib.stream()), "gnnlm_hgt_step")
+            elif kv is not None:
+                _lib.check(L.gnnlm_hgt_prefill(ctypes.byref(m), ctypes.byref(io), ctypes.byref(rdesc), ctypes.byref(kvd), _lib.ptr(ws),
+                                               ws.numel(), _lib.stream()), "gnnlm_hgt_prefill")
+            elif ragged is None:
                 _lib.check(L.gnnlm_hgt_forward(ctypes.byref(m), ctypes.byref(io), _lib.ptr(ws), ws.numel(),
                                                _lib.stream()), "gnnlm_hgt_forward")
             else:

@@ -156,6 +156,33 @@ class GnnLmModel(torch.nn.Module):
             extra["orig_ratio"] = self.orig_prob_ratio                      # :1005
         return x, extra
 
+    # ---- generation: the graph decoder one token at a time (generate_gnn.GnnGenerator)
+    def _rows_graph(self, ids, store, left, right, n_blocks, T, block_off=None):
+        if self.orig_prob_ratio > 0:
+            raise NotImplementedError("orig_prob_ratio > 0 is not built for generation: the base-LM / GNN mixture is scored by eval_lm only")
+        if store is None:
+            raise ValueError("prefill_rows / step_rows need the model's store (make_store)")
+        return NeighborGraph(ids=ids, n_blocks=n_blocks, T=T, left=left, right=right, store=store, block_off=block_off)
+
+    def new_cache(self, B, cap, done=None, device=None):
+        """The graph decoder's K' / V' cache (``HGT.new_cache``); ``done`` is shared with the base LM's cache."""
+        return self.hgt_decoder.new_cache(B, cap, done=done, device=device)
+
+    def prefill_rows(self, x, ids, cache, store, left, right, block_off):
+        """Base-LM rows ``x`` [n_tok, d] of the packed prompts (``block_off``; block b is sequence b of ``cache``) and their neighbour
+        ids [n_tok, kg] -> the GNN rows [n_tok, d] (``HGT.prefill``: the cache is filled).  ``short_cut``: the rows pass through."""
+        G = self._rows_graph(ids, store, left, right, cache.B, 0, block_off)
+        if self.short_cut:
+            return x
+        return self.hgt_decoder.prefill(G, {"tgt": x}, cache)["tgt"]
+
+    def step_rows(self, x, ids, cache, store, left, right, max_len=None):
+        """One new base-LM row per sequence ``x`` [B, d] and its neighbour ids [B, kg] -> the GNN rows [B, d] (``HGT.step``)."""
+        G = self._rows_graph(ids, store, left, right, cache.B, 1)
+        if self.short_cut:
+            return x
+        return self.hgt_decoder.step(G, {"tgt": x}, cache, max_len=max_len)["tgt"]
+
     def target_log_probs(self, net_output, target):
         """log p(target) [bsz, tgt_len]: get_normalized_probs(log_probs=True) + gather
         (transformer.py:1064-1079, sequence_scorer.py:48-53,89) without the dense [T, V] tensor."""

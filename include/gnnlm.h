@@ -1465,6 +1465,51 @@ const uint8_t* gnnlm_store_codes(const gnnlm_store_t* s);
 const void* gnnlm_store_vals(const gnnlm_store_t* s);
 int gnnlm_store_destroy(gnnlm_store_t* s);
 
+/* ------------------------------------------------------------------------------------------------
+ * Incremental decoding through the HGT: generation from the GNN-LM itself.  Additive to ABI 12: new entries over the structs
+ * above, no new struct, no member moved.
+ * Replaces: HGTLayer.infer (fairseq/models/hgt.py:81-297), which the reference never reaches (extract_graph_features asserts
+ *           incremental_state is None, transformer.py:1028; infer hard-codes max_len = 512 and no growing graph is built).
+ * The step is EXACT.  In the implicit graph ntgt nodes never receive from tgt nodes, a token's star edges read only its own
+ * neighbours' context groups, and the ('tgt','intra','tgt') edges are u -> w for u <= w inside a block: the output row of
+ * token w in every layer is a function of its own input row, its own neighbour ids and the layer's folded K' / V' rows of
+ * the tokens before it.  Those rows are what the cache holds.
+ *
+ * The cache is a gnnlm_kv_cache_t of its own with L = model->n_layers and d = model->d: row u of sequence b in layer l holds
+ * the K' (V') row of token u of block b that layer l's tgt projections produce -- relation_att * relation_pri / sqrt(d_k)
+ * folded into K', relation_msg into V' (gnnlm_hgt_layer_t.wk_t / wv_t), heads side by side.  len is its own; done may point
+ * at the base LM cache's array.
+ * ---------------------------------------------------------------------------------------------- */
+/* gnnlm_hgt_forward_ragged over packed prompts that also fills the cache: block b is sequence b.  After every layer's tgt
+ * projections one copy kernel writes the K' and V' rows of block b to cache rows [0, len_b) of sequence b of that layer; a last
+ * tiny launch sets len[b] = len_b.  done is not touched.  The forward itself enqueues exactly what gnnlm_hgt_forward_ragged
+ * enqueues, so io->out_tgt is the same bits.  Workspace: gnnlm_hgt_workspace_bytes_ragged.  Refused before anything is
+ * launched, beyond what the forward refuses: blocks->n_blocks != cache->B, a longest block that the host knows to exceed
+ * cache->cap (it holds at least ceil(n_tok / n_blocks) rows), cache->d != model->d, cache->L != model->n_layers, a cache that
+ * gnnlm_decode_attn would refuse.  A block that turns out longer than cache->cap on the device is cut at cap rows (memory
+ * safety only). */
+int gnnlm_hgt_prefill(const gnnlm_hgt_t* model, const gnnlm_hgt_io_t* io, const gnnlm_ragged_t* blocks,
+                      const gnnlm_kv_cache_t* cache, void* workspace, size_t workspace_bytes, void* stream);
+/* One decoding step: `io` holds ONE new token per sequence (io->n_blocks = cache->B, io->T = 1; tgt_feats, ids and out_tgt
+ * have B rows).  Per layer it runs gnnlm_hgt_forward's loop with one substitution: the causal branch is gnnlm_decode_attn of
+ * the new q row against the layer's cache rows -- which appends the new K' / V' rows -- and enters the message sum through
+ * the residual operand of the star branch's output GEMM.  The star branch, the ntgt updates, the group merge (group_ids /
+ * n_unique_dev), state_cache and row_table are those of the forward.  One last tiny launch does len[b] += 1 for the rows that
+ * are not done and in range.
+ * A row with done[b] != 0, or len[b] outside [0, min(cap, max_len)), follows gnnlm_decode_attn's contract: nothing is
+ * appended, an out-of-range row is counted once in *cache->n_bad, and its out_tgt row means nothing.
+ * `max_len` is HOST data, the rule of gnnlm_tlm_step_io_t.max_len: an upper bound on len[b] + 1 over every execution of the
+ * enqueued work.  The call only enqueues: no allocation, no host read, no synchronisation -- it can be captured in a HIP graph.
+ * GNNLM_E_INVALID before anything is launched, gnnlm_last_error() naming the field: io->T != 1, io->n_blocks != cache->B,
+ * model->max_intra_context > 0 (the decode kernel has no window), io->ntgt_feats (input adapters), io->fetched_codes /
+ * model->shards (sharded and peer stores), model->token_embed (--reinit-nfeat), io->out_ntgt / out_valid, d / n_heads outside
+ * {16, 32, 64, 128}, max_len outside [1, cache->cap], cache->d != model->d, cache->L != model->n_layers, and everything
+ * gnnlm_hgt_forward and gnnlm_decode_attn refuse. */
+size_t gnnlm_hgt_step_workspace_bytes(const gnnlm_hgt_t* model, const gnnlm_hgt_io_t* io, const gnnlm_kv_cache_t* cache,
+                                      int32_t max_len);
+int gnnlm_hgt_step(const gnnlm_hgt_t* model, const gnnlm_hgt_io_t* io, const gnnlm_kv_cache_t* cache, int32_t max_len,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
